@@ -9,11 +9,15 @@ N > 1, one RCCL all-gather of that table across ranks.  Msample/s = complex inpu
 (SURVEY.md 8d).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--streams D] [--mode table|stream] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  The default run (N = 1) also times, inside the same process, the other BASELINE
-configurations as sub-results: config 2 (two streams), the same 64 streams with the corrected stream written
-(18 B/sample) and the scanner path at 200 and 12 800 captures (configs 3 / 5 per GPU).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the last step's outputs if
+--dump-outputs is given and prints the line.  With --full the run (N = 1) also times, inside the same process, the other
+BASELINE configurations as sub-results: config 2 (two streams), the same 64 streams with the corrected stream written
+(18 B/sample) and the scanner path at 200 and 12 800 captures (configs 3 / 5 per GPU); it also checks rows against the
+CPU oracle, times the variants of the headline loop, runs the kernel event passes and the CPU baselines, and reports
+the rooflines.
 """
 from __future__ import annotations
 
@@ -133,6 +137,13 @@ def parse():
     ap.add_argument("--cache-streams", default=None,
                     help="keep the generated synthetic streams in this .npy file and reuse them (profiling passes that rerun the "
                          "same command; generation is deterministic, the file only saves the host time)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the pre-warm-less figure, the depth-1 / sustained / one-buffer "
+                         "variants, the oracle and all-gather checks, the kernel event passes, rooflines, sub-results and CPU "
+                         "baselines (each still subject to --no-kernel-events / --no-sub / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; a fixed "
+                         "sample of r_correct in stream mode, and of the streams past 64 MB in all)")
     return ap.parse_args()
 
 
@@ -144,11 +155,11 @@ def _gen_one(job):
 
 
 def gen_streams(jobs):
-    """Synthetic captures for `jobs` = [(dongle, frames, kwargs)], one worker process per host core (0.5 s of NumPy per
-    stream).  Called BEFORE this process touches the GPU: the workers are forked from a process without HIP state."""
+    """Synthetic captures for `jobs` = [(dongle, frames, kwargs)], one worker process per host core, at most 16 (0.5 s of
+    NumPy per stream).  Called BEFORE this process touches the GPU: the workers are forked from a process without HIP state."""
     ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     world = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))
-    workers = max(1, min(ncpu // world, 32, len(jobs)))      # under torchrun every rank of the node generates at the same time
+    workers = max(1, min(ncpu // world, 16, len(jobs)))      # under torchrun every rank of the node generates at the same time
     if workers == 1:
         return [_gen_one(j) for j in jobs]
     from concurrent.futures import ProcessPoolExecutor
@@ -311,7 +322,7 @@ def main():
         ncand = nd + nd // 3 + 8                             # about one synthetic seed in eight is rejected by the fine search
         cand_jobs = [(100000 * rank + lo + i, frames, {}) for i in range(ncand)]
         jobs = list(cand_jobs)
-        n_mixed = 64 if (world == 1 and not args.no_sub and args.mode == "table") else 0
+        n_mixed = 64 if (args.full and world == 1 and not args.no_sub and args.mode == "table") else 0
         jobs += [(5000 + i, frames, kw) for i, kw in enumerate(mixed_kwargs(n_mixed, 5000))]
         cache = args.cache_streams and f"{args.cache_streams}.r{rank}.n{len(jobs)}.f{frames}.npy"
         if cache and os.path.exists(cache):
@@ -440,7 +451,8 @@ def main():
     # idle, and W = 3 steps (0.55 ms) do not bring it to the state a service runs in -- the same step, --prewarm-steps times,
     # before the W warm-up steps of the contract (20 timed steps read 0.184 ms without this, 0.174 with it and in every longer run)
     # ... and the same W + K steps WITHOUT them first (`ms_per_step_no_prewarm`: the protocol of rounds 1-3, kept in the line so
-    # that rounds stay comparable -- VERDICT r4 #2)
+    # that rounds stay comparable -- VERDICT r4 #2; a plain run does these steps too, so that its headline follows the
+    # same earlier steps, and leaves their figure to --full)
     elapsed_cold = time_steps(torch, dev, step, args.steps, args.warmup, fence) if args.prewarm_steps > 0 else None
     for _ in range(args.prewarm_steps):
         step()
@@ -480,11 +492,13 @@ def main():
     last_b = (nstep[0] - 1) % NBUF
     last = (nstep[0] - 1) % NG                                       # (gather buffer pair of the last step)
     table = cal.table(last_b).numpy().copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, calib_outputs(torch, cal, last_b, table, host_gath[last].numpy() if use_dist else None), D)
     # every output set of the loop holds the same table: the steps in flight did not disturb each other
-    tables_identical = all(bool(np.array_equal(cal.table(b).numpy(), table, equal_nan=True)) for b in range(min(NBUF, nstep[0])))
+    tables_identical = all(bool(np.array_equal(cal.table(b).numpy(), table, equal_nan=True)) for b in range(min(NBUF, nstep[0]))) if args.full else None
     # ... and the same K steps (a) one at a time, (b) on ONE raw buffer (which the Infinity Cache then serves), single rank only
     variants = {}
-    if not use_dist and args.mode == "table" and os.environ.get("GSMCAL_BENCH_NO_VARIANTS") != "1":     # (=1: profiler passes that want the headline loop last)
+    if args.full and not use_dist and args.mode == "table" and os.environ.get("GSMCAL_BENCH_NO_VARIANTS") != "1":     # (=1: profiler passes that want the headline loop last)
         def timed_variant(d_, nraw_, k_=None):
             k_ = k_ or args.steps
             ctx.set_pipeline_depth(d_)
@@ -507,25 +521,25 @@ def main():
                 tables_identical = tables_identical and s3
         loop["nraw"] = nraw
     ctx.set_pipeline_depth(1)                                        # everything below (checks, event passes, sub-results): one call at a time
-    cal.launch(last_b, r=0)
-    ctx.sync()
-    assert np.array_equal(cal.table(last_b).numpy(), table, equal_nan=True)
+    if args.full:
+        cal.launch(last_b, r=0)
+        ctx.sync()
+        assert np.array_equal(cal.table(last_b).numpy(), table, equal_nan=True)
 
-    # ---- every rank checks rows of its OWN shard against the CPU oracle before anything is reported, whatever the
-    # flags (the check used to ride on the CPU-baseline leg) ----
-    from oracle import gsmcal_oracle as oracle
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import parity
-    det = gsmcal.last_batch_details(min(D, nd), ctx=ctx)
-    pos_host = cal.pos_ts[last_b].cpu().numpy()
+    # ---- --full: every rank checks rows of its OWN shard against the CPU oracle before anything is reported, whatever the
+    # other flags (the check used to ride on the CPU-baseline leg) ----
     n_rank_checked = 0
-    orc_rows = {}
-    for i in range(min(nd, 4)):
-        orc_rows[i] = oracle.calibrate_stream(distinct[i], coef, ts, fc)
-        parity.compare_stream(orc_rows[i], table[i], det, i, _pos_info(pos_host, table, i))
-        n_rank_checked += 1
+    if args.full:
+        from oracle import gsmcal_oracle as oracle
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import parity
+        det = gsmcal.last_batch_details(min(D, nd), ctx=ctx)
+        pos_host = cal.pos_ts[last_b].cpu().numpy()
+        for i in range(min(nd, 4)):
+            parity.compare_stream(oracle.calibrate_stream(distinct[i], coef, ts, fc), table[i], det, i, _pos_info(pos_host, table, i))
+            n_rank_checked += 1
     gathered_ok = None
-    if use_dist:
+    if use_dist and args.full:
         # the collective's result, checked against what every rank says it sent: digests of the local tables travel
         # through a second, independent group (gloo over TCP), and each rank compares every peer's block of the
         # RCCL-gathered table with that peer's digest -- not only its own rows (gsmcal.dist.check_gathered_table)
@@ -542,14 +556,15 @@ def main():
         "metric": "IQ Msamples/s through FCCH+SCH calib",
         "value": round(value, 3), "unit": "Msample/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 4), "prewarm_steps": args.prewarm_steps,
-        "ms_per_step_no_prewarm": round(1e3 * (elapsed_cold if elapsed_cold is not None else elapsed) / args.steps, 4),
-        "ms_per_step_no_prewarm_what": "the same W + K steps, timed FIRST (before the pre-warm steps" + (" and before the placement autotune: "
-                                       "collective in line" if use_dist else "") + "); the headline follows W + K + prewarm_steps earlier steps",
+        **({"ms_per_step_no_prewarm": round(1e3 * (elapsed_cold if elapsed_cold is not None else elapsed) / args.steps, 4),
+            "ms_per_step_no_prewarm_what": "the same W + K steps, timed FIRST (before the pre-warm steps" + (" and before the placement autotune: "
+                                           "collective in line" if use_dist else "") + "); the headline follows W + K + prewarm_steps earlier steps"}
+           if args.full else {}),
         "pipeline_depth": depth, **({"one_in_flight": "--one-in-flight: the host fenced behind every step (a profiler pass, not the headline)"}
                                     if args.one_in_flight else {}),
         "input": (f"rotated over {nraw} buffers ({nraw} x {D * 2 * N / 1e6:.1f} MB: beyond the 256 MB Infinity Cache, every raw byte from HBM)"
                   if nraw > 1 else "one raw buffer re-read every step (served by the Infinity Cache)"),
-        "tables_identical": tables_identical, **variants,
+        **({"tables_identical": tables_identical} if args.full else {}), **variants,
         "higher_is_better": True, "scaling": args.scaling,
         "vs_baseline": None, "dtype": "f64",
         "data": f"synthetic 8x-oversampled GSM BCCH-carrier uint8 IQ (seed {synth.DEFAULT_SEED}); {nd} distinct "
@@ -568,7 +583,7 @@ def main():
         out["config"]["collective_fallback_from_native"] = gather_fallback
     if autotune:
         out["config"]["collective_autotune"] = autotune
-    if rank == 0:
+    if rank == 0 and args.full:
         path_gbs = value * 1e6 * bps / 1e9
         roof = {"bound": "hbm", "achieved": round(path_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(path_gbs / HBM_PEAK_GBS, 4), "traffic": None,
@@ -651,9 +666,9 @@ def main():
                                              f"(NumPy/SciPy fp64 restatement, 1 thread) in {t_cpu:.1f} s"}
             out["parity_checked_streams"] = max(checked, n_rank_checked)
             out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
-            # the same restatement on every host core (one worker process per core over independent streams): SURVEY 8d
+            # the same restatement on every host core, at most 16 (one worker process per core over independent streams): SURVEY 8d
             # asks for the all-core figure next to the single-thread one
-            ncpu = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+            ncpu = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
             if ncpu > 1:
                 from concurrent.futures import ProcessPoolExecutor
                 nrun = min(4 * ncpu, 1024)
@@ -666,6 +681,7 @@ def main():
                                                  "kind": "port",
                                                  "sample": f"{nrun} streams over {ncpu} worker processes in {t_all:.1f} s"}
                 out["speedup_vs_cpu_all_cores"] = round(value / out["cpu_baseline_all_cores"]["value"], 1)
+    if rank == 0:
         if "parity_checked_streams" not in out:
             out["parity_checked_streams"] = n_rank_checked
         print(json.dumps(out))
@@ -1037,7 +1053,7 @@ def bench_single_rank_collective(args, D):
     env["GSMCAL_FORCE_DIST"] = "1"
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--streams", str(D), "--frames", str(args.frames), "--distinct", str(args.distinct),
-           "--no-sub", "--no-cpu-baseline", "--no-kernel-events"]
+           "--full", "--no-sub", "--no-cpu-baseline", "--no-kernel-events"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     if p.returncode != 0 or not line:
@@ -1114,12 +1130,14 @@ def bench_ingest(torch, gsmcal, dev, ctx, D=256, nbatch=8):
 
 
 def bench_scan(args, torch, gsmcal, dev, ctx, D, frames, distinct, steps, warmup, cpu=True, use_dist=False, world=1, rank=0,
-               sizes=None, tg=None, first_unit=None):
+               sizes=None, tg=None, first_unit=None, full=True, outputs=None):
     """Scanner path (BASELINE configs 3/5): D captures resident in HBM -> snr, num_hit per capture on the host.
     N > 1 (multi_rtl_sdr_gsm_FCCH_scanner.m:60-65,163-186: the ARFCN split across dongles and the one table every rank needs):
     `sizes` = captures per rank, `tg` = the table gatherer (2 columns: snr, num_hit), `first_unit` = this rank's first global
     capture index; each step ends with ONE all-gather of the (snr, num_hit) table, the GATHERED table goes to the host and is
-    digest-checked against every rank's own rows (gsmcal.dist.check_gathered_table), as in the calibration workload."""
+    digest-checked against every rank's own rows (gsmcal.dist.check_gathered_table), as in the calibration workload.
+    full=False: the timed steps only (no one-call-at-a-time figure, event pass, checks or CPU baseline); `outputs`, a dict,
+    receives the last timed step's table."""
     import torch.distributed as dist
 
     from gsmcal import synth
@@ -1175,7 +1193,7 @@ def bench_scan(args, torch, gsmcal, dev, ctx, D, frames, distinct, steps, warmup
         torch.cuda.synchronize(dev)
 
     elapsed1 = None
-    if pdepth > 1 and not use_dist:                                  # one call at a time first (reported beside the figure)
+    if full and pdepth > 1 and not use_dist:                         # one call at a time first (reported beside the figure)
         elapsed1 = time_steps(torch, dev, step, steps, warmup, fence, prewarm_s=SUB_PREWARM_S)
     ctx.set_pipeline_depth(pdepth)
     elapsed = time_steps(torch, dev, step, steps, warmup + pdepth - 1, fence, prewarm_s=0.0 if use_dist else SUB_PREWARM_S)
@@ -1189,6 +1207,13 @@ def bench_scan(args, torch, gsmcal, dev, ctx, D, frames, distinct, steps, warmup
         elapsed = float(tt.item())
         last = (nstep[0] - 1) % NB
         res = out_t[last].cpu().numpy()
+        if outputs is not None:
+            outputs.update(table=res.copy(), table_gathered=host_gath[last].numpy().copy())
+    else:
+        res = host_out.numpy().copy()
+        if outputs is not None:
+            outputs["table"] = res.copy()
+    if use_dist and full:
         # every rank checks every peer's block of the gathered table against that peer's own digest (independent gloo group)
         from gsmcal import dist as gdist
         chk = dist.new_group(backend="gloo")
@@ -1197,8 +1222,6 @@ def bench_scan(args, torch, gsmcal, dev, ctx, D, frames, distinct, steps, warmup
         off = sum(sizes[:rank])
         assert np.array_equal(g_all[off: off + D], res, equal_nan=True), "gathered scan table differs from this rank's rows"
         gathered_ok = True
-    else:
-        res = host_out.numpy().copy()
     value = sum(sizes) * N * steps / elapsed / 1e6
     out = {"ms_per_step": round(1e3 * elapsed / steps, 4), "value": round(value, 3), "pipeline_depth": pdepth,
            **({"ms_per_step_depth1": round(1e3 * elapsed1 / steps, 4)} if elapsed1 is not None else {}),
@@ -1206,6 +1229,9 @@ def bench_scan(args, torch, gsmcal, dev, ctx, D, frames, distinct, steps, warmup
            "path_frac_of_hbm": round(value * 1e6 * 2.25 / 1e9 / HBM_PEAK_GBS / world, 4),
            "captures_with_hits": int(np.sum(res[:, 1] > 0)),
            "gathered_table_checked_against_every_rank": gathered_ok}
+    if not full:
+        del raw_t
+        return out
     if not args.no_kernel_events and rank == 0:
         def launch_only():                                   # (no collective in here: only rank 0 runs this pass)
             ctx.check(ctx.lib.gsmcal_fcch_scan_batch_dev(ctx.h, C.c_void_p(raw_t.data_ptr()), D, N, cp, len(coef),
@@ -1260,8 +1286,12 @@ def bench_scan_main(args, rank, world, dev, use_dist):
     if D < 1:
         raise SystemExit("more ranks than captures")
     tg, gather_kind, ncomm, gather_fallback = setup_gatherer(torch, gsmcal, gdist, ctx, dev, stream, local_rank, sizes, 2, pairs=4) if use_dist else (None, "none", None, None)
+    outputs = {}
     r = bench_scan(args, torch, gsmcal, dev, ctx, D, args.frames, args.distinct, args.steps, args.warmup,
-                   cpu=not args.no_cpu_baseline and world == 1, use_dist=use_dist, world=world, rank=rank, sizes=sizes, tg=tg, first_unit=first_unit)
+                   cpu=not args.no_cpu_baseline and world == 1, use_dist=use_dist, world=world, rank=rank, sizes=sizes, tg=tg, first_unit=first_unit,
+                   full=args.full, outputs=outputs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, D)
     N = args.frames * 10000
     out = {"metric": "IQ Msamples/s through FCCH scanner path", "value": r["value"], "unit": "Msample/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
@@ -1287,6 +1317,40 @@ def bench_scan_main(args, rank, world, dev, use_dist):
         print(json.dumps(out))
     if use_dist:
         finish_dist(torch, dist, gdist, dev, ncomm, gather_fallback)
+
+
+DUMP_LIMIT_BYTES = 60 << 20      # (under 64 MB with the .npy headers)
+
+
+def calib_outputs(torch, cal, b, table, gathered=None):
+    """What a caller of the timed calibration step receives from output set b: the table, the burst positions (pos_info as the
+    library writes it, [D][2][MAX_POS_ROWS]), r_len and, in stream mode, a fixed seeded sample of r_correct's samples (the whole
+    array is 16 B per sample), the same sample positions in every stream."""
+    out = {"table": table, "pos_info": cal.pos_ts[b].cpu().numpy(), "r_len": cal.rlen_ts[b].cpu().numpy().astype(np.float64)}
+    if gathered is not None:
+        out["table_gathered"] = gathered
+    if cal.r_ts is not None:
+        k = max(1, min(cal.N, (DUMP_LIMIT_BYTES // 2) // (16 * cal.D)))
+        idx = np.sort(np.random.default_rng(1234).choice(cal.N, size=k, replace=False))
+        out["r_correct_sample"] = cal.r_ts[b][:, torch.from_numpy(idx).to(cal.dev), :].cpu().numpy()
+        out["r_correct_sample_index"] = idx.astype(np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays, rows):
+    """--dump-outputs: one DIR/<name>.npy per array, float64, at most DUMP_LIMIT_BYTES in all.  Past that, every array with
+    `rows` rows (one per stream / capture) keeps the same fixed, seeded sample of its rows, listed in DIR/rows.npy."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    per_row = sum(a.nbytes for a in arrays.values() if a.ndim and len(a) == rows) / rows
+    other = sum(a.nbytes for a in arrays.values() if not (a.ndim and len(a) == rows))
+    if other + per_row * rows > DUMP_LIMIT_BYTES:
+        keep = max(1, min(rows, int((DUMP_LIMIT_BYTES - other) // (per_row + 8))))
+        sample = np.sort(np.random.default_rng(4321).choice(rows, size=keep, replace=False))
+        arrays = {k: (a[sample] if a.ndim and len(a) == rows else a) for k, a in arrays.items()}
+        arrays["rows"] = sample.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def _oracle_warm(_):

@@ -41,12 +41,17 @@ def test_total_ppm_calculation_host_entry_point(gsmcal_mod):
         assert (math.isinf(a) and math.isinf(b)) or a == b
 
 
-def test_no_cpu_fallback_context_fails_loudly_without_gpu(gsmcal_mod):
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is present")
-    with pytest.raises(gsmcal_mod.GsmcalError):
-        gsmcal_mod.Context(0)
+def test_no_cpu_fallback_context_fails_loudly_without_gpu():
+    """In a child process that sees no device (HIP_VISIBLE_DEVICES=-1 hides any GPU the machine has) creating a context
+    raises GsmcalError: there is no CPU path to fall back to."""
+    import subprocess
+    import sys
+    code = ("import sys, gsmcal\n"
+            "try:\n    gsmcal.Context(0)\nexcept gsmcal.GsmcalError as e:\n    print('GsmcalError:', e)\n    sys.exit(0)\n"
+            "sys.exit(3)\n")
+    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, HIP_VISIBLE_DEVICES="-1"),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "GsmcalError:" in p.stdout, p.stdout + p.stderr[-2000:]
 
 
 def test_product_package_does_not_import_the_oracle():

@@ -19,11 +19,11 @@ def test_host_side_under_address_sanitizer(tmp_path):
         pytest.skip("ROCm toolchain not present")
     lib = tmp_path / "libgsmcal_asan.so"
     src = os.path.join(ROOT, "multi-rtl-sdr-calibration_amd", "csrc", "gsmcal.hip")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-shared", "-fPIC", "-fsanitize=address",
-                        "-fno-gpu-sanitize", "-shared-libsan", src, "-o", str(lib), "-ldl"], capture_output=True, text=True)
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-shared", "-fPIC",
+                        "-fsanitize=address", "-fno-gpu-sanitize", "-shared-libsan", src, "-o", str(lib), "-ldl"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     exe = tmp_path / "asan_driver"
-    r = subprocess.run([clang, "-fsanitize=address", "-shared-libsan", "-I" + os.path.join(ROOT, "include"),
+    r = subprocess.run([clang, "-fsanitize=address", "-fno-gpu-sanitize", "-shared-libsan", "-I" + os.path.join(ROOT, "include"),
                         os.path.join(ROOT, "tests", "asan_driver.c"), "-o", str(exe), "-L" + str(tmp_path), "-lgsmcal_asan",
                         "-Wl,-rpath," + str(tmp_path), "-lm"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -190,7 +190,7 @@ def test_bench_distributed_step_on_one_rank_and_its_fall_back(fail_native):
     if fail_native:
         env["GSMCAL_BENCH_FAIL_NATIVE"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--streams", "4", "--distinct", "4",
-           "--no-sub", "--no-cpu-baseline", "--no-kernel-events"]
+           "--full", "--no-sub", "--no-cpu-baseline", "--no-kernel-events"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     assert p.returncode == 0 and line, p.stderr[-2000:]
@@ -203,6 +203,62 @@ def test_bench_distributed_step_on_one_rank_and_its_fall_back(fail_native):
         assert "GSMCAL_BENCH_FAIL_NATIVE" in cfg["collective_fallback_from_native"]
     else:
         assert "native RCCL" in cfg["collective"] and "collective_fallback_from_native" not in cfg
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_step_and_repeats(tmp_path, g_mod, ctx):
+    """A plain `bench.py --dump-outputs DIR` run (no --full): the line carries the headline keys and none of what --full adds,
+    DIR holds the last timed step's outputs as float64 .npy files within 64 MB (stream mode: a fixed sample of r_correct), a
+    second run with the same arguments writes the same values, and they are bit for bit what the library's host entry point
+    returns for the same streams (bench.py's selection: the first 4 seeds of rank 0's range that the chain calibrates)."""
+    import json
+    import subprocess
+    import sys
+    g = g_mod
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm-steps", "2",
+           "--streams", "4", "--distinct", "4", "--mode", "stream"]
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run(cmd + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+        assert p.returncode == 0 and line, p.stderr[-2000:]
+        r = json.loads(line[-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in r, k
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        assert not any(k in r for k in ("sub_results", "roofline", "cpu_baseline", "tables_identical", "ms_per_step_no_prewarm"))
+        files = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+        assert set(files) == {"table", "pos_info", "r_len", "r_correct_sample", "r_correct_sample_index"}
+        assert all(a.dtype == np.float64 for a in files.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        assert files["table"].shape == (4, g.TABLE_COLS) and r["config"]["streams_calibrated_ok"] == 4
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name], equal_nan=True), name
+    # the same streams through gsmcal.calibrate_batch
+    coef = g.synth.fir1(46, 200e3 / g.synth.FS)
+    ts = g.synth.sch_training_sequence()
+    picked = []
+    for i in range(64):                                      # rank 0's candidate seeds: dongles 0, 1, 2, ...
+        raw = g.synth.make_stream(dongle=i, num_frames=102)[0]
+        if g.calibrate_batch(raw[None], coef, ts, 957.4e6, ctx=ctx)["table"][0, 9] == 0:
+            picked.append(raw)
+        if len(picked) == 4:
+            break
+    ref = g.calibrate_batch(np.stack(picked), coef, ts, 957.4e6, want_r=True, ctx=ctx)
+    got = dumps[0]
+    assert np.array_equal(got["table"], ref["table"], equal_nan=True)
+    assert np.all(got["table"][:, 9] == 0) and np.all(np.isfinite(got["table"][:, 4:6])) and np.all(got["table"][:, 4:6] != 0)
+    assert np.array_equal(got["r_len"], ref["r_len"].astype(np.float64))
+    for i in range(4):
+        k = int(got["table"][i, 7])
+        assert k > 0 and np.array_equal(got["pos_info"][i, :, :k], ref["pos_info_raw"][i, :, :k]), i
+    idx = got["r_correct_sample_index"].astype(np.int64)
+    assert len(idx) > 0 and np.all(np.diff(idx) > 0)
+    want = ref["r_correct"][:, idx]
+    assert np.array_equal(got["r_correct_sample"], np.stack([want.real, want.imag], axis=-1))
+    assert np.any(got["r_correct_sample"] != 0)
 
 
 def test_scanner_calls_in_flight_change_no_bit(g_mod, ctx):
@@ -257,7 +313,7 @@ def test_bench_scan_workload_distributed_step_on_one_rank(fail_native):
     if fail_native:
         env["GSMCAL_BENCH_FAIL_NATIVE"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "scan", "--steps", "3", "--warmup", "1", "--streams", "50",
-           "--frames", "64", "--distinct", "8", "--no-cpu-baseline", "--no-kernel-events"]
+           "--frames", "64", "--distinct", "8", "--full", "--no-cpu-baseline", "--no-kernel-events"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     assert p.returncode == 0 and line, p.stderr[-2000:]

@@ -5,7 +5,7 @@
 #
 #   gpurun --timeout 900 -- 'tools/ab_session.sh NAME REPS "label|ENV=1 ENV2=x|bench args" "label2||bench args" ...'
 #
-# Every variant runs `python bench.py <bench args> --no-cpu-baseline --no-sub` with its environment (GSMCAL_* switches,
+# Every variant runs `python bench.py <bench args> --full --no-cpu-baseline --no-sub` with its environment (GSMCAL_* switches,
 # GSMCAL_LIB=<another build> for an A/B of two libraries), REPS times round-robin; one line per run goes to
 # gpurun_out/NAME.txt: label, ms per step, calibrated streams, the six longest kernels of the untimed event pass.
 # Empty bench args default to the headline shape with 200 timed steps.
@@ -17,7 +17,7 @@ for rep in $(seq 1 "$REPS"); do
   for v in "$@"; do
     IFS='|' read -r label envs bargs <<< "$v"
     [ -z "$bargs" ] && bargs="--steps 200 --warmup 20"
-    line=$(env $envs timeout 600 python bench.py $bargs --no-cpu-baseline --no-sub --cache-streams /tmp/ab_streams.npy 2>>"gpurun_out/$NAME.err" | python -c "
+    line=$(env $envs timeout 600 python bench.py $bargs --full --no-cpu-baseline --no-sub --cache-streams /tmp/ab_streams.npy 2>>"${O%.txt}.err" | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

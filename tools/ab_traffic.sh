@@ -17,7 +17,7 @@ L=$R/multi-rtl-sdr-calibration_amd/lib
 OUT=$R/profiles/${RT}_ab_traffic.txt
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-sub --no-kernel-events --cache-streams /tmp/gsmcal_streams --steps 20 --warmup 3"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-sub --no-kernel-events --cache-streams /tmp/gsmcal_streams --steps 20 --warmup 3"
 $B > /dev/null 2>&1      # (fills the stream cache)
 : > $OUT
 echo "# tools/ab_traffic.sh $RT: 64 distinct streams x 1 020 000, table mode, raw batch rotated over 4 buffers; algorithmic 130.56 MB per step" >> $OUT

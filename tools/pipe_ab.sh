@@ -8,7 +8,7 @@ set -u
 tag=${1:-pipe_ab}; shift
 out=gpurun_out/$tag
 mkdir -p "$out"
-B="python bench.py --no-sub --no-cpu-baseline --no-kernel-events --cache-streams /tmp/gsmcal_streams"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-kernel-events --cache-streams /tmp/gsmcal_streams"
 if [ $# -eq 0 ]; then set -- 1:1 2:1 3:1 4:1 5:1 6:1 8:1 2:2 3:3 4:1; fi
 for cfg in "$@"; do
   d=${cfg%%:*}; s=${cfg##*:}

@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 export GSMCAL_BENCH_NO_VARIANTS=1     # (the headline loop only: no depth-2 / one-buffer variants behind it)
-B="python3 $R/bench.py --no-cpu-baseline --no-sub --no-kernel-events --cache-streams /tmp/gsmcal_streams"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-sub --no-kernel-events --cache-streams /tmp/gsmcal_streams"
 CAL="$B --steps 20 --warmup 3"
 CALC="$CAL --prewarm-steps 0"     # counter passes: the counters do not depend on the clock state, and 256 fewer steps keep the .db files small
 BIG="$B --steps 10 --warmup 3 --streams 1024 --prewarm-steps 20"
