@@ -261,6 +261,18 @@ int gsmcal_frontend_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, co
 int gsmcal_frontend_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, const double* coef,
                               int ntaps, int decim, double* d_out);
 
+/* Band power of D captures: power[d] = mean(abs(filter(coef,1,raw2iq(s_d))(1:decim:end)).^2)
+ * (multi_rtl_sdr_split_scanner.m:154-156, multi_rtl_sdr_diversity_scanner.m:156-158; coef = [1], decim = 1:
+ * scan_band_power_spectrum.m:80-84).  raw: D x 2N bytes, capture-major as above.  power: [D] doubles.
+ * 1 <= ntaps <= 1024, decim >= 1, anything else GSMCAL_E_ARG.  The DC of raw2iq.m:8 is removed as exact integer sums, so a
+ * constant capture gives exactly 0; a capture's result is bit-identical at any position in a batch of any size.  The calls
+ * use workspaces of their own: gsmcal_last_batch_details / _snr and gsmcal_last_call_report keep answering for the call
+ * before.  _dev: enqueues on the context's stream only; d_power may be device or pinned host memory. */
+int gsmcal_band_power_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, const double* coef,
+                            int ntaps, int decim, double* power);
+int gsmcal_band_power_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, const double* coef,
+                                int ntaps, int decim, double* d_power);
+
 /* Scanner detect loop for D captures (multi_rtl_sdr_gsm_FCCH_scanner.m:132-135 front end,
  * :164 FCCH_coarse_position, :168-185 acceptance).  Outputs per capture: snr, num_hit (as the
  * driver's arrays), optional positions/snrs [D][GSMCAL_MAX_HITS] and counts [D] (NULL to skip). */

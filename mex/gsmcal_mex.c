@@ -7,13 +7,14 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan; do
+ *            carrier_correct_post_SCH total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan gsmcal_band_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
  *
- * The last two are not shadows of .m files: they are the fused entry points (one call per driver loop body)
+ * The last three are not shadows of .m files: they are the fused entry points (one call per driver loop body)
  *   [table, pos_info] = gsmcal_calibrate(s, coef, sch_training_sequence, freq)   replaces gsm_sync_demod.m:107-124
  *   [snr, num_hit]    = gsmcal_fcch_scan(s, coef)                                replaces ..FCCH_scanner.m:132-135,163-186
+ *   power_spectrum    = gsmcal_band_power(s_all, coef, decimate_ratio)          replaces ..split_scanner.m:154-156
  * with s the 2N x D uint8 matrix fread() delivers (gsm_sync_demod.m:96; pass uint8(s) if it was read as double).
  * tests/test_abi_cpu.py compiles every target against a declaration-only mex.h (tests/mex_stub) as a prototype check.
  *
@@ -296,6 +297,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             "gsmcal_fcch_scan");
         if (nlhs > 1) plhs[1] = nh;
     }
+#elif defined(GSMCAL_FN_gsmcal_band_power)
+    /* power = gsmcal_band_power(s_all, coef, decimate_ratio)     multi_rtl_sdr_split_scanner.m:154-156 (diversity_scanner.m:
+     * 156-158 per dongle) for all captures: mean(abs(r_flt(1:decimate_ratio:end,:)).^2, 1) with r_flt = filter(coef,1,raw2iq(s_all))
+     * s_all: 2N x D uint8, one column per capture; coef: real taps; power: 1 x D linear */
+    mwSize rows2n = mxGetM(prhs[0]), d = mxGetN(prhs[0]);
+    if (!mxIsUint8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s_all must be uint8 (the bytes fread(...,'uint8') delivers)");
+    if (nrhs < 3 || mxIsComplex(prhs[1])) mexErrMsgIdAndTxt("gsmcal:args", "usage: power = gsmcal_band_power(s_all, coef, decimate_ratio)");
+    plhs[0] = mxCreateDoubleMatrix(1, d, mxREAL);
+    chk(gsmcal_band_power_batch(ctx(), U8_PTR(prhs[0]), (int)d, (long)(rows2n / 2), REAL_PTR(prhs[1]),
+                                (int)mxGetNumberOfElements(prhs[1]), (int)mxGetScalar(prhs[2]), REAL_PTR(plhs[0])),
+        "gsmcal_band_power");
 #else
 #error "define one GSMCAL_FN_<function> (see the header comment)"
 #endif

@@ -61,6 +61,10 @@ SIGNATURES = {
                                         c_double_p]),
     "gsmcal_frontend_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                             C.c_void_p]),
+    "gsmcal_band_power_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
+                                          c_double_p]),
+    "gsmcal_band_power_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
+                                              C.c_void_p]),
     "gsmcal_fcch_scan_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_int_p]),
     "gsmcal_fcch_scan_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int,

@@ -428,6 +428,63 @@ def frontend_batch(raw, coef, decim, ctx=None):
     return out
 
 
+def band_power_batch(raw, coef, decim, ctx=None):
+    """raw: (D, 2N) uint8 -> (D,) linear band power mean(abs(filter(coef,1,raw2iq(s))(1:decim:end)).^2)
+    (multi_rtl_sdr_split_scanner.m:154-156; coef = [1], decim = 1: scan_band_power_spectrum.m:80-84)."""
+    ctx = ctx or default_context()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    if raw.ndim != 2 or raw.shape[1] % 2:
+        raise ValueError("raw must be (D, 2N) bytes")
+    d, two_n = raw.shape
+    coef = np.ascontiguousarray(np.atleast_1d(np.asarray(coef, dtype=np.float64)).ravel())
+    out = np.empty(d)
+    ctx.check(ctx.lib.gsmcal_band_power_batch(ctx.h, raw.ctypes.data_as(_lib.c_u8_p), d, two_n // 2, _dp(coef), len(coef),
+                                              int(decim), _dp(out)), "band_power_batch")
+    return out
+
+
+def band_power_batch_dev(d_raw, d, n, coef, decim, d_power, ctx=None):
+    """Device-pointer form of band_power_batch: only enqueues on the context's stream (ctx.sync() before reading).
+    d_raw: [d][2n] bytes; d_power: [d] doubles in device or pinned host memory."""
+    ctx = ctx or default_context()
+    coef = np.ascontiguousarray(np.atleast_1d(np.asarray(coef, dtype=np.float64)).ravel())
+    ctx.check(ctx.lib.gsmcal_band_power_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), _dp(coef), len(coef), int(decim),
+                                                  C.c_void_p(d_power)), "band_power_batch_dev")
+
+
+def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,
+                        ctx=None):
+    """multi_rtl_sdr_split_scanner.m:150-177 after the captures: s_all is the script's (2*num_samples, num_dongle *
+    num_freq_per_sub_band) uint8 matrix (column = capture, units in dist.scan_frequency_plan's order).  Returns the fields
+    the script saves (dist.split_spectrum_record), power_spectrum linear."""
+    from . import dist
+    _, coef, decim, num_samples = dist.spectrum_filter(sample_rate, freq_step, observe_time)
+    s_all = np.asarray(s_all, dtype=np.uint8)
+    if s_all.ndim != 2 or s_all.shape[0] != 2 * num_samples:
+        raise ValueError("s_all must be (2*num_samples, units)")
+    power = band_power_batch(s_all.T, coef, decim, ctx=ctx)
+    return dist.split_spectrum_record(power, start_freq, end_freq, freq_step, num_dongle, gain, observe_time, sample_rate)
+
+
+def diversity_spectrum_scan(s_all, start_freq, end_freq, freq_step, gain=0, observe_time=0.1, sample_rate=2.048e6, ctx=None):
+    """multi_rtl_sdr_diversity_scanner.m:150-180 after the captures: s_all is the script's (2*num_samples, length(freq),
+    num_dongle) uint8 array.  All num_dongle*length(freq) captures go to the GPU in one call.  Returns the fields the
+    script saves (dist.diversity_spectrum_record): power_spectrum (num_dongle x length(freq)) and its linear mean over
+    dongles, power_spectrum_combine."""
+    from . import dist
+    _, coef, decim, num_samples = dist.spectrum_filter(sample_rate, freq_step, observe_time)
+    s_all = np.asarray(s_all, dtype=np.uint8)
+    if s_all.ndim == 2:
+        s_all = s_all[:, :, None]
+    if s_all.ndim != 3 or s_all.shape[0] != 2 * num_samples:
+        raise ValueError("s_all must be (2*num_samples, length(freq), num_dongle)")
+    num_dongle, nf = s_all.shape[2], s_all.shape[1]
+    raw = s_all.transpose(2, 1, 0).reshape(num_dongle * nf, 2 * num_samples)     # capture (dongle i, point j) = row i*nf + j
+    power = band_power_batch(raw, coef, decim, ctx=ctx).reshape(num_dongle, nf)
+    return dist.diversity_spectrum_record(power, start_freq, end_freq, freq_step, num_dongle, gain, observe_time,
+                                          sample_rate)
+
+
 def fcch_scan_batch(raw, coef, ctx=None):
     """Scanner detect loop for D captures -> dict(snr, num_hit, positions, pos_snr, counts)."""
     ctx = ctx or default_context()

@@ -138,7 +138,8 @@ void gsmcal_ctx_destroy(gsmcal_ctx* c) {
     (void)hipDeviceSynchronize();
     fused_gate_unregister(c);
     DevBuf* bufs[] = {&c->coef, &c->ts, &c->cf, &c->table, &c->snrhit, &c->arr_in, &c->arr_out, &c->posinfo, &c->rlen,
-                      &c->misc, &c->tw, &c->csum_head, &c->tw_sch};
+                      &c->misc, &c->tw, &c->csum_head, &c->tw_sch, &c->bp_coef, &c->bp_state, &c->bp_part, &c->bp_raw,
+                      &c->bp_out};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < MAX_LANES; ++i) {
@@ -710,6 +711,79 @@ int gsmcal_frontend_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, cons
     HIPCHK(c, hipMemcpyAsync(c->misc.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
     RET_IF(gsmcal_frontend_batch_dev(c, (const uint8_t*)c->misc.p, d, n, coef, ntaps, decim, (double*)c->arr_out.p));
     HIPCHK(c, hipMemcpyAsync(out, c->arr_out.p, (size_t)nd * d * sizeof(cplx), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- band power: multi_rtl_sdr_split_scanner.m:154-156, multi_rtl_sdr_diversity_scanner.m:156-158, scan_band_power_spectrum.m:80-84
+// Two passes over the whole batch: k_dc_sum (exact byte sums), then k_band_power.  Cutting the batch into chunks that stay in the
+// 256 MiB Infinity Cache between the passes was measured and is slower (2004 captures, 821 MB: 0.576 ms in 128 MiB chunks against
+// 0.522 ms whole; profiles/band_power_chunking.json): every chunk adds two launch boundaries at which the GPU drains.
+static const auto k_band_power32 = &k_band_power<32>;
+static const auto k_band_power64 = &k_band_power<64>;
+static const auto k_band_power128 = &k_band_power<128>;
+static const auto k_band_power_any = &k_band_power<0>;
+
+int gsmcal_band_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n, const double* coef, int ntaps, int decim,
+                                double* d_power) {
+    if (!c || !d_raw || !coef || !d_power || d < 1 || n < 1 || n > (1L << 40) || ntaps < 1 || ntaps > BP_MAX_TAPS || decim < 1)
+        return GSMCAL_E_ARG;
+    ENTER(c);
+    c->cur = &c->lanes[0];                              // the context's stream; the lane's buffers are not touched
+    const long nd = (n + decim - 1) / decim;
+    bool sym = ntaps == 32 || ntaps == 64 || ntaps == 128;
+    for (int k = 0; sym && k < ntaps / 2; ++k) sym = coef[k] == coef[ntaps - 1 - k];
+    // kept rows per block: enough for a span of ~BP_SPAN samples (small decimations: several rows per lane), at most what the
+    // LDS budget admits
+    int rows = (int)std::min<long>(BP_MAX_ROWS, std::max<long>(BP_ROWS, (BP_SPAN / decim) / BP_ROWS * BP_ROWS));
+    if (bp_lds_bytes(rows, decim, ntaps, !sym) > BP_LDS_BYTES) {
+        const long fit = ((long)(BP_LDS_BYTES - ((ntaps * 8 + 15) & ~15)) / 2 - 8 - 24 - ntaps) / decim + 1;
+        rows = (int)std::max(1L, std::min<long>(rows, fit));
+    }
+    const long nblk = (nd + rows - 1) / rows;
+    if (nblk > (1L << 30)) return GSMCAL_E_ARG;
+    if ((int)c->h_bp_coef.size() != ntaps || memcmp(c->h_bp_coef.data(), coef, (size_t)ntaps * sizeof(double)) != 0) {
+        RET_IF(ensure(c, c->bp_coef, (size_t)ntaps * sizeof(double)));
+        c->h_bp_coef.assign(coef, coef + ntaps);
+        const hipError_t e = hipMemcpyAsync(c->bp_coef.p, c->h_bp_coef.data(), (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { c->h_bp_coef.clear(); c->err = std::string("hipMemcpyAsync (band-power taps): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
+    }
+    RET_IF(ensure(c, c->bp_state, (size_t)d * sizeof(StreamState)));
+    RET_IF(ensure(c, c->bp_part, (size_t)d * nblk * sizeof(double)));
+    StreamState* st = (StreamState*)c->bp_state.p;
+    double* part = (double*)c->bp_part.p;
+    const double* dcoef = (const double*)c->bp_coef.p;
+    const size_t lds = bp_lds_bytes(rows, decim, ntaps, !sym);
+    LAUNCH(c, k_band_power_clear, dim3((d + 255) / 256), dim3(256), 0, st, d);
+    const long chunk = 65535;                           // (the grid's y limit)
+    for (long lo = 0; lo < d; lo += chunk) {
+        const int S = (int)std::min(chunk, (long)d - lo);
+        const uint8_t* raw = d_raw + (size_t)lo * 2 * n;
+        int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));           // dc_means()'s geometry
+        blocks = std::max(1, std::min(blocks, std::max(1, 4096 / S)));
+        LAUNCH(c, k_dc_sum, dim3(blocks, S), dim3(256), 0, raw, 2 * n, st + lo);
+        const dim3 grid((unsigned)nblk, S);
+        const StreamState* st_lo = st + lo;
+        double* part_lo = part + lo * nblk;
+        if (!sym) LAUNCH(c, k_band_power_any, grid, dim3(256), lds, raw, 2 * n, st_lo, dcoef, ntaps, decim, nd, rows, part_lo);
+        else if (ntaps == 32) LAUNCH(c, k_band_power32, grid, dim3(256), lds, raw, 2 * n, st_lo, dcoef, ntaps, decim, nd, rows, part_lo);
+        else if (ntaps == 64) LAUNCH(c, k_band_power64, grid, dim3(256), lds, raw, 2 * n, st_lo, dcoef, ntaps, decim, nd, rows, part_lo);
+        else LAUNCH(c, k_band_power128, grid, dim3(256), lds, raw, 2 * n, st_lo, dcoef, ntaps, decim, nd, rows, part_lo);
+    }
+    LAUNCH(c, k_band_power_finish, dim3((d + 63) / 64), dim3(64), 0, (const double*)part, (int)nblk, d, n, nd, d_power);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_band_power_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, const double* coef, int ntaps, int decim,
+                            double* power) {
+    if (!c || !raw || !coef || !power || d < 1 || n < 1 || ntaps < 1 || ntaps > BP_MAX_TAPS || decim < 1) return GSMCAL_E_ARG;
+    ENTER(c);
+    RET_IF(ensure(c, c->bp_raw, (size_t)2 * n * d));
+    RET_IF(ensure(c, c->bp_out, (size_t)d * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(c->bp_raw.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
+    RET_IF(gsmcal_band_power_batch_dev(c, (const uint8_t*)c->bp_raw.p, d, n, coef, ntaps, decim, (double*)c->bp_out.p));
+    HIPCHK(c, hipMemcpyAsync(power, c->bp_out.p, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

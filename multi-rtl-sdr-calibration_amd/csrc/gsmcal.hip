@@ -28,6 +28,7 @@
 #include "kernels_estim.h"
 #include "kernels_frontend.h"
 #include "kernels_demod.h"
+#include "kernels_spectrum.h"
 #include "state.h"
 
 #define GSMCAL_VERSION "gsmcal-mi355x 0.1 (gfx950)"

@@ -141,6 +141,10 @@ struct gsmcal_ctx {
     unsigned long coef_epoch = 0, head_epoch = ~0ul;   // coef_epoch: bumped whenever h_coef changes
     int tw_n = 0;                            // length the twiddle table was built for
     std::vector<double> h_coef, h_ts, h_cf;   // host copies: upload only when changed
+    // band power (gsmcal_band_power_batch*): workspaces of its own, so that a band-power call leaves the lanes, the shared
+    // taps and every answer about the calibration / scan call before it untouched
+    DevBuf bp_coef, bp_state, bp_part, bp_raw, bp_out;
+    std::vector<double> h_bp_coef;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream
     static constexpr int AG_SLOTS = 4;

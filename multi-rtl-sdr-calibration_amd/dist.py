@@ -476,3 +476,58 @@ def _num2str(v):
     if float(v) == int(v):
         return str(int(v))
     return ("%11.5g" % v).strip()
+
+
+# ------------------------------------------------------------------------------------------------
+# band power-spectrum scanners (multi_rtl_sdr_split_scanner.m, multi_rtl_sdr_diversity_scanner.m)
+# ------------------------------------------------------------------------------------------------
+def spectrum_filter(sample_rate, rbw, observe_time):
+    """The scanners' filter design (multi_rtl_sdr_split_scanner.m:51-57,71; ..diversity_scanner.m:51-57,66) ->
+    (coef_order, coef, decimate_ratio, num_samples).
+
+    coef_order = 2^ceil(log2(sample_rate/RBW)) - 1 clamped to 31..127, coef = fir1(coef_order, RBW/sample_rate),
+    decimate_ratio = floor(sample_rate/(2*RBW)), num_samples = observe_time*sample_rate (must be a whole number: the
+    scripts size s_all with it)."""
+    from .synth import fir1
+    if not (sample_rate > 0 and rbw > 0 and observe_time > 0):
+        raise ValueError("sample_rate, rbw and observe_time must be positive")
+    coef_order = 2 ** int(np.ceil(np.log2(sample_rate / rbw))) - 1
+    coef_order = max(min(coef_order, 127), 31)
+    coef = fir1(coef_order, rbw / sample_rate)
+    decimate_ratio = int(np.floor(sample_rate / (2 * rbw)))
+    if decimate_ratio < 1:
+        raise ValueError("RBW above half the sample rate: floor(sample_rate/(2*RBW)) is 0")
+    num_samples = observe_time * sample_rate
+    if num_samples != int(num_samples):
+        raise ValueError("observe_time*sample_rate = %r is not a whole number of samples" % num_samples)
+    return coef_order, coef, decimate_ratio, int(num_samples)
+
+
+def split_spectrum_record(power_spectrum, start_freq, end_freq, freq_step, num_dongle, gain, observe_time, sample_rate):
+    """The fields multi_rtl_sdr_split_scanner.m:176-177 saves, from the gathered power column (one linear power per unit,
+    units in scan_frequency_plan's order, padded points included: 1 x num_dongle*num_freq_per_sub_band)."""
+    freq, _ = scan_frequency_plan(start_freq, end_freq, freq_step, num_dongle)
+    ps = np.asarray(power_spectrum, dtype=np.float64).ravel()
+    if ps.size != freq.size:
+        raise ValueError("power spectrum does not match the frequency plan")
+    _, coef, _, _ = spectrum_filter(sample_rate, freq_step, observe_time)
+    return {"power_spectrum": ps, "start_freq": start_freq, "end_freq": end_freq, "freq_step": freq_step,
+            "observe_time": observe_time, "RBW": freq_step, "gain": gain, "sample_rate": sample_rate, "coef": coef,
+            "freq": freq,
+            "filename": "split_scan_%s_%s_gain%s_%sdongles.mat" % (_num2str(start_freq), _num2str(end_freq),
+                                                                   _num2str(gain), _num2str(num_dongle))}
+
+
+def diversity_spectrum_record(power_spectrum, start_freq, end_freq, freq_step, num_dongle, gain, observe_time, sample_rate):
+    """The fields multi_rtl_sdr_diversity_scanner.m:180 saves: power_spectrum (num_dongle x length(start:step:end), every
+    dongle sweeps the whole grid) and power_spectrum_combine = mean(power_spectrum, 1) (:176, a linear mean over dongles)."""
+    n = int(np.floor((end_freq - start_freq) / freq_step + 1e-9)) + 1           # length(start:step:end)
+    ps = np.asarray(power_spectrum, dtype=np.float64).reshape(num_dongle, -1)
+    if ps.shape[1] != n:
+        raise ValueError("power spectrum does not match the frequency grid")
+    _, coef, _, _ = spectrum_filter(sample_rate, freq_step, observe_time)
+    return {"power_spectrum": ps, "power_spectrum_combine": np.mean(ps, axis=0), "start_freq": start_freq,
+            "end_freq": end_freq, "freq_step": freq_step, "observe_time": observe_time, "RBW": freq_step, "gain": gain,
+            "sample_rate": sample_rate, "coef": coef,
+            "filename": "scan_%s_%s_gain%s_%sdongles.mat" % (_num2str(start_freq), _num2str(end_freq), _num2str(gain),
+                                                             _num2str(num_dongle))}
