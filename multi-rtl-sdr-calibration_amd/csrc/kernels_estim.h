@@ -149,7 +149,7 @@ __device__ __forceinline__ int burst_gather_fast(const StreamState* __restrict__
     cplx* buf1 = (cplx*)(smem + gc.off_region1);
     auto lerp1 = [&](int i) {                                    // level-1 sample lo1+i
         const long k = lo1 + i;
-        const double xq = (double)k * f1;                        // interp_seq = (0:max_len-1)'.*(1+e)
+        const double xq = lerp_pos((double)k, f1);               // interp_seq = (0:max_len-1)'.*(1+e)
         const long i0 = (long)floor(xq);
         const long i1 = i0 + 1 > hi0 ? hi0 : i0 + 1;             // beyond the last sample the weight is 0
         const double t = xq - (double)i0;
@@ -187,7 +187,7 @@ __device__ __forceinline__ int burst_gather_fast(const StreamState* __restrict__
 #pragma unroll 1
         for (int i = tid; i < L; i += NT) {
             const long k = lo3 + i;
-            const double xq = (double)k * f3;
+            const double xq = lerp_pos((double)k, f3);
             const long i0 = (long)floor(xq);
             const long i1 = i0 + 1 > hi1 ? hi1 : i0 + 1;
             const double t = xq - (double)i0;

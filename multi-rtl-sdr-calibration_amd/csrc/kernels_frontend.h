@@ -644,6 +644,16 @@ __device__ __forceinline__ long level_len(const StreamState* st, int level) {
 // samples 4 apart (the 4-outputs-per-lane FIR below) hit distinct banks with ds_read_b128.
 __device__ __forceinline__ int xs_pad(int p) { return p + (p >> 2); }
 
+// Query position k*(1+e) of interp1 (interp_seq, FCCH_fine_correction.m:123, SCH_corr_rate_correction.m:126), ROUNDED to
+// double as the reference rounds it before interp1 sees it.  Contraction must stay off here: left to the compiler, the
+// weight xq - floor(xq) behind it becomes fma(k, f, -floor(xq)) -- the weight of the UNROUNDED product, up to an ulp of xq
+// (1.2e-10 at k = 6e5) away from the reference's.  On unfiltered samples that moved the tone estimate by 2e-11 ppm and the
+// end of the corrected stream by 4e-8 rad (tests/test_gpu_general_taps.py, the one-tap filter).
+__device__ __forceinline__ double lerp_pos(double k, double f) {
+#pragma clang fp contract(off)
+    return k * f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // filter(coef,1,.) for FOUR consecutive outputs i0 .. i0+3 from the padded LDS copy xq (xs_pad indexing; i0 a multiple of
 // 4): y[i] = sum_k coef[k] x[i-k], every accumulator taking its taps oldest first (transposed direct-form order) -- the
@@ -903,7 +913,7 @@ __device__ __forceinline__ cplx* gather_core(const StreamState* __restrict__ sts
         if (type == OP_LERP) {
             for (int i = threadIdx.x; i < cnt; i += NT) {
                 const long k = lo_j + i;
-                const double xq = (double)k * p;            // interp_seq = (0:max_len-1)'.*(1+e)
+                const double xq = lerp_pos((double)k, p);   // interp_seq = (0:max_len-1)'.*(1+e)
                 const long i0 = (long)floor(xq);
                 const long i1 = i0 + 1 > phi_ ? phi_ : i0 + 1;  // beyond the last sample the weight is 0
                 const double t = xq - (double)i0;
@@ -1156,7 +1166,7 @@ __global__ void __launch_bounds__(ST_THREADS) k_stream_tile(const StreamState* _
             const double dlo2 = (double)lo2, dlo0 = (double)lo0;    // (indices < 2^53: the double sums and differences below are exact)
             const int last0 = cnt0 - 1;
             for (int i = tid; i < cnt2; i += ST_THREADS) {
-                const double xq = (dlo2 + (double)i) * f1;      // interp_seq = (0:max_len-1)'.*(1+e)
+                const double xq = lerp_pos(dlo2 + (double)i, f1);   // interp_seq = (0:max_len-1)'.*(1+e)
                 const double j0f = floor(xq);
                 const int j0 = (int)(j0f - dlo0);
                 const int j1 = j0 + 1 > last0 ? last0 : j0 + 1; // beyond the last sample the weight is 0
@@ -1174,7 +1184,7 @@ __global__ void __launch_bounds__(ST_THREADS) k_stream_tile(const StreamState* _
             const double dlo3 = (double)lo3, dlo2 = (double)lo2;
             const int last2 = cnt2 - 1;
             for (int i = tid; i < L4; i += ST_THREADS) {
-                const double xq = (dlo3 + (double)i) * f3;
+                const double xq = lerp_pos(dlo3 + (double)i, f3);
                 const double j0f = floor(xq);
                 const int j0 = (int)(j0f - dlo2);
                 const int j1 = j0 + 1 > last2 ? last2 : j0 + 1;
@@ -1407,7 +1417,7 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
             for (int k = 0; k < 4; ++k) {                       // (cnt2 <= 4 * ST_THREADS: static register indices for ab2)
                 const int i = tid + k * ST_THREADS;
                 if (i < cnt2) {
-                    const double xq = (p2 + (double)(k * ST_THREADS)) * f1;
+                    const double xq = lerp_pos(p2 + (double)(k * ST_THREADS), f1);
                     const double j0f = floor(xq);
                     const int j0 = (int)(j0f - dlo0);
                     const int j1 = j0 + 1 > last0 ? last0 : j0 + 1;
@@ -1428,7 +1438,7 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
             for (int k = 0; k < 4; ++k) {
                 const int i = tid + k * ST_THREADS;
                 if (i < L4) {
-                    const double xq = (p3 + (double)(k * ST_THREADS)) * f3;
+                    const double xq = lerp_pos(p3 + (double)(k * ST_THREADS), f3);
                     const double j0f = floor(xq);
                     const int j0 = (int)(j0f - dlo2);
                     const int j1 = j0 + 1 > last2 ? last2 : j0 + 1;
