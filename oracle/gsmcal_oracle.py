@@ -43,6 +43,27 @@ class MatlabIndexError(IndexError):
     """Raised where MATLAB would stop with 'index out of bounds' (SURVEY 8a pitfall 12)."""
 
 
+# The early exits of the chain, numbered as include/gsmcal.h numbers them (GSMCAL_S_*): the reference returns normally
+# from each with sentinel outputs; a stage function called with info={} leaves the code of the exit it took -- 0 for none --
+# in info["exit"].  (GSMCAL_S_ALL_INF = 12 belongs to total_ppm_calculation alone and is not recorded.)
+S_NO_FCCH = 1           # FCCH_coarse_position.m:27-30
+S_FEW_HITS = 2          # FCCH_fine_correction.m:12-15 / SCH_corr_rate_correction.m:11
+S_FINE_FEW = 3          # FCCH_fine_correction.m:69 not taken: fewer than 5 fine positions
+S_FINE_SPACING = 4      # FCCH_fine_correction.m:95-102
+S_FINE_FEW_BURSTS = 5   # FCCH_fine_correction.m:135-142: the dropped last burst leaves fewer than 5
+S_FINE_LOW_SNR = 6      # FCCH_fine_correction.m:192-196
+S_SCH_EDGE = 7          # SCH_corr_rate_correction.m:59-63
+S_SCH_FEW = 8           # SCH_corr_rate_correction.m:84 not taken
+S_SCH_SPACING = 9       # SCH_corr_rate_correction.m:106-112
+S_POST_NO_POS = 10      # carrier_correct_post_SCH.m:10-13
+S_POST_FEW_BCCH = 11    # carrier_correct_post_SCH.m:15-19
+
+
+def _exit(info, code):
+    if info is not None:
+        info["exit"] = code
+
+
 def matlab_round(x):
     """MATLAB round(): half away from zero (FCCH_coarse_position.m:35-36 rounds 1562.5 -> 1563)."""
     x = np.asarray(x, dtype=np.float64)
@@ -208,7 +229,7 @@ def specific_fft_snr_fix_avg(s, target_set, fft_len, th, avg_snr):
 # ------------------------------------------------------------------------------------------------
 # a5  FCCH_coarse_position.m:5-94
 # ------------------------------------------------------------------------------------------------
-def FCCH_coarse_position(s, decimation_ratio):
+def FCCH_coarse_position(s, decimation_ratio, info=None):
     """[position, snr] = FCCH_coarse_position(s, decimation_ratio)
 
     Returns (position, snr) as float64 row vectors (1x-symbol units, 1-based), or (-1.0, -1.0)
@@ -227,7 +248,9 @@ def FCCH_coarse_position(s, decimation_ratio):
     if n_first > length:
         raise MatlabIndexError("s(1:ceil(23 frames)) exceeds the signal")
     hit_flag, hit_idx, hit_avg_snr, hit_snr = move_fft_snr_runtime_avg(s[:n_first], mv_len, fft_len, th)
+    _exit(info, 0)
     if not hit_flag:
+        _exit(info, S_NO_FCCH)
         return -1.0, -1.0
 
     num_sym_between_FCCH = 10 * num_slot_per_frame * num_sym_per_slot
@@ -307,7 +330,9 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
     sampling_ppm = math.inf
     carrier_ppm = math.inf
     base_position = np.atleast_1d(np.asarray(base_position, dtype=np.float64))
+    _exit(info, 0)
     if len(base_position) < 5:  # :12
+        _exit(info, S_FEW_HITS)
         return FCCH_pos, r, sampling_ppm, carrier_ppm
 
     symbol_rate = SYMBOL_RATE
@@ -358,6 +383,7 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
         b = diff_seq - d1_ov
         b_logical = np.abs(b) < max_th1
         if (np.sum(a_logical) + np.sum(b_logical)) != last_idx - 1:  # :95
+            _exit(info, S_FINE_SPACING)
             return -1.0, r, sampling_ppm, carrier_ppm
         expected_distance = np.sum(a_logical * d_ov) + np.sum(b_logical * d1_ov)
         actual_distance = FCCH_pos[-1] - FCCH_pos[0]
@@ -402,7 +428,10 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
         if info is not None:
             info["fcch_snr"] = FCCH_snr.copy()
         if np.sum(FCCH_snr < 5) > 0:  # :192
+            _exit(info, S_FINE_LOW_SNR)
             return -1.0, r, sampling_ppm, carrier_ppm
+    else:
+        _exit(info, S_FINE_FEW if last_idx < 5 else S_FINE_FEW_BURSTS)
     return FCCH_pos, r, sampling_ppm, carrier_ppm
 
 
@@ -418,7 +447,9 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
     pos_info = np.array([[-1.0, -1.0]])
     sampling_ppm = math.inf
     FCCH_pos = np.atleast_1d(np.asarray(FCCH_pos, dtype=np.float64))
+    _exit(info, 0)
     if len(FCCH_pos) < 5:  # :11
+        _exit(info, S_FEW_HITS)
         return pos_info, r, sampling_ppm
     s = np.asarray(s).ravel()
     sch = np.asarray(sch_training_sequence).ravel()
@@ -456,6 +487,7 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
             if info is not None:   # the reference returns here; keep what was computed so far for the tests
                 info["first_round_sch_pos"] = SCH_pos[:i + 1].copy()
                 info["sch_edge_abort"] = True
+            _exit(info, S_SCH_EDGE)
             return np.array([[-1.0, -1.0]]), r, sampling_ppm
     if info is not None:
         info["first_round_sch_pos"] = SCH_pos.copy()
@@ -475,6 +507,7 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
         b = diff_seq - d1_ov
         b_logical = np.abs(b) < max_th1
         if (np.sum(a_logical) + np.sum(b_logical)) != num_sch - 1:  # :106
+            _exit(info, S_SCH_SPACING)
             return pos_info, r, sampling_ppm
         expected_distance = np.sum(a_logical * d_ov) + np.sum(b_logical * d1_ov)
         actual_distance = SCH_pos[-1] - SCH_pos[0]
@@ -525,6 +558,8 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
                 if runout:
                     break
         pos_info = np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+    else:
+        _exit(info, S_SCH_FEW)
     return pos_info, r, sampling_ppm
 
 
@@ -536,9 +571,12 @@ def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info
     r = -1.0
     carrier_ppm = math.inf
     pos_info = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
+    _exit(info, 0)
     if np.all(pos_info == -1):  # :10
+        _exit(info, S_POST_NO_POS)
         return r, carrier_ppm
     if np.sum(pos_info[:, 1] == 2) < 4:  # :15-19
+        _exit(info, S_POST_FEW_BCCH)
         return r, carrier_ppm
     s = np.asarray(s).ravel()
     symbol_rate = SYMBOL_RATE
@@ -616,7 +654,8 @@ def calibrate_stream(raw, coef, sch_training_sequence, carrier_freq,
     r = raw2iq(raw)                              # :107
     r = matlab_filter(coef, r)                   # :110
     dec = oversampling_ratio * coarse_decimation
-    pos_c, snr_c = FCCH_coarse_position(r[0::dec], coarse_decimation)            # :117
+    info0 = {}
+    pos_c, snr_c = FCCH_coarse_position(r[0::dec], coarse_decimation, info0)     # :117
     out["coarse_pos"], out["coarse_snr"] = np.atleast_1d(pos_c), np.atleast_1d(snr_c)
     info = {}
     FCCH_pos, r_c, sp1, cp1 = FCCH_fine_correction(r, pos_c, oversampling_ratio, carrier_freq, info)  # :118
@@ -627,12 +666,21 @@ def calibrate_stream(raw, coef, sch_training_sequence, carrier_freq,
     out["sch_first_round_pos"] = info2.get("first_round_sch_pos", np.zeros(0))
     out["sch_edge_abort"] = bool(info2.get("sch_edge_abort", False))
     out["pos_info"] = pos_info
-    r_c, cp2 = carrier_correct_post_SCH(r_c, pos_info, oversampling_ratio, carrier_freq)  # :120
+    info3 = {}
+    r_c, cp2 = carrier_correct_post_SCH(r_c, pos_info, oversampling_ratio, carrier_freq, info3)  # :120
     out["sampling_ppm"] = np.array([sp1, sp2])
     out["carrier_ppm"] = np.array([cp1, cp2])
     out["total_sampling_ppm"] = total_ppm_calculation([sp1, sp2])  # :123
     out["total_carrier_ppm"] = total_ppm_calculation([cp1, cp2])   # :124
     out["r_len"] = len(r_c) if isinstance(r_c, np.ndarray) else -1
+    # columns 6..9 of the calibration table (include/gsmcal.h GSMCAL_T_*): the exit codes stage by stage, the first
+    # non-zero one along coarse -> fine -> SCH -> post, and the counts with the reference's sentinel shapes ([-1] counts as
+    # one FCCH position; [-1 -1] as one row, the -ones(3*num_fcch_hit, 2) of the :84 / :106 exits as that many)
+    out["stage_exit"] = np.array([info0["exit"], info["exit"], info2["exit"], info3["exit"]])
+    out["status"] = int(next((c for c in out["stage_exit"] if c != 0), 0))
+    out["n_fcch"] = len(out["fcch_pos"])
+    out["n_pos_rows"] = int(pos_info.shape[0])
+    out["first_fcch_pos"] = float(pos_info[0, 0])
     if keep_r:
         out["r_correct"] = r_c
     return out

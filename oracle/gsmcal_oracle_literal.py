@@ -23,6 +23,12 @@ from scipy.linalg import toeplitz
 SYMBOL_RATE = (1625.0 / 6.0) * 1e3
 
 
+def note_exit(info, code):
+    """info["exit"] = the include/gsmcal.h number (GSMCAL_S_*) of the early exit a stage function took, 0 for none"""
+    if info is not None:
+        info["exit"] = code
+
+
 def m_round(x):
     """MATLAB round: ties away from zero."""
     return math.floor(x + 0.5) if x >= 0 else -math.floor(-x + 0.5)
@@ -156,7 +162,8 @@ def specific_fft_snr_fix_avg(s, target_set, fft_len, th, avg_snr):
 
 
 # ---- FCCH_coarse_position.m -----------------------------------------------------------------------------------------
-def FCCH_coarse_position(s, decimation_ratio):
+def FCCH_coarse_position(s, decimation_ratio, info=None):
+    note_exit(info, 0)
     position = -1.0
     snr = -1.0
     num_sym_per_slot = 625 / 4
@@ -172,6 +179,7 @@ def FCCH_coarse_position(s, decimation_ratio):
         raise IndexError("index exceeds matrix dimensions")
     hit_flag, hit_idx, hit_avg_snr, hit_snr = move_fft_snr_runtime_avg(s[:n_first], mv_len, fft_len, th)   # :25
     if not hit_flag:                                                                # :27
+        note_exit(info, 1)                                                          # GSMCAL_S_NO_FCCH
         return position, snr
     num_sym_between_FCCH = 10 * num_slot_per_frame * num_sym_per_slot
     num_sym_between_FCCH1 = 11 * num_slot_per_frame * num_sym_per_slot
@@ -268,7 +276,8 @@ def _tone_estimate(r, pos_list, fft_len, sampling_rate):
 
 
 # ---- FCCH_fine_correction.m -----------------------------------------------------------------------------------------
-def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq):
+def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, info=None):
+    note_exit(info, 0)
     s = np.asarray(s, dtype=np.complex128).ravel()
     r = -1.0
     FCCH_pos = -1.0
@@ -276,6 +285,7 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq):
     carrier_ppm = math.inf
     base_position = np.atleast_1d(np.asarray(base_position, dtype=np.float64))
     if len(base_position) < 5:                                                      # :12
+        note_exit(info, 2)                                                          # GSMCAL_S_FEW_HITS
         return FCCH_pos, r, sampling_ppm, carrier_ppm, []
     symbol_rate = SYMBOL_RATE
     sampling_rate = symbol_rate * oversampling_ratio
@@ -327,6 +337,7 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq):
         a_logical = [abs(d - d_ov) < max_th for d in diff_seq]
         b_logical = [abs(d - d1_ov) < max_th1 for d in diff_seq]
         if sum(a_logical) + sum(b_logical) != last_idx - 1:                         # :95
+            note_exit(info, 4)                                                      # GSMCAL_S_FINE_SPACING
             return -1.0, r, sampling_ppm, carrier_ppm, first_round
         expected = sum(d_ov for f in a_logical if f) + sum(d1_ov for f in b_logical if f)
         actual = FCCH_pos[-1] - FCCH_pos[0]
@@ -348,6 +359,10 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq):
         FCCH_pos = [g + first_FCCH_pos - 1 for g in grid]
         if FCCH_pos[-1] + fft_len - 1 > len(r):                                     # :135
             FCCH_pos = FCCH_pos[:-1]
+            if len(FCCH_pos) < 5:
+                note_exit(info, 5)                                                  # GSMCAL_S_FINE_FEW_BURSTS (:142 not taken)
+    else:
+        note_exit(info, 3)                                                          # GSMCAL_S_FINE_FEW (:69 not taken)
     if len(FCCH_pos) >= 5:
         fcch_mat, _ipr, pr, fo = _tone_estimate(r, FCCH_pos, fft_len, sampling_rate)
         target_freq = symbol_rate / 4
@@ -368,17 +383,20 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq):
             npow = sum(fd[k - 1] for k in noise_idx)
             snr.append(10 * math.log10(sp_ / npow))
         if sum(1 for v in snr if v < 5) > 0:                                        # :192
+            note_exit(info, 6)                                                      # GSMCAL_S_FINE_LOW_SNR
             return -1.0, r, sampling_ppm, carrier_ppm, first_round
     return np.array(FCCH_pos, dtype=np.float64), r, sampling_ppm, carrier_ppm, first_round
 
 
 # ---- SCH_corr_rate_correction.m -------------------------------------------------------------------------------------
-def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ratio):
+def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ratio, info=None):
+    note_exit(info, 0)
     r = -1.0
     pos_info = np.array([[-1.0, -1.0]])
     sampling_ppm = math.inf
     FCCH_pos = np.atleast_1d(np.asarray(FCCH_pos, dtype=np.float64))
     if len(FCCH_pos) < 5:                                                           # :11
+        note_exit(info, 2)                                                          # GSMCAL_S_FEW_HITS
         return pos_info, r, sampling_ppm
     s = np.asarray(s, dtype=np.complex128).ravel()
     ts = np.asarray(sch_training_sequence, dtype=np.complex128).ravel()
@@ -414,8 +432,11 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
                 max_idx = j
         SCH_pos[i - 1] = sp + max_idx - 1
         if max_idx == 1 or max_idx == length:                                       # :59
+            note_exit(info, 7)                                                      # GSMCAL_S_SCH_EDGE
             return np.array([[-1.0, -1.0]]), r, sampling_ppm
     num_sch = len(SCH_pos)
+    if num_sch < 5:
+        note_exit(info, 8)                                                          # GSMCAL_S_SCH_FEW (:84 not taken)
     if num_sch >= 5:
         r = s
         first_SCH_pos = SCH_pos[0]
@@ -428,6 +449,7 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
         a_logical = [abs(d - d_ov) < max_th for d in diff_seq]
         b_logical = [abs(d - d1_ov) < max_th1 for d in diff_seq]
         if sum(a_logical) + sum(b_logical) != num_sch - 1:                          # :106
+            note_exit(info, 9)                                                      # GSMCAL_S_SCH_SPACING
             return pos_info, r, sampling_ppm
         expected = sum(d_ov for f in a_logical if f) + sum(d1_ov for f in b_logical if f)
         actual = SCH_pos[-1] - SCH_pos[0]
@@ -492,13 +514,16 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
 
 
 # ---- carrier_correct_post_SCH.m -------------------------------------------------------------------------------------
-def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq):
+def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info=None):
+    note_exit(info, 0)
     r = -1.0
     carrier_ppm = math.inf
     pos_info = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
     if all(v == -1 for v in pos_info.ravel()):                                      # :10
+        note_exit(info, 10)                                                         # GSMCAL_S_POST_NO_POS
         return r, carrier_ppm
     if sum(1 for v in pos_info[:, 1] if v == 2) < 4:                                # :15
+        note_exit(info, 11)                                                         # GSMCAL_S_POST_FEW_BCCH
         return r, carrier_ppm
     s = np.asarray(s, dtype=np.complex128).ravel()
     symbol_rate = SYMBOL_RATE
@@ -526,3 +551,28 @@ def total_ppm_calculation(ppm_in):
     for v in ppm_in:
         tmp = tmp * (1 + v * 1e-6)
     return (tmp - 1) * 1e6
+
+
+# ---- gsm_sync_demod.m:107-124, one dongle ---------------------------------------------------------------------------
+def calibrate_stream(raw, coef, sch_training_sequence, carrier_freq, oversampling_ratio=8, coarse_decimation=8):
+    """The per-dongle body of the driver, and what the calibration table's columns 6..9 say about it (include/gsmcal.h
+    GSMCAL_T_*): status = the first exit met along coarse -> fine -> SCH -> post, n_fcch = length(FCCH_pos) (1 for the -1
+    sentinel), n_pos_rows = size(pos_info, 1), first_fcch_pos = pos_info(1, 1)."""
+    i0, i1, i2, i3 = {}, {}, {}, {}
+    r = filter_fir(coef, raw2iq(np.asarray(raw, dtype=np.float64))[:, 0])           # :107, :110
+    pos, snr = FCCH_coarse_position(r[0::oversampling_ratio * coarse_decimation], coarse_decimation, i0)   # :117
+    fp, r1, sp1, cp1, first = FCCH_fine_correction(r, pos, oversampling_ratio, carrier_freq, i1)            # :118
+    pi, r2, sp2 = SCH_corr_rate_correction(r1, fp, sch_training_sequence, oversampling_ratio, i2)           # :119
+    r3, cp2 = carrier_correct_post_SCH(r2, pi, oversampling_ratio, carrier_freq, i3)                        # :120
+    stage_exit = [i0["exit"], i1["exit"], i2["exit"], i3["exit"]]
+    status = 0
+    for code in stage_exit:
+        if code != 0:
+            status = code
+            break
+    fcch_pos = np.atleast_1d(np.asarray(fp, dtype=np.float64))
+    return {"coarse_pos": np.atleast_1d(pos), "coarse_snr": np.atleast_1d(snr), "first": np.asarray(first, dtype=np.float64),
+            "fcch_pos": fcch_pos, "pos_info": pi, "sp": [sp1, sp2], "cp": [cp1, cp2],
+            "tot": [total_ppm_calculation([sp1, sp2]), total_ppm_calculation([cp1, cp2])], "r": r3,
+            "stage_exit": stage_exit, "status": status, "n_fcch": len(fcch_pos), "n_pos_rows": int(pi.shape[0]),
+            "first_fcch_pos": float(pi[0, 0])}

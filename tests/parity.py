@@ -58,6 +58,12 @@ def compare_stream(orc, row, det, i, pos_info):
     assert_ppm(row[3], orc["carrier_ppm"][1], "carrier_ppm(2)")
     assert_ppm(row[4], orc["total_sampling_ppm"], "total sampling ppm")
     assert_ppm(row[5], orc["total_carrier_ppm"], "total carrier ppm")
+    if "status" in orc:
+        # columns 6..9 (include/gsmcal.h GSMCAL_T_N_FCCH, _N_POS_ROWS, _FIRST_FCCH_POS, _STATUS): the counts with the reference's
+        # sentinel shapes and the first exit met along the chain, exactly (dicts built from tests/golden/calib_golden.json
+        # carry no such key)
+        want = [float(orc["n_fcch"]), float(orc["n_pos_rows"]), float(orc["first_fcch_pos"]), float(orc["status"])]
+        assert [float(v) for v in row[6:10]] == want, f"table columns 6..9 (n_fcch, n_pos_rows, first_fcch_pos, status): gpu {list(row[6:10])} vs oracle {want}"
 
 
 # ---- helpers for tests that need many streams: worker functions for a SPAWNED process pool (a pytest process that has
