@@ -60,6 +60,7 @@ enum {
 #define GSMCAL_MAX_HITS 24          /* capacity for FCCH/SCH hits per stream (ceil(len/1562.5)) */
 #define GSMCAL_MAX_POS_ROWS (6 * GSMCAL_MAX_HITS)
 #define GSMCAL_TABLE_COLS 10
+#define GSMCAL_DEMOD_COLS (4 + 3 * GSMCAL_MAX_HITS)   /* one row of gsmcal_fcch_demod_batch[_dev]: 76 doubles */
 
 /* columns of one row of the calibration table (doubles; this row is what ranks all-gather) */
 enum {
@@ -73,6 +74,17 @@ enum {
     GSMCAL_T_N_POS_ROWS = 7,        /* rows of pos_info (1 if sentinel)                              */
     GSMCAL_T_FIRST_FCCH_POS = 8,    /* pos_info(1,1) or -1                                           */
     GSMCAL_T_STATUS = 9             /* first non-zero status code met along the chain               */
+};
+
+/* columns of one row of the FCCH_demod table (doubles) */
+enum {
+    GSMCAL_D_NUM_FCCH = 0,                          /* type-0 rows of pos_info                    FCCH_demod.m:20 */
+    GSMCAL_D_MEAN_FREQ = 1,                         /* mean(freq), NaN without a burst            :44             */
+    GSMCAL_D_CARRIER_PPM = 2,                       /* 1e6*(mean_freq - symbol_rate/4)/carrier    :47-48          */
+    GSMCAL_D_STATUS = 3,                            /* 0, GSMCAL_S_POST_NO_POS, GSMCAL_E_CAPACITY or GSMCAL_E_INDEX */
+    GSMCAL_D_FREQ = 4,                              /* [GSMCAL_MAX_HITS] tone frequency per burst :42             */
+    GSMCAL_D_SNR = 4 + GSMCAL_MAX_HITS,             /* [GSMCAL_MAX_HITS] in-band SNR, dB          :62             */
+    GSMCAL_D_MAX_IDX = 4 + 2 * GSMCAL_MAX_HITS      /* [GSMCAL_MAX_HITS] max_idx - (fft_len/2+1)  :66             */
 };
 
 /* ---- algorithm thresholds (the constants the reference hard-codes inside its functions) ---------- */
@@ -113,7 +125,7 @@ const char* gsmcal_last_error(gsmcal_ctx* ctx);
  * SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79) -- and a MEX file that shadows one
  * would otherwise run silent.  After gsmcal_FCCH_coarse_position / _FCCH_fine_correction / _SCH_corr_rate_correction /
  * _carrier_correct_post_SCH this returns the lines that call's .m file would have printed, '\n'-separated, numbers formatted as
- * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  buf may be NULL; the return value is the
+ * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  gsmcal_FCCH_demod leaves its lines too.  buf may be NULL; the return value is the
  * text's length without the terminator.  The gateway mexPrintf()s it; the Python mirror prints it when GSMCAL_VERBOSE=1. */
 long gsmcal_last_call_report(gsmcal_ctx* ctx, char* buf, size_t cap);
 long gsmcal_num2str(const double* x, int n, char* buf, size_t cap);
@@ -247,6 +259,21 @@ int gsmcal_SCH_equalise(gsmcal_ctx* ctx, const double* s, long len, const double
                         const double* sch_training_sequence, int len_ts, int oversampling_ratio,
                         double* x_eq, int cap_bursts, int* num_bursts, int* len_fde_ov);
 
+/* FCCH_demod(s,pos_info,ov,carrier_freq)                            FCCH_demod.m:5-66
+ * The check behind the calibration (gsm_sync_demod.m:144): per FCCH row of pos_info (type 0, start sp) the window
+ * s(sp : sp+148*ov-1), the first maximum of its power spectrum in fftshift order, the tone frequency from the integer-bin
+ * rotation and the mean phase step of the unit phasors (:28-42), and the SNR of :51-63 -- the five bins at the peak against the
+ * rest of the 110 bins around the centre.  freq, snr, max_idx: capacity `cap` doubles, *num_fcch written; max_idx holds the
+ * offset max_idx - (fft_len/2+1) the reference prints (:66).  *mean_freq = mean(freq), *carrier_ppm the carrier error still left
+ * (:44-48); both NaN when pos_info has no type-0 row (MATLAB's mean([])).
+ * snr: where noise_power < 0 (peak outside the band) MATLAB's log10 yields a complex number: NaN here; noise_power == 0: +Inf.
+ * pos_info all -1 (:8-11): returns GSMCAL_S_POST_NO_POS with *num_fcch = 0.  More than GSMCAL_MAX_HITS type-0 rows (or than
+ * `cap`): GSMCAL_E_CAPACITY.  A window that leaves the stream: GSMCAL_E_INDEX, decided before a sample is read.
+ * gsmcal_last_call_report then returns the lines the .m file prints (:6,9,43,45,49,65,66). */
+int gsmcal_FCCH_demod(gsmcal_ctx* ctx, const double* s, long len, const double* pos_info, int rows, int ld,
+                      int oversampling_ratio, double carrier_freq, double* freq, double* snr, double* max_idx, int cap,
+                      int* num_fcch, double* mean_freq, double* carrier_ppm);
+
 /* ppm_out = total_ppm_calculation(ppm_in)                           total_ppm_calculation.m:5-21
  * (pure host arithmetic; no context needed) */
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out);
@@ -299,6 +326,20 @@ int gsmcal_calibrate_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, lon
                                int ntaps, const double* sch_training_sequence, int len_ts,
                                const double* carrier_freq, double* d_table, double* d_pos_info,
                                double* d_r_correct, long* d_r_len);
+
+/* FCCH_demod for D streams, on exactly the optional outputs of gsmcal_calibrate_batch[_dev]: r [D][stride] complex, r_len [D]
+ * (-1 where the reference returns r = -1), pos_info [D][2][GSMCAL_MAX_POS_ROWS] with -1 padding; carrier_freq: host [D].
+ * out: [D][GSMCAL_DEMOD_COLS], row = {num_fcch, mean_freq, carrier_ppm, status, freq[], snr[], max_idx[]} (GSMCAL_D_*), unused
+ * entries NaN.  Per-row outcomes go in the status column, not the return value: r_len = -1 or an all -1 pos_info gives
+ * GSMCAL_S_POST_NO_POS (num_fcch 0, the rest NaN); GSMCAL_E_CAPACITY / GSMCAL_E_INDEX as above (num_fcch = the type-0 rows,
+ * the rest NaN).  A burst's figures do not depend on the batch it is in: a row is bit-identical alone, at any position, and
+ * equal to what gsmcal_FCCH_demod returns.  _dev: device pointers, only enqueues on the context's stream -- directly behind a
+ * calibrate call, no host synchronisation in between; d_out may be device or pinned host memory.  The calls use a workspace of
+ * their own: gsmcal_last_batch_details / _snr and gsmcal_last_call_report keep answering for the call before. */
+int gsmcal_fcch_demod_batch(gsmcal_ctx* ctx, const double* r, long stride, const long* r_len, const double* pos_info, int d,
+                            int oversampling_ratio, const double* carrier_freq, double* out);
+int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
+                                int d, int oversampling_ratio, const double* carrier_freq, double* d_out);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,

@@ -7,7 +7,7 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan gsmcal_band_power; do
+ *            carrier_correct_post_SCH FCCH_demod total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan gsmcal_band_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
  *
@@ -53,7 +53,7 @@ static void chk(int rc, const char* what) {
 }
 
 /* The .m file this MEX file shadows disp()s its intermediate results (FCCH_coarse_position.m:92-94, FCCH_fine_correction.m:66,
- * 116,156-161,190, SCH_corr_rate_correction.m:80,118, carrier_correct_post_SCH.m:73-79, and a warning at every early exit): print
+ * 116,156-161,190, SCH_corr_rate_correction.m:80,118, carrier_correct_post_SCH.m:73-79, FCCH_demod.m:43-66, and a warning at every early exit): print
  * the same lines, from the library's report of the call just made (getenv GSMCAL_QUIET=1: run silent). */
 static void say(void) {
     char buf[8192];
@@ -246,6 +246,24 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     plhs[0] = lr < 0 ? scalar(-1.0) : cplx_col(r, (mwSize)lr);
     if (nlhs > 1) plhs[1] = scalar(cp);
     if (r) mxFree(r);
+
+#elif defined(GSMCAL_FN_FCCH_demod)
+    /* FCCH_demod(s,pos_info,ov,carrier_freq): prints what FCCH_demod.m:6-66 prints (it returns nothing); asked for outputs it
+     * also hands the printed figures back: [freq, snr, max_idx, carrier_ppm] = FCCH_demod(...), rows of num_fcch entries with
+     * max_idx the offset of :66.  At the :8 exit (pos_info == -1) the outputs are empty and carrier_ppm is NaN. */
+    mwSize n = 0, i;
+    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    int rows = (int)mxGetM(prhs[1]), nb = 0;
+    double v[3 * GSMCAL_MAX_HITS], mf, cp;
+    chk(gsmcal_FCCH_demod(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, (int)mxGetScalar(prhs[2]), mxGetScalar(prhs[3]),
+                          v, v + GSMCAL_MAX_HITS, v + 2 * GSMCAL_MAX_HITS, GSMCAL_MAX_HITS, &nb, &mf, &cp), "FCCH_demod");
+    say();
+    for (i = 0; i < 3 && (int)i < nlhs; ++i) {
+        mwSize k;
+        plhs[i] = mxCreateDoubleMatrix(1, (mwSize)nb, mxREAL);
+        for (k = 0; k < (mwSize)nb; ++k) REAL_PTR(plhs[i])[k] = v[i * GSMCAL_MAX_HITS + k];
+    }
+    if (nlhs > 3) plhs[3] = scalar(cp);
 
 #elif defined(GSMCAL_FN_total_ppm_calculation)
     /* ppm_out = total_ppm_calculation(ppm_in) */

@@ -14,6 +14,7 @@ sentinel returns (scalar -1.0 / inf, pos_info = [[-1, -1]]) so that tests read l
     [FCCH_pos,r,sampling_ppm,carrier_ppm] = FCCH_fine_correction(s,base_position,ov,carrier_freq)
     [pos_info,r,sampling_ppm] = SCH_corr_rate_correction(s,FCCH_pos,sch_training_sequence,ov)
     [r,carrier_ppm] = carrier_correct_post_SCH(s,pos_info,ov,carrier_freq)
+    FCCH_demod(s,pos_info,ov,carrier_freq)                           FCCH_demod.m:5 (what it prints, returned as a dict)
     ppm_out = total_ppm_calculation(ppm_in)
 
 Everything computes on the GPU through the C ABI; there is no CPU fallback.
@@ -27,7 +28,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import DEMOD_COLS, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -396,6 +397,30 @@ def SCH_equalise(s, pos_info, training_sequence, oversampling_ratio, ctx=None):
     return out[:nb.value]
 
 
+def FCCH_demod(s, pos_info, oversampling_ratio, carrier_freq, ctx=None):
+    """FCCH_demod(s, pos_info, ov, carrier_freq) -- FCCH_demod.m:5-66, the check behind the calibration: per FCCH burst of
+    pos_info the tone frequency `freq`, the in-band SNR `snr` (dB; NaN where the reference's noise_power is negative) and the
+    offset of the spectrum's peak `max_idx` (max_idx - (fft_len/2+1), :66); `mean_freq` and the carrier error still left,
+    `carrier_ppm`.  Returns a dict of these, or None at the :8 exit (pos_info all -1)."""
+    ctx = ctx or default_context()
+    buf, n = _r_in(s)
+    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
+    rows = pi.shape[0]
+    pic = np.ascontiguousarray(pi.T)
+    cap = int(np.sum(pi[:, 1] == 0)) if pi.shape[1] > 1 else 0
+    freq, snr, idx = (np.full(max(cap, 1), np.nan) for _ in range(3))
+    nb = C.c_int()
+    mf, cp = C.c_double(), C.c_double()
+    rc = ctx.check(ctx.lib.gsmcal_FCCH_demod(ctx.h, _dp(buf) if buf is not None else None, n, _dp(pic), rows, rows,
+                                             int(oversampling_ratio), float(carrier_freq), _dp(freq), _dp(snr), _dp(idx), cap,
+                                             C.byref(nb), C.byref(mf), C.byref(cp)), "FCCH_demod")
+    _say(ctx)
+    if rc == 10:
+        return None
+    k = nb.value
+    return {"freq": freq[:k], "snr": snr[:k], "max_idx": idx[:k].astype(np.int64), "mean_freq": mf.value, "carrier_ppm": cp.value}
+
+
 def total_ppm_calculation(ppm_in):
     lib = _lib.load()
     p = np.ascontiguousarray(np.atleast_1d(np.asarray(ppm_in, dtype=np.float64)))
@@ -450,6 +475,45 @@ def band_power_batch_dev(d_raw, d, n, coef, decim, d_power, ctx=None):
     coef = np.ascontiguousarray(np.atleast_1d(np.asarray(coef, dtype=np.float64)).ravel())
     ctx.check(ctx.lib.gsmcal_band_power_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), _dp(coef), len(coef), int(decim),
                                                   C.c_void_p(d_power)), "band_power_batch_dev")
+
+
+DEMOD_FIELDS = ("num_fcch", "mean_freq", "carrier_ppm", "status")      # columns 0..3 of a demod row; then freq | snr | max_idx
+
+
+def demod_rows(table):
+    """(D, DEMOD_COLS) table of fcch_demod_batch[_dev] -> dict of its columns (freq, snr, max_idx: (D, MAX_HITS), NaN unused)."""
+    t = np.asarray(table).reshape(-1, DEMOD_COLS)
+    out = {k: t[:, i] for i, k in enumerate(DEMOD_FIELDS)}
+    out["freq"], out["snr"], out["max_idx"] = (t[:, 4 + j * MAX_HITS: 4 + (j + 1) * MAX_HITS] for j in range(3))
+    return out
+
+
+def fcch_demod_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, carrier_freq, ctx=None):
+    """FCCH_demod.m:5-66 for D streams, on what calibrate_batch(..., want_r=True) returns: r_correct (D, N) complex, r_len (D,)
+    (-1 where the reference returns r = -1), pos_info_raw (D, 2, MAX_POS_ROWS).  Returns the (D, DEMOD_COLS) table (demod_rows
+    names its columns); per-row outcomes are in its status column."""
+    ctx = ctx or default_context()
+    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
+    d, stride = r.shape
+    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
+    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
+    if len(rl) != d:
+        raise ValueError("r_len must have one entry per stream")
+    cf = np.ascontiguousarray(np.broadcast_to(np.asarray(carrier_freq, dtype=np.float64), (d,)))
+    out = np.empty((d, DEMOD_COLS))
+    ctx.check(ctx.lib.gsmcal_fcch_demod_batch(ctx.h, _dp(r), stride, rl.ctypes.data_as(_lib.c_long_p), _dp(pi), d,
+                                              int(oversampling_ratio), _dp(cf), _dp(out)), "fcch_demod_batch")
+    return out
+
+
+def fcch_demod_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio, carrier_freq, d_out, ctx=None):
+    """Device-pointer form of fcch_demod_batch: only enqueues on the context's stream, e.g. directly behind calibrate_batch_dev
+    on its d_r_correct / d_r_len / d_pos_info (ctx.sync() before reading).  d_out: [d][DEMOD_COLS] doubles, device or pinned."""
+    ctx = ctx or default_context()
+    cf = np.ascontiguousarray(np.broadcast_to(np.asarray(carrier_freq, dtype=np.float64), (int(d),)))
+    ctx.check(ctx.lib.gsmcal_fcch_demod_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
+                                                  int(d), int(oversampling_ratio), _dp(cf), C.c_void_p(d_out)),
+              "fcch_demod_batch_dev")
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

@@ -65,6 +65,7 @@ int gsmcal_ctx_create_on_stream(int device_id, void* hip_stream, gsmcal_ctx** ou
     (void)hipFuncSetAttribute((const void*)k_post_chain_r<8, 512, 47>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_sch_equalise, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_sch_fd_training, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
+    (void)hipFuncSetAttribute((const void*)k_fcch_demod, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_fft_burst<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_fft_burst<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_burst_tone<0, 8, 47>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
@@ -139,7 +140,7 @@ void gsmcal_ctx_destroy(gsmcal_ctx* c) {
     fused_gate_unregister(c);
     DevBuf* bufs[] = {&c->coef, &c->ts, &c->cf, &c->table, &c->snrhit, &c->arr_in, &c->arr_out, &c->posinfo, &c->rlen,
                       &c->misc, &c->tw, &c->csum_head, &c->tw_sch, &c->bp_coef, &c->bp_state, &c->bp_part, &c->bp_raw,
-                      &c->bp_out};
+                      &c->bp_out, &c->fd_tw, &c->fd_cf, &c->fd_part, &c->fd_in, &c->fd_len, &c->fd_pos, &c->fd_out};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < MAX_LANES; ++i) {
@@ -673,6 +674,98 @@ int gsmcal_SCH_equalise(gsmcal_ctx* c, const double* s, long len, const double* 
         if (st[i] != 0) return st[i];                           // MATLAB: index exceeds matrix dimensions at s(sp:ep), :81
     *num_bursts = nb;
     return 0;
+}
+
+// ---- FCCH_demod.m:5-66: the check behind the calibration ------------------------------------------------------
+// k_fcch_demod (one workgroup per burst slot and stream) + k_fcch_demod_finish (one wave per stream) on the context's stream;
+// nothing of the lanes, the shared taps or the state of the calibrate / scan call before is touched.
+int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
+                                int ov, const double* carrier_freq, double* d_out) {
+    if (!c || !d_r || !d_r_len || !d_pos_info || !carrier_freq || !d_out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    if (ov > 256) return GSMCAL_E_UNSUPPORTED;
+    const int nfft = 148 * ov;                                  // FCCH_demod.m:13-16
+    const size_t lds = fd_lds_bytes(nfft);
+    if (lds > 159 * 1024) return GSMCAL_E_UNSUPPORTED;
+    ENTER(c);
+    c->cur = &c->lanes[0];                                      // the context's stream; the lane's buffers are not touched
+    const double fs = GSM_SYMBOL_RATE * (double)ov;             // :30-31
+    const int hnl = (int)ceil(((double)nfft * 200e3 / fs) / 2.0);   // :53 half_noise_len (55 for every ov)
+    if (c->fd_tw_n != nfft) {
+        RET_IF(ensure(c, c->fd_tw, (size_t)nfft * sizeof(cplx)));
+        LAUNCH(c, k_make_twiddles, dim3((nfft + 255) / 256), dim3(256), 0, (cplx*)c->fd_tw.p, nfft);
+        c->fd_tw_n = nfft;
+    }
+    if ((int)c->h_fd_cf.size() != d || !c->fd_cf.p || memcmp(c->h_fd_cf.data(), carrier_freq, (size_t)d * sizeof(double)) != 0) {
+        RET_IF(ensure(c, c->fd_cf, (size_t)d * sizeof(double)));
+        c->h_fd_cf.assign(carrier_freq, carrier_freq + d);
+        const hipError_t e = hipMemcpyAsync(c->fd_cf.p, c->h_fd_cf.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { c->h_fd_cf.clear(); c->err = std::string("hipMemcpyAsync (FCCH_demod carrier_freq): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
+    }
+    RET_IF(ensure(c, c->fd_part, (size_t)d * MAXH * FD_PART * sizeof(double)));
+    double* part = (double*)c->fd_part.p;
+    const long chunk = 65535;                                   // (the grid's y limit)
+    for (long lo = 0; lo < d; lo += chunk) {
+        const int S = (int)std::min(chunk, (long)d - lo);
+        LAUNCH(c, k_fcch_demod, dim3(MAXH, S), dim3(FD_THREADS), lds, (const cplx*)d_r + (size_t)lo * stride, stride, d_r_len + lo,
+               d_pos_info + (size_t)lo * 2 * MAXROWS, nfft, ov, hnl, (const cplx*)c->fd_tw.p, part + (size_t)lo * MAXH * FD_PART);
+    }
+    LAUNCH(c, k_fcch_demod_finish, dim3(d), dim3(64), 0, d_r_len, d_pos_info, (const double*)c->fd_cf.p, (const double*)part, d_out);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_fcch_demod_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
+                            const double* carrier_freq, double* out) {
+    if (!c || !r || !r_len || !pos_info || !carrier_freq || !out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    ENTER(c);
+    const size_t nr = (size_t)d * stride * sizeof(cplx), np = (size_t)d * 2 * MAXROWS * sizeof(double);
+    RET_IF(ensure(c, c->fd_in, nr));
+    RET_IF(ensure(c, c->fd_len, (size_t)d * sizeof(long)));
+    RET_IF(ensure(c, c->fd_pos, np));
+    RET_IF(ensure(c, c->fd_out, (size_t)d * GSMCAL_DEMOD_COLS * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(c->fd_in.p, r, nr, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->fd_len.p, r_len, (size_t)d * sizeof(long), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->fd_pos.p, pos_info, np, hipMemcpyHostToDevice, c->stream));
+    RET_IF(gsmcal_fcch_demod_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d, ov,
+                                       carrier_freq, (double*)c->fd_out.p));
+    HIPCHK(c, hipMemcpyAsync(out, c->fd_out.p, (size_t)d * GSMCAL_DEMOD_COLS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int gsmcal_FCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* pos_info, int rows, int ld, int ov, double carrier_freq,
+                      double* freq, double* snr, double* max_idx, int cap, int* num_fcch, double* mean_freq, double* carrier_ppm) {
+    if (!c || !pos_info || !num_fcch || rows < 1 || ld < rows || ov < 1 || cap < 0) return GSMCAL_E_ARG;
+    ENTER(c);
+    *num_fcch = 0;
+    if (mean_freq) *mean_freq = NAN;
+    if (carrier_ppm) *carrier_ppm = NAN;
+    std::vector<double> row(GSMCAL_DEMOD_COLS, NAN);
+    bool all_m1 = true;                                         // :8 `if pos_info == -1`: every element
+    int nb = 0;
+    for (int i = 0; i < rows; ++i) {
+        all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
+        nb += pos_info[ld + i] == 0.0;
+    }
+    if (all_m1) {
+        row[GSMCAL_D_STATUS] = GSMCAL_S_POST_NO_POS;
+        c->report = report_fcch_demod(row.data());
+        return GSMCAL_S_POST_NO_POS;
+    }
+    if (!s || len < 1) return GSMCAL_E_ARG;
+    if (rows > MAXROWS || nb > MAXH || nb > cap) return GSMCAL_E_CAPACITY;
+    if (nb > 0 && (!freq || !snr || !max_idx)) return GSMCAL_E_ARG;
+    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
+    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
+    RET_IF(gsmcal_fcch_demod_batch(c, s, len, &len, pi.data(), 1, ov, &carrier_freq, row.data()));
+    const int status = (int)row[GSMCAL_D_STATUS];
+    if (status < 0) return status;                              // MATLAB: index exceeds matrix dimensions at s(sp:ep), :26
+    for (int i = 0; i < nb; ++i) { freq[i] = row[GSMCAL_D_FREQ + i]; snr[i] = row[GSMCAL_D_SNR + i]; max_idx[i] = row[GSMCAL_D_MAX_IDX + i]; }
+    *num_fcch = nb;
+    if (mean_freq) *mean_freq = row[GSMCAL_D_MEAN_FREQ];
+    if (carrier_ppm) *carrier_ppm = row[GSMCAL_D_CARRIER_PPM];
+    c->report = report_fcch_demod(row.data());
+    return status;
 }
 
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------

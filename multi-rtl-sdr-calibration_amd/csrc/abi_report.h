@@ -1,5 +1,5 @@
 // abi_report.h -- the reference's console diagnostics (FCCH_coarse_position.m:6,28,92-94, FCCH_fine_correction.m:6,13,66,
-// 96-99,116,156-161,190-193, SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79) as TEXT:
+// 96-99,116,156-161,190-193, SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79, FCCH_demod.m:6,9,43-49,65-66) as TEXT:
 // the per-function entry points of abi_calls.h have the stream's state on the host anyway and leave the lines the .m file would
 // have disp()ed in the context; gsmcal_last_call_report() hands them to the MEX gateway (mexPrintf) or the Python mirror.
 // Included by gsmcal.hip ahead of abi_calls.h (host code only).
@@ -123,6 +123,19 @@ std::string report_post(const StreamState& st) {
     for (int i = 0; i < st.n_rows && i < MAXROWS; ++i) nb += st.pos_info[MAXROWS + i] == 0.0;
     if (nb > MAXH) nb = MAXH;
     if (nb > 0) rep_tone(r, "post SCH:", st.fo_burst, nb, st.carrier_ppm2);
+    return r;
+}
+
+// FCCH_demod.m:6,9,43,45,49,65,66.  row: one row of the FCCH_demod table (GSMCAL_D_*), status 0 or GSMCAL_S_POST_NO_POS.
+std::string report_fcch_demod(const double* row) {
+    std::string r = " \n";
+    if ((int)row[GSMCAL_D_STATUS] == GSMCAL_S_POST_NO_POS) return r + "FCCH demod: Warning! No valid position information!\n";
+    const int nb = (int)row[GSMCAL_D_NUM_FCCH];
+    r += "FCCH demod: FCCH freq " + rep_num2str(row + GSMCAL_D_FREQ, nb) + "\n";
+    r += "FCCH demod: mean FCCH freq " + rep_num2str(row[GSMCAL_D_MEAN_FREQ]) + "\n";
+    r += "FCCH demod: carrier error ppm " + rep_num2str(row[GSMCAL_D_CARRIER_PPM]) + "\n";
+    r += "FCCH demod: SNR " + rep_num2str(row + GSMCAL_D_SNR, nb) + "\n";
+    r += "FCCH demod: max idx " + rep_num2str(row + GSMCAL_D_MAX_IDX, nb) + "\n";
     return r;
 }
 

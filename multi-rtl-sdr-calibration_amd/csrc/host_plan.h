@@ -145,6 +145,11 @@ struct gsmcal_ctx {
     // taps and every answer about the calibration / scan call before it untouched
     DevBuf bp_coef, bp_state, bp_part, bp_raw, bp_out;
     std::vector<double> h_bp_coef;
+    // FCCH_demod (gsmcal_FCCH_demod, gsmcal_fcch_demod_batch*): workspaces of its own for the same reason -- its twiddle table too,
+    // the oversampling ratio may differ from the chain's
+    DevBuf fd_tw, fd_cf, fd_part, fd_in, fd_len, fd_pos, fd_out;
+    int fd_tw_n = 0;
+    std::vector<double> h_fd_cf;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream
     static constexpr int AG_SLOTS = 4;
