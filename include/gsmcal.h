@@ -300,6 +300,25 @@ int gsmcal_band_power_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, 
 int gsmcal_band_power_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, const double* coef,
                                 int ntaps, int decim, double* d_power);
 
+/* Several sub-band powers per capture (multi_rtl_sdr_diversity_scanner_another_bak.m:186-210, the multi-channel diversity
+ * scanner: every grid point that falls inside a capture is taken out of that one capture):
+ *   power[c][j] = mean(abs(filter(coef,1, raw2iq(s_c).*exp(1i*(1:N)'*phase_rotate[c][j]))(1:decim:end)).^2)
+ * raw: D x 2N bytes, capture-major; phase_rotate: HOST memory [D][nsub] in both forms (radians per sample, :195, taken
+ * verbatim: the sign is the caller's), NaN = unused slot (its power is NaN, nothing is computed for it); power: [D][nsub].
+ * decim = 1 is the script (:203); decim > 1 keeps rows 1:decim:end as multi_rtl_sdr_diversity_scanner.m:156-158 does.
+ * 1 <= ntaps <= 128 (:52-53), 1 <= nsub <= GSMCAL_MAX_SUBBANDS, decim >= 1, d >= 1, n >= 1, no NULL pointer, no infinite
+ * phase_rotate: anything else GSMCAL_E_ARG, decided before anything is enqueued.  The mixer is folded into the taps
+ * (h_k = coef_k e^{-jwk}, built on the host in double): no phase ramp over n is formed.  DC as in gsmcal_band_power_batch:
+ * a constant capture gives exactly 0 in every sub-band.  A (capture, phase) pair gives the same bits in any slot, beside any
+ * other sub-bands, at any position in a batch of any size.  Workspaces of their own: gsmcal_last_batch_details / _snr and
+ * gsmcal_last_call_report keep answering for the call before.  _dev: enqueues on the context's stream only; d_power may be
+ * device or pinned host memory. */
+#define GSMCAL_MAX_SUBBANDS 16
+int gsmcal_subband_power_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, const double* coef, int ntaps, int decim,
+                               const double* phase_rotate, int nsub, double* power);
+int gsmcal_subband_power_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, const double* coef, int ntaps,
+                                   int decim, const double* phase_rotate, int nsub, double* d_power);
+
 /* Scanner detect loop for D captures (multi_rtl_sdr_gsm_FCCH_scanner.m:132-135 front end,
  * :164 FCCH_coarse_position, :168-185 acceptance).  Outputs per capture: snr, num_hit (as the
  * driver's arrays), optional positions/snrs [D][GSMCAL_MAX_HITS] and counts [D] (NULL to skip). */

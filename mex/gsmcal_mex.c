@@ -7,14 +7,16 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan gsmcal_band_power; do
+ *            carrier_correct_post_SCH FCCH_demod total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan gsmcal_band_power \
+ *            gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
  *
- * The last three are not shadows of .m files: they are the fused entry points (one call per driver loop body)
+ * The last four are not shadows of .m files: they are the fused entry points (one call per driver loop body)
  *   [table, pos_info] = gsmcal_calibrate(s, coef, sch_training_sequence, freq)   replaces gsm_sync_demod.m:107-124
  *   [snr, num_hit]    = gsmcal_fcch_scan(s, coef)                                replaces ..FCCH_scanner.m:132-135,163-186
  *   power_spectrum    = gsmcal_band_power(s_all, coef, decimate_ratio)          replaces ..split_scanner.m:154-156
+ *   power             = gsmcal_subband_power(s, coef, phase_rotate)             replaces ..diversity_scanner_another_bak.m:192-204
  * with s the 2N x D uint8 matrix fread() delivers (gsm_sync_demod.m:96; pass uint8(s) if it was read as double).
  * tests/test_abi_cpu.py compiles every target against a declaration-only mex.h (tests/mex_stub) as a prototype check.
  *
@@ -326,6 +328,19 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     chk(gsmcal_band_power_batch(ctx(), U8_PTR(prhs[0]), (int)d, (long)(rows2n / 2), REAL_PTR(prhs[1]),
                                 (int)mxGetNumberOfElements(prhs[1]), (int)mxGetScalar(prhs[2]), REAL_PTR(plhs[0])),
         "gsmcal_band_power");
+#elif defined(GSMCAL_FN_gsmcal_subband_power)
+    /* power = gsmcal_subband_power(s, coef, phase_rotate [, decimate_ratio])     multi_rtl_sdr_diversity_scanner_another_bak.m:192-204
+     * for all captures and all their sub-frequencies: power(j,c) = mean(abs(filter(coef,1,raw2iq(s(:,c)).*exp(1i*(1:N)'*phase_rotate(j,c)))).^2)
+     * s: 2N x D uint8, one column per capture; coef: real taps (at most 128); phase_rotate: J x D (J <= GSMCAL_MAX_SUBBANDS), NaN = unused
+     * slot; power: J x D linear, NaN in unused slots.  decimate_ratio (default 1, the script) keeps rows 1:decimate_ratio:end. */
+    mwSize rows2n = mxGetM(prhs[0]), d = mxGetN(prhs[0]);
+    if (!mxIsUint8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s must be uint8 (the bytes fread(...,'uint8') delivers)");
+    if (nrhs < 3 || mxIsComplex(prhs[1]) || mxIsComplex(prhs[2]) || mxGetN(prhs[2]) != d)
+        mexErrMsgIdAndTxt("gsmcal:args", "usage: power = gsmcal_subband_power(s, coef, phase_rotate) with phase_rotate J x size(s,2)");
+    plhs[0] = mxCreateDoubleMatrix(mxGetM(prhs[2]), d, mxREAL);
+    chk(gsmcal_subband_power_batch(ctx(), U8_PTR(prhs[0]), (int)d, (long)(rows2n / 2), REAL_PTR(prhs[1]),
+                                   (int)mxGetNumberOfElements(prhs[1]), nrhs > 3 ? (int)mxGetScalar(prhs[3]) : 1, REAL_PTR(prhs[2]),
+                                   (int)mxGetM(prhs[2]), REAL_PTR(plhs[0])), "gsmcal_subband_power");
 #else
 #error "define one GSMCAL_FN_<function> (see the header comment)"
 #endif

@@ -16,6 +16,7 @@ c_u8_p = C.POINTER(C.c_uint8)
 MAX_HITS = 24
 MAX_POS_ROWS = 6 * MAX_HITS
 TABLE_COLS = 10
+MAX_SUBBANDS = 16
 DEMOD_COLS = 4 + 3 * MAX_HITS      # one row of fcch_demod_batch: num_fcch, mean_freq, carrier_ppm, status, freq[], snr[], max_idx[]
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
@@ -72,6 +73,10 @@ SIGNATURES = {
                                           c_double_p]),
     "gsmcal_band_power_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                               C.c_void_p]),
+    "gsmcal_subband_power_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
+                                             c_double_p, C.c_int, c_double_p]),
+    "gsmcal_subband_power_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
+                                                 c_double_p, C.c_int, C.c_void_p]),
     "gsmcal_fcch_scan_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_int_p]),
     "gsmcal_fcch_scan_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int,

@@ -477,6 +477,39 @@ def band_power_batch_dev(d_raw, d, n, coef, decim, d_power, ctx=None):
                                                   C.c_void_p(d_power)), "band_power_batch_dev")
 
 
+def _subband_args(coef, phase_rotate, d):
+    coef = np.ascontiguousarray(np.atleast_1d(np.asarray(coef, dtype=np.float64)).ravel())
+    w = np.ascontiguousarray(np.atleast_2d(np.asarray(phase_rotate, dtype=np.float64)))
+    if w.ndim != 2 or w.shape[0] != d:
+        raise ValueError("phase_rotate must be (D, J): one row of sub-band phases per capture")
+    return coef, w
+
+
+def subband_power_batch(raw, coef, phase_rotate, decim=1, ctx=None):
+    """raw: (D, 2N) uint8, phase_rotate: (D, J) radians per sample (NaN = unused slot) -> (D, J) linear powers
+    mean(abs(filter(coef,1, raw2iq(s).*exp(1i*(1:N)'*phase_rotate[c][j]))(1:decim:end)).^2)
+    (multi_rtl_sdr_diversity_scanner_another_bak.m:194-203; decim = 1 is the script).  NaN slots return NaN."""
+    ctx = ctx or default_context()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    if raw.ndim != 2 or raw.shape[1] % 2:
+        raise ValueError("raw must be (D, 2N) bytes")
+    d, two_n = raw.shape
+    coef, w = _subband_args(coef, phase_rotate, d)
+    out = np.empty(w.shape)
+    ctx.check(ctx.lib.gsmcal_subband_power_batch(ctx.h, raw.ctypes.data_as(_lib.c_u8_p), d, two_n // 2, _dp(coef), len(coef),
+                                                 int(decim), _dp(w), w.shape[1], _dp(out)), "subband_power_batch")
+    return out
+
+
+def subband_power_batch_dev(d_raw, d, n, coef, phase_rotate, d_power, decim=1, ctx=None):
+    """Device-pointer form of subband_power_batch: only enqueues on the context's stream (ctx.sync() before reading).
+    d_raw: [d][2n] bytes; phase_rotate: (d, J) on the host; d_power: [d][J] doubles in device or pinned host memory."""
+    ctx = ctx or default_context()
+    coef, w = _subband_args(coef, phase_rotate, int(d))
+    ctx.check(ctx.lib.gsmcal_subband_power_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), _dp(coef), len(coef), int(decim),
+                                                     _dp(w), w.shape[1], C.c_void_p(d_power)), "subband_power_batch_dev")
+
+
 DEMOD_FIELDS = ("num_fcch", "mean_freq", "carrier_ppm", "status")      # columns 0..3 of a demod row; then freq | snr | max_idx
 
 
@@ -547,6 +580,38 @@ def diversity_spectrum_scan(s_all, start_freq, end_freq, freq_step, gain=0, obse
     power = band_power_batch(raw, coef, decim, ctx=ctx).reshape(num_dongle, nf)
     return dist.diversity_spectrum_record(power, start_freq, end_freq, freq_step, num_dongle, gain, observe_time,
                                           sample_rate)
+
+
+def multichannel_spectrum_scan(r_all_raw, start_freq, end_freq, freq_step, gain=0, observe_time=0.2, sample_rate=2.048e6,
+                               shift_sign=-1, decim=1, ctx=None):
+    """multi_rtl_sdr_diversity_scanner_another_bak.m:186-231 after the captures: r_all_raw is (2*num_samples, num_dongle,
+    length(real_freq)) uint8, the script's s per real_freq_idx (:155-176) before raw2iq.  All num_dongle*length(real_freq)
+    captures go to the GPU in one call, every grid point of a capture is taken out of it (dist.multichannel_frequency_plan).
+    shift_sign: the sign of the mixer's phase.  -1 (default) does what the comment at :193 says, the sub-frequency goes to 0 Hz
+    and power_spectrum[:, i] belongs to freq[i]; +1 is the script's literal line :195-196, which measures the point mirrored
+    about the capture's centre.  decim = 1 is the script (:203).  Returns dist.multichannel_spectrum_record's fields."""
+    from . import dist
+    if shift_sign not in (-1, 1):
+        raise ValueError("shift_sign must be -1 or +1")
+    _, coef, _, num_samples = dist.spectrum_filter(sample_rate, freq_step, observe_time)
+    plan = dist.multichannel_frequency_plan(start_freq, end_freq, freq_step, sample_rate)
+    r = np.asarray(r_all_raw, dtype=np.uint8)
+    ncap = len(plan["real_freq"])
+    if r.ndim != 3 or r.shape[0] != 2 * num_samples or r.shape[2] != ncap:
+        raise ValueError("r_all_raw must be (2*num_samples, num_dongle, length(real_freq))")
+    num_dongle = r.shape[1]
+    nsub = max(len(v) for v in plan["freq_set"])
+    if nsub > _lib.MAX_SUBBANDS:
+        raise ValueError("a capture holds %d grid points: more than %d" % (nsub, _lib.MAX_SUBBANDS))
+    w = np.full((ncap, nsub), np.nan)
+    for c, rel in enumerate(plan["relative_sub_freq_set"]):
+        w[c, :len(rel)] = shift_sign * rel * 2 * np.pi / sample_rate                          # :195
+    raw = r.transpose(1, 2, 0).reshape(num_dongle * ncap, 2 * num_samples)      # capture (dongle i, real_freq c) = row i*ncap + c
+    power = subband_power_batch(raw, coef, np.tile(w, (num_dongle, 1)), decim=decim, ctx=ctx).reshape(num_dongle, ncap, nsub)
+    ps = np.empty((num_dongle, len(plan["freq"])))
+    for c, fs in enumerate(plan["freq_set"]):
+        ps[:, fs] = power[:, c, :len(fs)]                                       # idx of :186-210, capture by capture
+    return dist.multichannel_spectrum_record(ps, start_freq, end_freq, freq_step, num_dongle, gain, observe_time, sample_rate)
 
 
 def fcch_scan_batch(raw, coef, ctx=None):

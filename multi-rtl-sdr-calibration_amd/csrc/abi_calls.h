@@ -140,7 +140,8 @@ void gsmcal_ctx_destroy(gsmcal_ctx* c) {
     fused_gate_unregister(c);
     DevBuf* bufs[] = {&c->coef, &c->ts, &c->cf, &c->table, &c->snrhit, &c->arr_in, &c->arr_out, &c->posinfo, &c->rlen,
                       &c->misc, &c->tw, &c->csum_head, &c->tw_sch, &c->bp_coef, &c->bp_state, &c->bp_part, &c->bp_raw,
-                      &c->bp_out, &c->fd_tw, &c->fd_cf, &c->fd_part, &c->fd_in, &c->fd_len, &c->fd_pos, &c->fd_out};
+                      &c->bp_out, &c->fd_tw, &c->fd_cf, &c->fd_part, &c->fd_in, &c->fd_len, &c->fd_pos, &c->fd_out,
+                      &c->sb_taps, &c->sb_idx, &c->sb_state, &c->sb_part, &c->sb_raw, &c->sb_out};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < MAX_LANES; ++i) {
@@ -877,6 +878,111 @@ int gsmcal_band_power_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, co
     HIPCHK(c, hipMemcpyAsync(c->bp_raw.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
     RET_IF(gsmcal_band_power_batch_dev(c, (const uint8_t*)c->bp_raw.p, d, n, coef, ntaps, decim, (double*)c->bp_out.p));
     HIPCHK(c, hipMemcpyAsync(power, c->bp_out.p, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- sub-band power: multi_rtl_sdr_diversity_scanner_another_bak.m:186-210, every grid point inside a capture out of that capture
+// The script's mixer exp(1i*(1:N)*w) is folded into the taps on the host (kernels_subband.h): one row h_k = coef_k e^{-jwk} per
+// distinct finite w of the call, computed in double and cached like h_bp_coef, plus a [capture][slot] index table (-1: NaN slot).
+// Passes: k_band_power_clear + k_dc_sum (exact byte sums), k_subband_power, k_subband_power_finish.
+static bool sb_args_ok(const void* raw, int d, long n, const double* coef, int ntaps, int decim, const double* phase_rotate, int nsub,
+                       const void* power) {
+    if (!raw || !coef || !phase_rotate || !power || d < 1 || n < 1 || n > (1L << 40) || ntaps < 1 || ntaps > SB_MAX_TAPS ||
+        nsub < 1 || nsub > GSMCAL_MAX_SUBBANDS || decim < 1)
+        return false;
+    for (size_t i = 0; i < (size_t)d * nsub; ++i)
+        if (std::isinf(phase_rotate[i])) return false;
+    return true;
+}
+
+int gsmcal_subband_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n, const double* coef, int ntaps, int decim,
+                                   const double* phase_rotate, int nsub, double* d_power) {
+    if (!c || !sb_args_ok(d_raw, d, n, coef, ntaps, decim, phase_rotate, nsub, d_power)) return GSMCAL_E_ARG;
+    ENTER(c);
+    c->cur = &c->lanes[0];                              // the context's stream; the lane's buffers are not touched
+    const long nd = (n + decim - 1) / decim;
+    // kept rows per block as in gsmcal_band_power_batch_dev, with the LDS of GSMCAL_MAX_SUBBANDS tap rows set aside whatever nsub
+    // is: the tiling -- and with it every bit of a sub-band's power -- depends on n, decim and ntaps only
+    int rows = (int)std::min<long>(BP_MAX_ROWS, std::max<long>(BP_ROWS, (BP_SPAN / decim) / BP_ROWS * BP_ROWS));
+    if (sb_lds_bytes(rows, decim, ntaps, SB_MAX_SUBBANDS) > BP_LDS_BYTES) {
+        const long fit = ((long)(BP_LDS_BYTES - SB_MAX_SUBBANDS * ntaps * sizeof(cplx)) / 2 - 8 - 24 - ntaps) / decim + 1;
+        rows = (int)std::max(1L, std::min<long>(rows, fit));
+    }
+    const long nblk = (nd + rows - 1) / rows;
+    if (nblk > (1L << 30)) return GSMCAL_E_ARG;
+    // distinct finite phases in order of first appearance (-0 counts as 0: the same taps) and the index table
+    const size_t cells = (size_t)d * nsub;
+    std::vector<double> w;
+    std::vector<int> idx(cells);
+    {
+        std::unordered_map<unsigned long long, int> seen;
+        for (size_t i = 0; i < cells; ++i) {
+            const double v = phase_rotate[i] == 0.0 ? 0.0 : phase_rotate[i];
+            if (std::isnan(v)) { idx[i] = -1; continue; }
+            unsigned long long key;
+            memcpy(&key, &v, sizeof(key));
+            auto it = seen.find(key);
+            if (it == seen.end()) { it = seen.emplace(key, (int)w.size()).first; w.push_back(v); }
+            idx[i] = it->second;
+        }
+    }
+    const bool same_coef = (int)c->h_sb_coef.size() == ntaps && memcmp(c->h_sb_coef.data(), coef, (size_t)ntaps * sizeof(double)) == 0;
+    const bool same_w = c->h_sb_w.size() == w.size() && (w.empty() || memcmp(c->h_sb_w.data(), w.data(), w.size() * sizeof(double)) == 0);
+    if (!w.empty() && (!same_coef || !same_w || !c->sb_taps.p)) {
+        const size_t nb = w.size() * ntaps * sizeof(cplx);
+        RET_IF(ensure(c, c->sb_taps, nb));
+        c->h_sb_coef.assign(coef, coef + ntaps);
+        c->h_sb_w = w;
+        c->h_sb_rows.resize(w.size() * ntaps * 2);
+        for (size_t u = 0; u < w.size(); ++u)
+            for (int m = 0; m < ntaps; ++m) {              // row[m] multiplies the sample m after the oldest: tap k = ntaps-1-m
+                const int k = ntaps - 1 - m;
+                c->h_sb_rows[(u * ntaps + m) * 2] = coef[k] * cos((double)k * w[u]);
+                c->h_sb_rows[(u * ntaps + m) * 2 + 1] = -(coef[k] * sin((double)k * w[u]));
+            }
+        const hipError_t e = hipMemcpyAsync(c->sb_taps.p, c->h_sb_rows.data(), nb, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { c->h_sb_coef.clear(); c->h_sb_w.clear(); c->err = std::string("hipMemcpyAsync (sub-band taps): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
+    }
+    if (c->h_sb_idx != idx || !c->sb_idx.p) {
+        RET_IF(ensure(c, c->sb_idx, cells * sizeof(int)));
+        c->h_sb_idx.swap(idx);
+        const hipError_t e = hipMemcpyAsync(c->sb_idx.p, c->h_sb_idx.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { c->h_sb_idx.clear(); c->err = std::string("hipMemcpyAsync (sub-band index table): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
+    }
+    RET_IF(ensure(c, c->sb_state, (size_t)d * sizeof(StreamState)));
+    RET_IF(ensure(c, c->sb_part, (size_t)d * nblk * nsub * sizeof(double)));
+    StreamState* st = (StreamState*)c->sb_state.p;
+    double* part = (double*)c->sb_part.p;
+    const int* didx = (const int*)c->sb_idx.p;
+    const size_t lds = sb_lds_bytes(rows, decim, ntaps, nsub);
+    LAUNCH(c, k_band_power_clear, dim3((d + 255) / 256), dim3(256), 0, st, d);
+    const long chunk = 65535;                           // (the grid's y limit)
+    for (long lo = 0; lo < d; lo += chunk) {
+        const int S = (int)std::min(chunk, (long)d - lo);
+        const uint8_t* raw = d_raw + (size_t)lo * 2 * n;
+        int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));           // dc_means()'s geometry
+        blocks = std::max(1, std::min(blocks, std::max(1, 4096 / S)));
+        LAUNCH(c, k_dc_sum, dim3(blocks, S), dim3(256), 0, raw, 2 * n, st + lo);
+        LAUNCH(c, k_subband_power, dim3((unsigned)nblk, S), dim3(256), lds, raw, 2 * n, (const StreamState*)(st + lo),
+               (const cplx*)c->sb_taps.p, didx + lo * nsub, ntaps, nsub, decim, nd, rows, part + lo * nblk * nsub);
+    }
+    LAUNCH(c, k_subband_power_finish, dim3((unsigned)((cells + 63) / 64)), dim3(64), 0, (const double*)part, didx, (int)nblk, d, nsub,
+           n, nd, d_power);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_subband_power_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, const double* coef, int ntaps, int decim,
+                               const double* phase_rotate, int nsub, double* power) {
+    if (!c || !sb_args_ok(raw, d, n, coef, ntaps, decim, phase_rotate, nsub, power)) return GSMCAL_E_ARG;
+    ENTER(c);
+    const size_t nout = (size_t)d * nsub * sizeof(double);
+    RET_IF(ensure(c, c->sb_raw, (size_t)2 * n * d));
+    RET_IF(ensure(c, c->sb_out, nout));
+    HIPCHK(c, hipMemcpyAsync(c->sb_raw.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
+    RET_IF(gsmcal_subband_power_batch_dev(c, (const uint8_t*)c->sb_raw.p, d, n, coef, ntaps, decim, phase_rotate, nsub, (double*)c->sb_out.p));
+    HIPCHK(c, hipMemcpyAsync(power, c->sb_out.p, nout, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include <dlfcn.h>
@@ -29,6 +30,7 @@
 #include "kernels_frontend.h"
 #include "kernels_demod.h"
 #include "kernels_spectrum.h"
+#include "kernels_subband.h"
 #include "state.h"
 
 #define GSMCAL_VERSION "gsmcal-mi355x 0.1 (gfx950)"

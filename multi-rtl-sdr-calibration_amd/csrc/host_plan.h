@@ -150,6 +150,12 @@ struct gsmcal_ctx {
     DevBuf fd_tw, fd_cf, fd_part, fd_in, fd_len, fd_pos, fd_out;
     int fd_tw_n = 0;
     std::vector<double> h_fd_cf;
+    // sub-band power (gsmcal_subband_power_batch*): workspaces of its own again.  sb_taps: one modulated tap row per distinct
+    // phase_rotate value, built on the host (h_sb_coef / h_sb_w: what the rows on the device were built from); sb_idx: the
+    // [capture][slot] table into them (h_sb_idx: its host copy, uploaded only when it changes)
+    DevBuf sb_taps, sb_idx, sb_state, sb_part, sb_raw, sb_out;
+    std::vector<double> h_sb_coef, h_sb_w, h_sb_rows;
+    std::vector<int> h_sb_idx;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream
     static constexpr int AG_SLOTS = 4;

@@ -531,3 +531,38 @@ def diversity_spectrum_record(power_spectrum, start_freq, end_freq, freq_step, n
             "sample_rate": sample_rate, "coef": coef,
             "filename": "scan_%s_%s_gain%s_%sdongles.mat" % (_num2str(start_freq), _num2str(end_freq), _num2str(gain),
                                                              _num2str(num_dongle))}
+
+
+# ------------------------------------------------------------------------------------------------
+# multi-channel diversity scanner (multi_rtl_sdr_diversity_scanner_another_bak.m)
+# ------------------------------------------------------------------------------------------------
+def multichannel_frequency_plan(start_freq, end_freq, freq_step, sample_rate):
+    """multi_rtl_sdr_diversity_scanner_another_bak.m:64-81: the dongles tune only every sample_rate/4 and every grid point
+    inside a capture is taken out of it.
+
+    freq = start:step:end; real_freq = start:sample_rate/4:end, plus one more when real_freq(end) + sample_rate/8 < freq(end)
+    (:67-69); capture i holds the points with freq > real_freq(i) - sample_rate/8 & freq <= real_freq(i) + sample_rate/8 (:77,
+    the strict > and the <=).  Returns dict(freq, real_freq, freq_set: per capture the indices into freq (0-based),
+    relative_sub_freq_set: per capture freq(freq_set) - real_freq(i), :80).  Units come in the order of idx at :186-210:
+    capture by capture, the points of a capture ascending."""
+    if not (freq_step > 0 and sample_rate > 0 and end_freq >= start_freq):
+        raise ValueError("freq_step and sample_rate must be positive and end_freq >= start_freq")
+    n = int(np.floor((end_freq - start_freq) / freq_step + 1e-9)) + 1           # length(start:step:end)
+    freq = start_freq + freq_step * np.arange(n, dtype=np.float64)
+    real_step = sample_rate / 4.0                                               # :65
+    nr = int(np.floor((end_freq - start_freq) / real_step + 1e-9)) + 1
+    real_freq = start_freq + real_step * np.arange(nr, dtype=np.float64)
+    if real_freq[-1] + real_step / 2 < freq[-1]:                                # :67-69
+        real_freq = np.append(real_freq, real_freq[-1] + real_step)
+    freq_set, rel = [], []
+    for c in real_freq:
+        k = np.flatnonzero((freq > c - real_step / 2) & (freq <= c + real_step / 2))          # :75-77
+        freq_set.append(k)
+        rel.append(freq[k] - c)                                                 # :80
+    return {"freq": freq, "real_freq": real_freq, "freq_set": freq_set, "relative_sub_freq_set": rel}
+
+
+def multichannel_spectrum_record(power_spectrum, start_freq, end_freq, freq_step, num_dongle, gain, observe_time, sample_rate):
+    """The fields multi_rtl_sdr_diversity_scanner_another_bak.m:225-231 saves: power_spectrum (num_dongle x length(freq)),
+    power_spectrum_combine = mean(power_spectrum, 1) (:227, linear), the scalars, coef and the file name of :230."""
+    return diversity_spectrum_record(power_spectrum, start_freq, end_freq, freq_step, num_dongle, gain, observe_time, sample_rate)
