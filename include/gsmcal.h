@@ -88,8 +88,27 @@ enum {
 };
 
 /* ---- algorithm thresholds (the constants the reference hard-codes inside its functions) ---------- */
-/* Defaults = the reference's literals.  gsmcal_set_params() takes effect from the next call on; the fields marked
- * "geometry" size windows and launch shapes and must keep their default (any other value: GSMCAL_E_UNSUPPORTED). */
+/* Defaults = the reference's literals.  gsmcal_set_params() takes effect from the next call on (calls in flight finish with the
+ * values they were made under; a captured graph is never replayed across a change); the fields marked "geometry" size windows
+ * and launch shapes and must keep their default (any other value: GSMCAL_E_UNSUPPORTED).
+ * Accepted ranges (anything else: GSMCAL_E_ARG, and the context keeps the values it had):
+ *   min_hits        2 .. GSMCAL_MAX_HITS (24)
+ *   scan_min_hits   >= 1.  At 1 a capture in which nothing was found is accepted as the reference's rule would accept it: its
+ *                   FCCH_pos = FCCH_snr = -1 is one element with no gap to refuse, so snr = -1 and num_hit = 1
+ *   post_min_bcch   >= 0 (0: the :15 exit is never taken)
+ *   coarse_th_db, fine_max_ppm, fine_gate_snr_db, sch_max_ppm, scan_spacing, scan_spacing_idle, scan_tol
+ *                   any double but NaN, infinities included (every comparison with NaN is false: refused, not defined).
+ *                   Comparisons are the reference's strict ones: hit iff snr - avg > coarse_th_db; a gap is in a spacing class
+ *                   iff |gap - 10 or 11 frames| < floor(frames * max_ppm * 1e-6); gate iff snr < fine_gate_snr_db; a scanner gap
+ *                   is refused iff |gap - spacing| > scan_tol.  coarse_th_db below -989 lets the first window hit (the moving
+ *                   average is seeded with 999 dB): the fine stage then answers GSMCAL_E_INDEX, as MATLAB would stop.
+ *                   fine_max_ppm / sch_max_ppm above 47 619 let one gap pass both class tests: it counts twice at :95 / :106,
+ *                   and where the count still fits the eleven-frame class wins (:129-130).
+ *                   Raising them does not widen what the resampling stages can follow: their tile and window buffers are sized for
+ *                   the reference's bounds plus a tenth, and a measured stretch above +4400 ppm (FCCH_fine_correction.m:113) or
+ *                   +440 ppm (SCH_corr_rate_correction.m:116) is answered with GSMCAL_E_UNSUPPORTED -- in the table's status
+ *                   column for a batch row -- instead of the reference's resampled stream.  From raw bytes the search windows
+ *                   themselves keep the error far below that; hand-given positions can exceed it. */
 typedef struct gsmcal_params {
     double coarse_th_db;        /* FCCH_coarse_position.m:21          th = 10            hit iff snr - avg > th            */
     int coarse_mv_factor;       /* FCCH_coarse_position.m:22          mv_len = 10*fft_len                     (geometry)  */

@@ -22,7 +22,17 @@ int gsmcal_set_params(gsmcal_ctx* c, const gsmcal_params* p) {
         c->err = "gsmcal_set_params: a geometry field differs from its default";
         return GSMCAL_E_UNSUPPORTED;
     }
-    if (p->min_hits < 2 || p->min_hits > GSMCAL_MAX_HITS || p->scan_min_hits < 1 || p->post_min_bcch < 0) return GSMCAL_E_ARG;
+    if (p->min_hits < 2 || p->min_hits > GSMCAL_MAX_HITS || p->scan_min_hits < 1 || p->post_min_bcch < 0) {
+        c->err = "gsmcal_set_params: min_hits outside 2..GSMCAL_MAX_HITS, scan_min_hits < 1 or post_min_bcch < 0";
+        return GSMCAL_E_ARG;
+    }
+    // every comparison with a NaN threshold is false: the coarse detector would never hit and its certificate never decide, the
+    // spacing classes would be empty, the SNR gate open -- no caller means that; refused rather than defined
+    if (std::isnan(p->coarse_th_db) || std::isnan(p->fine_max_ppm) || std::isnan(p->fine_gate_snr_db) || std::isnan(p->sch_max_ppm) ||
+        std::isnan(p->scan_spacing) || std::isnan(p->scan_spacing_idle) || std::isnan(p->scan_tol)) {
+        c->err = "gsmcal_set_params: a threshold is NaN";
+        return GSMCAL_E_ARG;
+    }
     c->params = *p;
     ++c->params_epoch;
     return 0;

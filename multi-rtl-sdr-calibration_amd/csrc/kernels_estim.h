@@ -629,6 +629,15 @@ __device__ __forceinline__ double grid_pos(unsigned a_mask, unsigned b_mask, dou
     return acc + first - 1.0;
 }
 
+// The largest STRETCH (e > 0: the resampled stream reads its source faster than it writes) the tile and window buffers behind the
+// two resampling stages are sized for: the reference's own bounds (max_ppm = 4000 / 400, FCCH_fine_correction.m:83,
+// SCH_corr_rate_correction.m:94) plus a tenth -- k_stream_tile[_s47] filters TILE + 8 source samples per tile ("the two lerps
+// stretch a tile by < 8": 1024 * 0.00484 + 5 roundings), the window gathers have 40 samples of slack.  With the default thresholds
+// no e gets here; gsmcal_params.fine_max_ppm / sch_max_ppm raised far enough could let one through (hand-given positions), and
+// the stage then answers GSMCAL_E_UNSUPPORTED instead of resampling past those buffers.
+#define GSMCAL_MAX_STRETCH_FINE 4400e-6
+#define GSMCAL_MAX_STRETCH_SCH 440e-6
+
 // FCCH_fine_correction.m:52-137 -- positions, sampling error, new grid, burst windows at level lvl+1
 __device__ void d_fine_decide(StreamState* st, int ov, int lvl, const DevParams& P, int lane) {
     if (st->status < 0 || st->stage_status[0] != 0) { LANE0(st->n_win = 0); return; }
@@ -651,6 +660,7 @@ __device__ void d_fine_decide(StreamState* st, int ov, int lvl, const DevParams&
     const double expected = (double)na * d_ov + (double)nb * d1_ov;            // :111
     const double actual = st->fine_first[last_idx - 1] - st->fine_first[0];
     const double e = (actual - expected) / expected;                           // :113
+    if (e > GSMCAL_MAX_STRETCH_FINE) { LANE0(set_status(st, 0, GSMCAL_E_UNSUPPORTED)); return; }
     const long len_r = level_len(st, lvl);
     const long max_len = e >= 0.0 ? (long)floor((double)len_r / (1.0 + e)) : len_r;   // :118-122
     LANE0(st->sampling_ppm1 = e * 1e6;
@@ -741,6 +751,7 @@ __device__ void d_sch_decide(StreamState* st, int ov, int lvl, const DevParams& 
     const double expected = (double)na * d_ov + (double)nb * d1_ov;
     const double actual = st->sch_first[num_sch - 1] - st->sch_first[0];
     const double e = (actual - expected) / expected;
+    if (e > GSMCAL_MAX_STRETCH_SCH) { LANE0(set_status(st, 1, GSMCAL_E_UNSUPPORTED)); return; }
     const long len_in = level_len(st, lvl);
     long len_r = len_in;
     if (e != 0.0) len_r = e > 0.0 ? (long)floor((double)len_in / (1.0 + e)) : len_in;   // :120
@@ -871,7 +882,12 @@ __device__ void d_scan_accept(const StreamState* st, int s, double* snr_numhit, 
                               double* pos_snr, int* counts, const DevParams& P, int lane) {
     const int n = st->n_coarse;
     double snr = 0.0, num_hit = 0.0;
-    if (n >= P.scan_min_hits) {
+    if (n == 0) {
+        // "nothing found" is FCCH_pos = FCCH_snr = -1: ONE element (:169 length(FCCH_pos)), no gap to refuse (~sum([]) is true).
+        // The reference's 3 never lets it through; scan_min_hits = 1 does: snr = mean(-1), num_hit = 1
+        // (a capture the detector left with an error -- MATLAB would have stopped -- has no hits either and is not one)
+        if (P.scan_min_hits <= 1 && st->status >= 0) { snr = -1.0; num_hit = 1.0; }
+    } else if (n >= P.scan_min_hits) {
         bool fail = false;
         if (lane < n - 1) {
             const double d = st->coarse_pos[lane + 1] - st->coarse_pos[lane];

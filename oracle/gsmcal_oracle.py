@@ -59,6 +59,31 @@ S_POST_NO_POS = 10      # carrier_correct_post_SCH.m:10-13
 S_POST_FEW_BCCH = 11    # carrier_correct_post_SCH.m:15-19
 
 
+# The thresholds of include/gsmcal.h's gsmcal_params that the library lets a caller move, under the same names, with the
+# reference's literals as defaults.  Every function below that decides on one of them takes `params`: None, a mapping or
+# an object whose instance attributes carry these names (a dataclass); anything else -- a ctypes structure keeps its fields out of
+# vars() -- is a TypeError, never a silent fall-back to the defaults.  A field replaces exactly the literal(s) the header cites
+# for it; the geometry fields (window sizes) are not tunable and are refused.
+PARAM_DEFAULTS = {"coarse_th_db": 10.0, "min_hits": 5, "fine_max_ppm": 4000.0, "fine_gate_snr_db": 5.0, "sch_max_ppm": 400.0,
+                  "post_min_bcch": 4, "scan_min_hits": 3, "scan_spacing": 12500.0, "scan_spacing_idle": 12500.0 + 1250.0,
+                  "scan_tol": 50.0}
+
+
+def resolve_params(params):
+    """-> dict with every field of PARAM_DEFAULTS; ValueError for a field that is not a tunable threshold"""
+    p = dict(PARAM_DEFAULTS)
+    if params is None:
+        return p
+    if not hasattr(params, "items") and (hasattr(params, "_fields_") or not hasattr(params, "__dict__")):
+        raise TypeError("params: a mapping or an object with instance attributes, not " + type(params).__name__)
+    items = params.items() if hasattr(params, "items") else vars(params).items()
+    for k, v in items:
+        if k not in p:
+            raise ValueError(f"{k} is not a tunable threshold of gsmcal_params")
+        p[k] = v
+    return p
+
+
 def _exit(info, code):
     if info is not None:
         info["exit"] = code
@@ -229,7 +254,7 @@ def specific_fft_snr_fix_avg(s, target_set, fft_len, th, avg_snr):
 # ------------------------------------------------------------------------------------------------
 # a5  FCCH_coarse_position.m:5-94
 # ------------------------------------------------------------------------------------------------
-def FCCH_coarse_position(s, decimation_ratio, info=None):
+def FCCH_coarse_position(s, decimation_ratio, info=None, params=None):
     """[position, snr] = FCCH_coarse_position(s, decimation_ratio)
 
     Returns (position, snr) as float64 row vectors (1x-symbol units, 1-based), or (-1.0, -1.0)
@@ -241,7 +266,7 @@ def FCCH_coarse_position(s, decimation_ratio, info=None):
     len_FCCH_CW = 148
     fft_len = int(2 ** math.floor(math.log2(len_FCCH_CW / decimation_ratio)))  # :17
     length = len(s)
-    th = 10.0
+    th = resolve_params(params)["coarse_th_db"]  # :21
     mv_len = 10 * fft_len
 
     n_first = int(math.ceil(23 * num_sym_per_frame / decimation_ratio))  # :25
@@ -319,7 +344,7 @@ def _interp1_linear(s, xq):
 # ------------------------------------------------------------------------------------------------
 # a6  FCCH_fine_correction.m:5-197
 # ------------------------------------------------------------------------------------------------
-def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, info=None):
+def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, info=None, params=None):
     """[FCCH_pos, r, sampling_ppm, carrier_ppm] = FCCH_fine_correction(s, base_position, ov, fc)
 
     Sentinels as in the reference: FCCH_pos = -1.0 / r = -1.0 (scalars), ppm = inf.
@@ -330,8 +355,10 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
     sampling_ppm = math.inf
     carrier_ppm = math.inf
     base_position = np.atleast_1d(np.asarray(base_position, dtype=np.float64))
+    P = resolve_params(params)
+    min_hits = P["min_hits"]
     _exit(info, 0)
-    if len(base_position) < 5:  # :12
+    if len(base_position) < min_hits:  # :12
         _exit(info, S_FEW_HITS)
         return FCCH_pos, r, sampling_ppm, carrier_ppm
 
@@ -368,20 +395,22 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
     if info is not None:
         info["first_round_pos"] = FCCH_pos.copy()
 
-    if last_idx >= 5:  # :69
+    if last_idx >= min_hits:  # :69
         r = s
         first_FCCH_pos = FCCH_pos[0]
         diff_seq = np.diff(FCCH_pos)
         num_sym_per_frame = (625.0 / 4.0) * 8
         d_ov = 10 * num_sym_per_frame * oversampling_ratio
         d1_ov = 11 * num_sym_per_frame * oversampling_ratio
-        max_ppm = 4000
+        max_ppm = P["fine_max_ppm"]  # :83
         max_th = math.floor(d_ov * max_ppm * 1e-6)
         max_th1 = math.floor(d1_ov * max_ppm * 1e-6)
         a = diff_seq - d_ov
         a_logical = np.abs(a) < max_th
         b = diff_seq - d1_ov
         b_logical = np.abs(b) < max_th1
+        if info is not None:
+            info["first_round_diff"] = diff_seq.copy()
         if (np.sum(a_logical) + np.sum(b_logical)) != last_idx - 1:  # :95
             _exit(info, S_FINE_SPACING)
             return -1.0, r, sampling_ppm, carrier_ppm
@@ -405,7 +434,7 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
             FCCH_pos = FCCH_pos[:-1]
 
     num_fcch = len(FCCH_pos)
-    if num_fcch >= 5:  # :142
+    if num_fcch >= min_hits:  # :142
         fcch_mat, int_pr, pr, fo = _fcch_tone_estimate(r, FCCH_pos, fft_len, sampling_rate)
         target_freq = symbol_rate / 4
         if info is not None:
@@ -427,18 +456,18 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
         FCCH_snr = 10.0 * np.log10(signal_power / noise_power)
         if info is not None:
             info["fcch_snr"] = FCCH_snr.copy()
-        if np.sum(FCCH_snr < 5) > 0:  # :192
+        if np.sum(FCCH_snr < P["fine_gate_snr_db"]) > 0:  # :192
             _exit(info, S_FINE_LOW_SNR)
             return -1.0, r, sampling_ppm, carrier_ppm
     else:
-        _exit(info, S_FINE_FEW if last_idx < 5 else S_FINE_FEW_BURSTS)
+        _exit(info, S_FINE_FEW if last_idx < min_hits else S_FINE_FEW_BURSTS)
     return FCCH_pos, r, sampling_ppm, carrier_ppm
 
 
 # ------------------------------------------------------------------------------------------------
 # a7  SCH_corr_rate_correction.m:5-181
 # ------------------------------------------------------------------------------------------------
-def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ratio, info=None):
+def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ratio, info=None, params=None):
     """[pos_info, r, sampling_ppm] = SCH_corr_rate_correction(s, FCCH_pos, sch_ts, ov)
 
     pos_info: (R,2) float64 (col 0 = 1-based start sample, col 1 = 0 FCCH / 1 SCH / 2 BCCH);
@@ -447,8 +476,10 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
     pos_info = np.array([[-1.0, -1.0]])
     sampling_ppm = math.inf
     FCCH_pos = np.atleast_1d(np.asarray(FCCH_pos, dtype=np.float64))
+    P = resolve_params(params)
+    min_hits = P["min_hits"]
     _exit(info, 0)
-    if len(FCCH_pos) < 5:  # :11
+    if len(FCCH_pos) < min_hits:  # :11
         _exit(info, S_FEW_HITS)
         return pos_info, r, sampling_ppm
     s = np.asarray(s).ravel()
@@ -493,19 +524,21 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
         info["first_round_sch_pos"] = SCH_pos.copy()
 
     num_sch = len(SCH_pos)
-    if num_sch >= 5:  # :84
+    if num_sch >= min_hits:  # :84
         r = s
         first_SCH_pos = SCH_pos[0]
         diff_seq = np.diff(SCH_pos)
         d_ov = 10 * num_sym_per_frame_ov
         d1_ov = 11 * num_sym_per_frame_ov
-        max_ppm = 400
+        max_ppm = P["sch_max_ppm"]  # :94
         max_th = math.floor(d_ov * max_ppm * 1e-6)
         max_th1 = math.floor(d1_ov * max_ppm * 1e-6)
         a = diff_seq - d_ov
         a_logical = np.abs(a) < max_th
         b = diff_seq - d1_ov
         b_logical = np.abs(b) < max_th1
+        if info is not None:
+            info["first_round_diff"] = diff_seq.copy()
         if (np.sum(a_logical) + np.sum(b_logical)) != num_sch - 1:  # :106
             _exit(info, S_SCH_SPACING)
             return pos_info, r, sampling_ppm
@@ -566,7 +599,7 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
 # ------------------------------------------------------------------------------------------------
 # a8  carrier_correct_post_SCH.m:5-83
 # ------------------------------------------------------------------------------------------------
-def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info=None):
+def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info=None, params=None):
     """[r, carrier_ppm] = carrier_correct_post_SCH(s, pos_info, ov, fc)"""
     r = -1.0
     carrier_ppm = math.inf
@@ -575,7 +608,7 @@ def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info
     if np.all(pos_info == -1):  # :10
         _exit(info, S_POST_NO_POS)
         return r, carrier_ppm
-    if np.sum(pos_info[:, 1] == 2) < 4:  # :15-19
+    if np.sum(pos_info[:, 1] == 2) < resolve_params(params)["post_min_bcch"]:  # :15-19
         _exit(info, S_POST_FEW_BCCH)
         return r, carrier_ppm
     s = np.asarray(s).ravel()
@@ -645,29 +678,37 @@ def total_ppm_calculation(ppm_in):
 # ------------------------------------------------------------------------------------------------
 # driver glue: gsm_sync_demod.m:107-124 (per dongle) and multi_rtl_sdr_gsm_FCCH_scanner.m:132-135,164-185
 # ------------------------------------------------------------------------------------------------
+def front_end(raw, coef):
+    """gsm_sync_demod.m:107,110: filter(coef, 1, raw2iq(raw))"""
+    return matlab_filter(coef, raw2iq(raw))
+
+
 def calibrate_stream(raw, coef, sch_training_sequence, carrier_freq,
-                     oversampling_ratio=8, coarse_decimation=8, keep_r=False):
+                     oversampling_ratio=8, coarse_decimation=8, keep_r=False, params=None, front=None):
     """One dongle of gsm_sync_demod.m:107-124.  raw: uint8-valued interleaved I,Q (2N,).
+    `front`: filter(coef,1,raw2iq(raw)) where the caller already has it (front_end(); it does not depend on `params`).
 
     Returns a dict with every intermediate the parity tests compare."""
     out = {}
-    r = raw2iq(raw)                              # :107
-    r = matlab_filter(coef, r)                   # :110
+    r = front_end(raw, coef) if front is None else front   # :107, :110
     dec = oversampling_ratio * coarse_decimation
     info0 = {}
-    pos_c, snr_c = FCCH_coarse_position(r[0::dec], coarse_decimation, info0)     # :117
+    pos_c, snr_c = FCCH_coarse_position(r[0::dec], coarse_decimation, info0, params)     # :117
     out["coarse_pos"], out["coarse_snr"] = np.atleast_1d(pos_c), np.atleast_1d(snr_c)
     info = {}
-    FCCH_pos, r_c, sp1, cp1 = FCCH_fine_correction(r, pos_c, oversampling_ratio, carrier_freq, info)  # :118
+    FCCH_pos, r_c, sp1, cp1 = FCCH_fine_correction(r, pos_c, oversampling_ratio, carrier_freq, info, params)  # :118
     out["fine_first_round_pos"] = info.get("first_round_pos", np.zeros(0))
     out["fcch_pos"] = np.atleast_1d(np.asarray(FCCH_pos, dtype=np.float64))
+    out["fine_gate_snr"] = info.get("fcch_snr", np.zeros(0))          # :185-191, what the :192 gate looks at
+    out["fine_first_round_diff"] = info.get("first_round_diff", np.zeros(0))
     info2 = {}
-    pos_info, r_c, sp2 = SCH_corr_rate_correction(r_c, FCCH_pos, sch_training_sequence, oversampling_ratio, info2)  # :119
+    pos_info, r_c, sp2 = SCH_corr_rate_correction(r_c, FCCH_pos, sch_training_sequence, oversampling_ratio, info2, params)  # :119
     out["sch_first_round_pos"] = info2.get("first_round_sch_pos", np.zeros(0))
     out["sch_edge_abort"] = bool(info2.get("sch_edge_abort", False))
+    out["sch_first_round_diff"] = info2.get("first_round_diff", np.zeros(0))
     out["pos_info"] = pos_info
     info3 = {}
-    r_c, cp2 = carrier_correct_post_SCH(r_c, pos_info, oversampling_ratio, carrier_freq, info3)  # :120
+    r_c, cp2 = carrier_correct_post_SCH(r_c, pos_info, oversampling_ratio, carrier_freq, info3, params)  # :120
     out["sampling_ppm"] = np.array([sp1, sp2])
     out["carrier_ppm"] = np.array([cp1, cp2])
     out["total_sampling_ppm"] = total_ppm_calculation([sp1, sp2])  # :123
@@ -711,25 +752,28 @@ def sampling_phase_difference(pos_info_1, pos_info_2, oversampling_ratio=8):
     return x, p2[:n, 0] - p1[:n, 0]
 
 
-def scanner_accept(FCCH_pos, FCCH_snr):
-    """Acceptance rule of multi_rtl_sdr_gsm_FCCH_scanner.m:168-185 -> (snr, num_hit)."""
+def scanner_accept(FCCH_pos, FCCH_snr, params=None):
+    """Acceptance rule of multi_rtl_sdr_gsm_FCCH_scanner.m:168-185 -> (snr, num_hit).
+    (The detector's "nothing found" is the scalar -1: one element.  With scan_min_hits = 1 the literal rule accepts it --
+    diff is empty, ~sum([]) is true -- as one hit of snr -1.)"""
+    P = resolve_params(params)
     FCCH_pos = np.atleast_1d(np.asarray(FCCH_pos, dtype=np.float64))
     FCCH_snr = np.atleast_1d(np.asarray(FCCH_snr, dtype=np.float64))
-    if len(FCCH_pos) >= 3:
+    if len(FCCH_pos) >= P["scan_min_hits"]:  # :169
         d = np.diff(FCCH_pos)
-        a = np.abs(d - 12500) > 50
+        a = np.abs(d - P["scan_spacing"]) > P["scan_tol"]  # :170-171
         if not np.sum(a):
             return float(_seq_mean(FCCH_snr)), float(len(FCCH_pos))
-        b = np.abs(d[a] - (12500 + 1250)) > 50
+        b = np.abs(d[a] - P["scan_spacing_idle"]) > P["scan_tol"]  # :176-177
         if not np.sum(b):
             return float(_seq_mean(FCCH_snr)), float(len(FCCH_pos))
     return 0.0, 0.0
 
 
-def scan_capture(raw, coef, oversampling_ratio=8, coarse_decimation=8):
+def scan_capture(raw, coef, oversampling_ratio=8, coarse_decimation=8, params=None, front=None):
     """One capture of the scanner: :132-135 front end + :164 detector + :168-185 acceptance."""
-    r = matlab_filter(coef, raw2iq(raw))
+    r = front_end(raw, coef) if front is None else front
     dec = oversampling_ratio * coarse_decimation
-    pos, snr = FCCH_coarse_position(r[0::dec], coarse_decimation)
-    s, n = scanner_accept(pos, snr)
+    pos, snr = FCCH_coarse_position(r[0::dec], coarse_decimation, None, params)
+    s, n = scanner_accept(pos, snr, params)
     return {"coarse_pos": np.atleast_1d(pos), "coarse_snr": np.atleast_1d(snr), "snr": s, "num_hit": n}

@@ -29,6 +29,28 @@ def note_exit(info, code):
         info["exit"] = code
 
 
+TUNABLE = ("coarse_th_db", "min_hits", "fine_max_ppm", "fine_gate_snr_db", "sch_max_ppm", "post_min_bcch", "scan_min_hits",
+           "scan_spacing", "scan_spacing_idle", "scan_tol")
+
+
+def lit(params, name, literal):
+    """The value the .m file hard-codes as `literal`, unless `params` (None, a mapping or an object whose INSTANCE attributes are
+    named as include/gsmcal.h's gsmcal_params names them -- a dataclass; a ctypes structure has none and is a TypeError) moves it.  Each call site below passes the reference's own literal, so this
+    module shares no table of defaults with the first oracle.  Anything but a tunable threshold in `params` is refused."""
+    if params is None:
+        return literal
+    if hasattr(params, "keys"):
+        given = dict(params)
+    elif hasattr(params, "_fields_") or not hasattr(params, "__dict__"):
+        raise TypeError("params: a mapping or an object with instance attributes, not " + type(params).__name__)
+    else:
+        given = dict(vars(params))
+    for key in given:
+        if key not in TUNABLE:
+            raise ValueError(key + " is not a tunable threshold of gsmcal_params")
+    return given.get(name, literal)
+
+
 def m_round(x):
     """MATLAB round: ties away from zero."""
     return math.floor(x + 0.5) if x >= 0 else -math.floor(-x + 0.5)
@@ -162,7 +184,7 @@ def specific_fft_snr_fix_avg(s, target_set, fft_len, th, avg_snr):
 
 
 # ---- FCCH_coarse_position.m -----------------------------------------------------------------------------------------
-def FCCH_coarse_position(s, decimation_ratio, info=None):
+def FCCH_coarse_position(s, decimation_ratio, info=None, params=None):
     note_exit(info, 0)
     position = -1.0
     snr = -1.0
@@ -172,7 +194,7 @@ def FCCH_coarse_position(s, decimation_ratio, info=None):
     len_FCCH_CW = 148
     fft_len = 2 ** math.floor(math.log2(len_FCCH_CW / decimation_ratio))            # :17
     length = len(s)
-    th = 10
+    th = lit(params, "coarse_th_db", 10)                                            # :21
     mv_len = 10 * fft_len
     n_first = math.ceil(23 * num_sym_per_frame / decimation_ratio)
     if n_first > length:
@@ -276,7 +298,7 @@ def _tone_estimate(r, pos_list, fft_len, sampling_rate):
 
 
 # ---- FCCH_fine_correction.m -----------------------------------------------------------------------------------------
-def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, info=None):
+def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, info=None, params=None):
     note_exit(info, 0)
     s = np.asarray(s, dtype=np.complex128).ravel()
     r = -1.0
@@ -284,7 +306,7 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
     sampling_ppm = math.inf
     carrier_ppm = math.inf
     base_position = np.atleast_1d(np.asarray(base_position, dtype=np.float64))
-    if len(base_position) < 5:                                                      # :12
+    if len(base_position) < lit(params, "min_hits", 5):                             # :12
         note_exit(info, 2)                                                          # GSMCAL_S_FEW_HITS
         return FCCH_pos, r, sampling_ppm, carrier_ppm, []
     symbol_rate = SYMBOL_RATE
@@ -324,14 +346,14 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
         last_idx = i
     FCCH_pos = FCCH_pos[:last_idx]
     first_round = list(FCCH_pos)
-    if last_idx >= 5:
+    if last_idx >= lit(params, "min_hits", 5):                                      # :69
         r = s
         first_FCCH_pos = FCCH_pos[0]
         diff_seq = [FCCH_pos[k + 1] - FCCH_pos[k] for k in range(last_idx - 1)]
         num_sym_per_frame = (625 / 4) * 8
         d_ov = 10 * num_sym_per_frame * oversampling_ratio
         d1_ov = 11 * num_sym_per_frame * oversampling_ratio
-        max_ppm = 4000
+        max_ppm = lit(params, "fine_max_ppm", 4000)                                 # :83
         max_th = math.floor(d_ov * max_ppm * 1e-6)
         max_th1 = math.floor(d1_ov * max_ppm * 1e-6)
         a_logical = [abs(d - d_ov) < max_th for d in diff_seq]
@@ -359,11 +381,11 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
         FCCH_pos = [g + first_FCCH_pos - 1 for g in grid]
         if FCCH_pos[-1] + fft_len - 1 > len(r):                                     # :135
             FCCH_pos = FCCH_pos[:-1]
-            if len(FCCH_pos) < 5:
+            if len(FCCH_pos) < lit(params, "min_hits", 5):
                 note_exit(info, 5)                                                  # GSMCAL_S_FINE_FEW_BURSTS (:142 not taken)
     else:
         note_exit(info, 3)                                                          # GSMCAL_S_FINE_FEW (:69 not taken)
-    if len(FCCH_pos) >= 5:
+    if len(FCCH_pos) >= lit(params, "min_hits", 5):                                 # :142
         fcch_mat, _ipr, pr, fo = _tone_estimate(r, FCCH_pos, fft_len, sampling_rate)
         target_freq = symbol_rate / 4
         mean_fo = 0.0
@@ -382,20 +404,22 @@ def FCCH_fine_correction(s, base_position, oversampling_ratio, carrier_freq, inf
             sp_ = sum(fd[k - 1] for k in sig_idx)
             npow = sum(fd[k - 1] for k in noise_idx)
             snr.append(10 * math.log10(sp_ / npow))
-        if sum(1 for v in snr if v < 5) > 0:                                        # :192
+        if info is not None:
+            info["fcch_snr"] = list(snr)
+        if sum(1 for v in snr if v < lit(params, "fine_gate_snr_db", 5)) > 0:       # :192
             note_exit(info, 6)                                                      # GSMCAL_S_FINE_LOW_SNR
             return -1.0, r, sampling_ppm, carrier_ppm, first_round
     return np.array(FCCH_pos, dtype=np.float64), r, sampling_ppm, carrier_ppm, first_round
 
 
 # ---- SCH_corr_rate_correction.m -------------------------------------------------------------------------------------
-def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ratio, info=None):
+def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ratio, info=None, params=None):
     note_exit(info, 0)
     r = -1.0
     pos_info = np.array([[-1.0, -1.0]])
     sampling_ppm = math.inf
     FCCH_pos = np.atleast_1d(np.asarray(FCCH_pos, dtype=np.float64))
-    if len(FCCH_pos) < 5:                                                           # :11
+    if len(FCCH_pos) < lit(params, "min_hits", 5):                                  # :11
         note_exit(info, 2)                                                          # GSMCAL_S_FEW_HITS
         return pos_info, r, sampling_ppm
     s = np.asarray(s, dtype=np.complex128).ravel()
@@ -435,15 +459,17 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
             note_exit(info, 7)                                                      # GSMCAL_S_SCH_EDGE
             return np.array([[-1.0, -1.0]]), r, sampling_ppm
     num_sch = len(SCH_pos)
-    if num_sch < 5:
+    if info is not None:
+        info["first_round_sch_pos"] = list(SCH_pos)
+    if num_sch < lit(params, "min_hits", 5):
         note_exit(info, 8)                                                          # GSMCAL_S_SCH_FEW (:84 not taken)
-    if num_sch >= 5:
+    if num_sch >= lit(params, "min_hits", 5):                                       # :84
         r = s
         first_SCH_pos = SCH_pos[0]
         diff_seq = [SCH_pos[k + 1] - SCH_pos[k] for k in range(num_sch - 1)]
         d_ov = 10 * num_sym_per_frame_ov
         d1_ov = 11 * num_sym_per_frame_ov
-        max_ppm = 400
+        max_ppm = lit(params, "sch_max_ppm", 400)                                   # :94
         max_th = math.floor(d_ov * max_ppm * 1e-6)
         max_th1 = math.floor(d1_ov * max_ppm * 1e-6)
         a_logical = [abs(d - d_ov) < max_th for d in diff_seq]
@@ -514,7 +540,7 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
 
 
 # ---- carrier_correct_post_SCH.m -------------------------------------------------------------------------------------
-def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info=None):
+def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info=None, params=None):
     note_exit(info, 0)
     r = -1.0
     carrier_ppm = math.inf
@@ -522,7 +548,7 @@ def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, info
     if all(v == -1 for v in pos_info.ravel()):                                      # :10
         note_exit(info, 10)                                                         # GSMCAL_S_POST_NO_POS
         return r, carrier_ppm
-    if sum(1 for v in pos_info[:, 1] if v == 2) < 4:                                # :15
+    if sum(1 for v in pos_info[:, 1] if v == 2) < lit(params, "post_min_bcch", 4):  # :15
         note_exit(info, 11)                                                         # GSMCAL_S_POST_FEW_BCCH
         return r, carrier_ppm
     s = np.asarray(s, dtype=np.complex128).ravel()
@@ -554,16 +580,58 @@ def total_ppm_calculation(ppm_in):
 
 
 # ---- gsm_sync_demod.m:107-124, one dongle ---------------------------------------------------------------------------
-def calibrate_stream(raw, coef, sch_training_sequence, carrier_freq, oversampling_ratio=8, coarse_decimation=8):
+def front_end(raw, coef):
+    """gsm_sync_demod.m:107,110: filter(coef, 1, raw2iq(raw))"""
+    return filter_fir(coef, raw2iq(np.asarray(raw, dtype=np.float64))[:, 0])
+
+
+# ---- multi_rtl_sdr_gsm_FCCH_scanner.m:168-185 -----------------------------------------------------------------------
+def scanner_accept(FCCH_pos, FCCH_snr, params=None):
+    """-> (snr(i), num_hit(i)) of one capture: both stay at the zeros of :160-161 unless the rule accepts"""
+    FCCH_pos = [float(v) for v in np.atleast_1d(FCCH_pos)]                          # (the -1 of "nothing found" is 1 x 1)
+    FCCH_snr = [float(v) for v in np.atleast_1d(FCCH_snr)]
+    snr = 0.0
+    num_hit = 0.0
+    diff_FCCH_pos = [FCCH_pos[k + 1] - FCCH_pos[k] for k in range(len(FCCH_pos) - 1)]       # :168
+    if len(FCCH_pos) >= lit(params, "scan_min_hits", 3):                            # :169
+        a = [abs(d - lit(params, "scan_spacing", 12500)) for d in diff_FCCH_pos]    # :170
+        a = [v > lit(params, "scan_tol", 50) for v in a]                            # :171
+        accept = False
+        if not sum(a):                                                              # :172
+            accept = True
+        else:
+            b = [abs(d - lit(params, "scan_spacing_idle", 12500 + 1250)) for d, f in zip(diff_FCCH_pos, a) if f]   # :176
+            b = [v > lit(params, "scan_tol", 50) for v in b]                        # :177
+            if not sum(b):                                                          # :178
+                accept = True
+        if accept:
+            total = 0.0
+            for v in FCCH_snr:                                                      # :173 / :179 mean(FCCH_snr)
+                total += v
+            snr = total / len(FCCH_snr)
+            num_hit = float(len(FCCH_pos))
+    return snr, num_hit
+
+
+def scan_capture(raw, coef, oversampling_ratio=8, coarse_decimation=8, params=None, front=None):
+    """:132-135 front end, :164 detector, :168-185 acceptance of one capture"""
+    r = front_end(raw, coef) if front is None else front
+    pos, snr = FCCH_coarse_position(r[0::oversampling_ratio * coarse_decimation], coarse_decimation, None, params)
+    s, n = scanner_accept(pos, snr, params)
+    return {"coarse_pos": np.atleast_1d(pos), "coarse_snr": np.atleast_1d(snr), "snr": s, "num_hit": n}
+
+
+def calibrate_stream(raw, coef, sch_training_sequence, carrier_freq, oversampling_ratio=8, coarse_decimation=8, params=None,
+                     front=None):
     """The per-dongle body of the driver, and what the calibration table's columns 6..9 say about it (include/gsmcal.h
     GSMCAL_T_*): status = the first exit met along coarse -> fine -> SCH -> post, n_fcch = length(FCCH_pos) (1 for the -1
     sentinel), n_pos_rows = size(pos_info, 1), first_fcch_pos = pos_info(1, 1)."""
     i0, i1, i2, i3 = {}, {}, {}, {}
-    r = filter_fir(coef, raw2iq(np.asarray(raw, dtype=np.float64))[:, 0])           # :107, :110
-    pos, snr = FCCH_coarse_position(r[0::oversampling_ratio * coarse_decimation], coarse_decimation, i0)   # :117
-    fp, r1, sp1, cp1, first = FCCH_fine_correction(r, pos, oversampling_ratio, carrier_freq, i1)            # :118
-    pi, r2, sp2 = SCH_corr_rate_correction(r1, fp, sch_training_sequence, oversampling_ratio, i2)           # :119
-    r3, cp2 = carrier_correct_post_SCH(r2, pi, oversampling_ratio, carrier_freq, i3)                        # :120
+    r = front_end(raw, coef) if front is None else front                            # :107, :110
+    pos, snr = FCCH_coarse_position(r[0::oversampling_ratio * coarse_decimation], coarse_decimation, i0, params)   # :117
+    fp, r1, sp1, cp1, first = FCCH_fine_correction(r, pos, oversampling_ratio, carrier_freq, i1, params)            # :118
+    pi, r2, sp2 = SCH_corr_rate_correction(r1, fp, sch_training_sequence, oversampling_ratio, i2, params)           # :119
+    r3, cp2 = carrier_correct_post_SCH(r2, pi, oversampling_ratio, carrier_freq, i3, params)                        # :120
     stage_exit = [i0["exit"], i1["exit"], i2["exit"], i3["exit"]]
     status = 0
     for code in stage_exit:
@@ -575,4 +643,5 @@ def calibrate_stream(raw, coef, sch_training_sequence, carrier_freq, oversamplin
             "fcch_pos": fcch_pos, "pos_info": pi, "sp": [sp1, sp2], "cp": [cp1, cp2],
             "tot": [total_ppm_calculation([sp1, sp2]), total_ppm_calculation([cp1, cp2])], "r": r3,
             "stage_exit": stage_exit, "status": status, "n_fcch": len(fcch_pos), "n_pos_rows": int(pi.shape[0]),
-            "first_fcch_pos": float(pi[0, 0])}
+            "first_fcch_pos": float(pi[0, 0]), "fine_gate_snr": np.asarray(i1.get("fcch_snr", []), dtype=np.float64),
+            "sch_first": np.asarray(i2.get("first_round_sch_pos", []), dtype=np.float64)}

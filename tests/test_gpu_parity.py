@@ -1216,7 +1216,8 @@ def test_fine_search_against_rocfft_spectra(g, setup):
 
 def test_params_pod_changes_decisions_and_rejects_geometry(g, setup):
     """gsmcal_params: the thresholds the reference hard-codes.  An impossible SNR gate turns every calibrated stream into
-    the :192-196 sentinel; a relaxed scanner rule accepts two-hit captures; geometry fields are refused."""
+    the :192-196 sentinel and the default brings the first table back; a geometry field is refused.  (Every threshold moved
+    against the oracle, the scanner's rule and the rest of set_params' contract: tests/test_gpu_params.py.)"""
     raw = np.stack([g.synth.make_stream(dongle=d)[0] for d in (0, 3)])
     c2 = g.Context(0)
     try:
