@@ -149,6 +149,9 @@ const char* gsmcal_last_error(gsmcal_ctx* ctx);
 long gsmcal_last_call_report(gsmcal_ctx* ctx, char* buf, size_t cap);
 long gsmcal_num2str(const double* x, int n, char* buf, size_t cap);
 const char* gsmcal_version(void);
+/* Bytes of LDS the coarse scan keeps for itself in front of its len + mv_len + 128 window SNRs (the size of the per-stream state
+ * is in it): what bounds len + mv_len in the three coarse-detector entry points below. */
+long gsmcal_coarse_scan_lds_fixed(void);
 /* Pipelined batch calls (round 6).  gsm_sync_demod.m:107-124 is a serial chain per batch of dongles; a service that calibrates batch
  * after batch does not need batch i finished before batch i+1 starts.  With depth D > 1, up to D consecutive
  * gsmcal_calibrate_batch_dev calls that run on one lane (up to 127 streams) are in flight at once: call i runs on internal HIP
@@ -222,12 +225,26 @@ int gsmcal_chn_filter_8x_4x(gsmcal_ctx* ctx, const double* s, long n, int d,
  * reference loads from gsm_chn_filter_4x.mat (:8-9); NULL/0 = the built-in 30 taps of gsm_chn_filter_4x.fda. */
 int gsmcal_chn_filter_4x(gsmcal_ctx* ctx, const double* s, long n, int d, const double* num, int ntaps, double* r);
 /* r = filter(coef, 1, s) column-wise (gsm_sync_demod.m:110, multi_rtl_sdr_gsm_FCCH_scanner.m:133);
- * keep every `decim`-th row starting with row 1 (decim = 1: all rows; the drivers' r(1:64:end,i)). */
+ * keep every `decim`-th row starting with row 1 (decim = 1: all rows; the drivers' r(1:64:end,i)).
+ * Any ntaps >= 1, decim >= 1, n >= 1 (n below ntaps or decim included): r has ceil(n/decim) rows; nothing is staged, so there is
+ * no upper limit on decim. */
 int gsmcal_filter(gsmcal_ctx* ctx, const double* coef, int ntaps, const double* s, long n, int d,
                   int decim, double* r);
 
 /* [hit_flag,hit_idx,hit_avg_snr,hit_snr] = move_fft_snr_runtime_avg(s,mv_len,fft_len,th)
- *                                                                    move_fft_snr_runtime_avg.m:5-50 */
+ *                                                                    move_fft_snr_runtime_avg.m:5-50
+ * Supported geometry of the three coarse-detector entry points (tests/test_gpu_geometry.py pins it):
+ *   fft_len 2 .. 64 (16: the radix-2 kernels; any other length: direct DFTs); fft_len < 2 is GSMCAL_E_ARG, fft_len > 64
+ *   GSMCAL_E_UNSUPPORTED.  At fft_len = 2 the reference's three "signal" bins count the other bin twice, the SNR is NaN and
+ *   nothing hits; at fft_len = 3 all bins are signal bins and noise_power is a rounding residue (0 or an ulp either side): the
+ *   call returns cleanly, which windows hit is not defined by the reference.
+ *   mv_len >= 1, len >= 1 (fewer than fft_len samples: no window, no hit).  The scan keeps len + mv_len + 128 SNRs in LDS
+ *   behind gsmcal_coarse_scan_lds_fixed() = 12 368 bytes of its own, 159 KiB in all: up to len + mv_len = 18 678
+ *   (GSMCAL_E_UNSUPPORTED beyond).
+ *   gsmcal_FCCH_coarse_position derives fft_len = 2^floor(log2(148/decimation_ratio)) itself: decimation_ratio 2 .. 74 is
+ *   served (fft_len 64 .. 2; 5, 6, 7 and 8 give the 16-point kernels), 1 (128-point windows) and 75 and above (windows of one
+ *   sample) are GSMCAL_E_UNSUPPORTED.  Fewer than ceil(28750/decimation_ratio) samples: GSMCAL_E_INDEX (s(1:n_first), :25).
+ * GSMCAL_E_UNSUPPORTED is decided on the host before anything is uploaded; no output has been written. */
 int gsmcal_move_fft_snr_runtime_avg(gsmcal_ctx* ctx, const double* s, long len, int mv_len, int fft_len,
                                     double th, int* hit_flag, double* hit_idx, double* hit_avg_snr,
                                     double* hit_snr);
@@ -244,7 +261,12 @@ int gsmcal_FCCH_coarse_position(gsmcal_ctx* ctx, const double* s, long len, int 
 /* [FCCH_pos,r,sampling_ppm,carrier_ppm] = FCCH_fine_correction(s,base_position,ov,carrier_freq)
  *                                                                    FCCH_fine_correction.m:5-197
  * r: capacity cap_r complex samples; *len_r = samples written (sentinel r = -1: *len_r = -1 and
- * nothing written).  r may be NULL (cap_r = 0) when only positions/ppm are wanted. */
+ * nothing written).  r may be NULL (cap_r = 0) when only positions/ppm are wanted.
+ * oversampling_ratio (this function, gsmcal_SCH_corr_rate_correction and gsmcal_carrier_correct_post_SCH share one range):
+ * 1 (148-point spectra, two 64-shift chunks) to 30, odd ratios included; held to the oracle at 1, 2, 3, 4, 5, 6, 8, 12, 16 and
+ * 30.  The burst kernels keep two 148*ov-sample buffers, the window's samples and their tables in LDS; from 31 on that
+ * passes 159 KiB (the chunk sweep follows at 34): GSMCAL_E_UNSUPPORTED, decided on the host before anything is uploaded or
+ * launched, nothing written.  (Behind it, 128 and above would pass the 255 chunks of 64 shifts a work item can name.) */
 int gsmcal_FCCH_fine_correction(gsmcal_ctx* ctx, const double* s, long len, const double* base_position,
                                 int num_base, int oversampling_ratio, double carrier_freq,
                                 double* fcch_pos, int cap_pos, int* num_pos,
@@ -273,7 +295,9 @@ int gsmcal_carrier_correct_post_SCH(gsmcal_ctx* ctx, const double* s, long len, 
  * burst x_eq = ifft(fft(x) ./ (fft(x_training) ./ fft(training))).  The Viterbi GMSK demodulator that follows in the
  * reference (Communications Toolbox, output discarded) is not part of this library.
  * x_eq: cap_bursts x len_fde_ov complex, burst-major; *num_bursts SCH bursts written, *len_fde_ov their length.
- * pos_info all -1 (:8-11): returns GSMCAL_S_POST_NO_POS with *num_bursts = 0. */
+ * pos_info all -1 (:8-11): returns GSMCAL_S_POST_NO_POS with *num_bursts = 0.
+ * oversampling_ratio 1 .. 12: a burst's three 194*ov-point buffers and the 97 x (2*ov + 1) matrix of its transform live in
+ * LDS; 13 and above pass 159 KiB: GSMCAL_E_UNSUPPORTED, nothing written. */
 int gsmcal_SCH_equalise(gsmcal_ctx* ctx, const double* s, long len, const double* pos_info, int rows, int ld,
                         const double* sch_training_sequence, int len_ts, int oversampling_ratio,
                         double* x_eq, int cap_bursts, int* num_bursts, int* len_fde_ov);
@@ -288,7 +312,9 @@ int gsmcal_SCH_equalise(gsmcal_ctx* ctx, const double* s, long len, const double
  * snr: where noise_power < 0 (peak outside the band) MATLAB's log10 yields a complex number: NaN here; noise_power == 0: +Inf.
  * pos_info all -1 (:8-11): returns GSMCAL_S_POST_NO_POS with *num_fcch = 0.  More than GSMCAL_MAX_HITS type-0 rows (or than
  * `cap`): GSMCAL_E_CAPACITY.  A window that leaves the stream: GSMCAL_E_INDEX, decided before a sample is read.
- * gsmcal_last_call_report then returns the lines the .m file prints (:6,9,43,45,49,65,66). */
+ * gsmcal_last_call_report then returns the lines the .m file prints (:6,9,43,45,49,65,66).
+ * oversampling_ratio 1 .. 33 (tested at 1, 2, 3, 4, 8 and 16): the window and its 37 x (4*ov + 1) transform matrix live in LDS
+ * and pass 159 KiB at 34, GSMCAL_E_UNSUPPORTED from there on. */
 int gsmcal_FCCH_demod(gsmcal_ctx* ctx, const double* s, long len, const double* pos_info, int rows, int ld,
                       int oversampling_ratio, double carrier_freq, double* freq, double* snr, double* max_idx, int cap,
                       int* num_fcch, double* mean_freq, double* carrier_ppm);
@@ -301,7 +327,10 @@ int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out);
 
 /* Front end of both drivers for D captures at once: raw2iq + filter(coef,1,.) + r(1:decim:end)
  * (gsm_sync_demod.m:107,110,117; multi_rtl_sdr_gsm_FCCH_scanner.m:132-135).
- * raw: D x 2N bytes (capture-major: capture d starts at raw + d*2N). out: D x ceil(N/decim) complex. */
+ * raw: D x 2N bytes (capture-major: capture d starts at raw + d*2N). out: D x ceil(N/decim) complex.
+ * Any N >= 1 (N below ntaps or decim included; 2N need not be a multiple of 16: captures may start anywhere), ntaps >= 1.
+ * decim: a workgroup stages the 256*decim + ntaps raw samples of its 256 outputs in LDS -- 1 .. 282 for one tap, 281 for 47,
+ * 277 for 300 taps; beyond that GSMCAL_E_UNSUPPORTED with nothing written (gsmcal_filter on raw2iq's output has no limit). */
 int gsmcal_frontend_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, const double* coef,
                           int ntaps, int decim, double* out);
 int gsmcal_frontend_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, const double* coef,

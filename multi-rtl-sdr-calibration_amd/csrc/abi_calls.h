@@ -401,6 +401,18 @@ int gsmcal_chn_filter_4x(gsmcal_ctx* c, const double* s, long n, int d, const do
 // ---- a3..a5 coarse detector -----------------------------------------------------------------------
 static int coarse_api(gsmcal_ctx* c, const double* s, long len, CoarseArgs a, StreamState* out) {
     ENTER(c);
+    int fft_len = a.fft_len;
+    long n_first = len;
+    if (a.mode == 0) {
+        // (above 74 the windows would be shorter than two samples -- refused below; above 148 the exponent would be negative)
+        fft_len = a.decimation_ratio > 74 ? 0 : 1 << (int)floor(log2(148.0 / (double)a.decimation_ratio));
+        n_first = (long)ceil(23.0 * 1250.0 / (double)a.decimation_ratio);
+    }
+    if (fft_len < 2 || fft_len > 64) return GSMCAL_E_UNSUPPORTED;
+    const long nwin = n_first - (fft_len - 1);
+    const size_t lds = coarse_scan_lds(n_first > 0 ? n_first : 0, a.mode == 0 ? 10 * fft_len : a.mv_len);
+    if (lds > 159 * 1024) return GSMCAL_E_UNSUPPORTED;
+    // (the refusals above are decided before anything is uploaded)
     RET_IF(upload_array(c, s, (size_t)len));
     std::vector<StreamState> v(1);
     host_init_state(v[0], len);
@@ -408,16 +420,6 @@ static int coarse_api(gsmcal_ctx* c, const double* s, long len, CoarseArgs a, St
     c->last_S = 1; c->cur = &c->lanes[0]; c->lanes[0].lo = 0; c->lanes[0].n = 1; c->n_lanes_used = 1;
     a.s = (const cplx*)c->arr_in.p; a.s_stride = len; a.len = len;
     a.th0 = c->params.coarse_th_db; a.min_hits = c->params.min_hits;
-    int fft_len = a.fft_len;
-    long n_first = len;
-    if (a.mode == 0) {
-        fft_len = 1 << (int)floor(log2(148.0 / (double)a.decimation_ratio));
-        n_first = (long)ceil(23.0 * 1250.0 / (double)a.decimation_ratio);
-    }
-    if (fft_len < 2 || fft_len > 64) return GSMCAL_E_UNSUPPORTED;
-    const long nwin = n_first - (fft_len - 1);
-    const size_t lds = coarse_scan_lds(n_first > 0 ? n_first : 0, a.mode == 0 ? 10 * fft_len : a.mv_len);
-    if (lds > 159 * 1024) return GSMCAL_E_UNSUPPORTED;
     if (a.mode != 2 && nwin >= 1 && n_first <= len) {
         RET_IF(ensure(c, c->cur->snrbuf, (size_t)nwin * sizeof(double)));
         a.snr_g = (double*)c->cur->snrbuf.p; a.snr_stride = nwin;
@@ -493,6 +495,7 @@ int gsmcal_FCCH_fine_correction(gsmcal_ctx* c, const double* s, long len, const 
     if (!c || !s || !base_position || !fcch_pos || !num_pos || len < 1 || num_base < 0 || ov < 1 || cap_pos < 1)
         return GSMCAL_E_ARG;
     if (num_base > MAXH) return GSMCAL_E_CAPACITY;
+    RET_IF(api_chain_check(ov, 0));
     ENTER(c);
     const Geom g(ov);
     RET_IF(upload_array(c, s, (size_t)len));
@@ -542,6 +545,7 @@ int gsmcal_SCH_corr_rate_correction(gsmcal_ctx* c, const double* s, long len, co
     if (!c || !fcch_pos || !sch_ts || !pos_info || !num_rows || num_fcch < 0 || len_ts < 1 || ov < 1 || cap_rows < 1)
         return GSMCAL_E_ARG;
     if (num_fcch > MAXH) return GSMCAL_E_CAPACITY;
+    RET_IF(api_chain_check(ov, len_ts));
     ENTER(c);
     const Geom g(ov);
     const bool have_s = s != nullptr && len >= 1;   // r = -1 from a failed fine stage arrives as s = NULL
@@ -597,6 +601,7 @@ int gsmcal_SCH_corr_rate_correction(gsmcal_ctx* c, const double* s, long len, co
 int gsmcal_carrier_correct_post_SCH(gsmcal_ctx* c, const double* s, long len, const double* pos_info, int rows, int ld,
                                     int ov, double carrier_freq, double* r, long cap_r, long* len_r, double* carrier_ppm) {
     if (!c || !pos_info || rows < 1 || ld < rows || ov < 1) return GSMCAL_E_ARG;
+    RET_IF(api_chain_check(ov, 0));
     ENTER(c);
     const Geom g(ov);
     bool all_m1 = true;                       // `if pos_info == -1` is true only if every element is -1

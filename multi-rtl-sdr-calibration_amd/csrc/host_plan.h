@@ -508,6 +508,30 @@ int post_chain_blocks_per_cu(gsmcal_ctx* c, int variant, size_t lds) {
     return nb;
 }
 
+// The largest dynamic LDS any launch of the per-function stages (run_fine / run_sch / run_post on a level-0 source) asks for at
+// this geometry, on whichever search path the context takes.  The API entry points refuse a ratio whose launches would not fit
+// before anything is uploaded or enqueued (the certificate kernel is not in the list: where it does not fit, k_fine_openall runs).
+size_t api_chain_lds(const Source& src, const Geom& g, int len_ts) {
+    size_t m = fk_lds_bytes(g.nfft);                                                                                  // k_fine_chunk
+    m = std::max(m, ((size_t)g.fine_wlen * sizeof(cplx) + FV_MAX_ITEMS * (sizeof(int) + sizeof(cplx)) + 15) & ~(size_t)15);   // k_fine_verify
+    m = std::max(m, fft_lds(g));                                                                                       // k_fft_burst<1>
+    m = std::max(m, (size_t)(g.fine_nshift - 1 + FS_CHUNK) * sizeof(cplx));                                            // k_fine_search
+    m = std::max(m, gather_lds(g.fine_wlen, 0, src.kind, src.ntaps));                                                  // k_gather
+    m = std::max(m, fused_lds(src, 1, g.nfft, burst_scratch(g)));                                                      // k_burst_tone<1, ..>
+    m = std::max(m, fused_lds(src, 0, g.nfft, burst_scratch(g)));                                                      // k_burst_tone<0, ..>
+    if (len_ts > 0) {                                                                                                  // k_window_sch
+        const size_t scratch = (size_t)(len_ts + g.sch_nshift * SCH_PARTS) * sizeof(cplx) + (size_t)g.sch_nshift * sizeof(double);
+        m = std::max(m, fused_lds(src, 0, g.sch_nshift - 1 + len_ts, scratch));
+    }
+    return m;
+}
+// GSMCAL_E_UNSUPPORTED for an oversampling ratio the per-function stages cannot serve (array sources), 0 otherwise
+int api_chain_check(int ov, int len_ts) {
+    if (ov > 127) return GSMCAL_E_UNSUPPORTED;                        // more than 255 chunks of 64 shifts (run_fine)
+    const Source probe{SRC_ARR, nullptr, 0, nullptr, 0, nullptr, 0};
+    return api_chain_lds(probe, Geom(ov), len_ts) > 159 * 1024 ? GSMCAL_E_UNSUPPORTED : 0;
+}
+
 // ---- FCCH_fine_correction body (input at level lvl; creates levels lvl+1 (lerp), lvl+2 (mix)) ----
 // setup_done: the window setup already ran at the end of k_coarse_scan (batch path).
 // next_sch_lvl >= 0: also run SCH_corr_rate_correction's window setup in the last decision launch.
