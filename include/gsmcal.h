@@ -367,6 +367,42 @@ int gsmcal_subband_power_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long 
 int gsmcal_subband_power_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, const double* coef, int ntaps,
                                    int decim, const double* phase_rotate, int nsub, double* d_power);
 
+/* CW sample-loss check (CW_check.m:6-8; check_CW_samples_loss_tcp.m:70,89-90 without the plots).  Per capture
+ *   s = raw2iq(bytes);  q_n = s(n+1)./s(n), n = 1..N-1;  phase_rotate = angle(mean(q));  r_n = angle(q_n) - phase_rotate
+ * with MATLAB's scaled complex division and r NOT wrapped (the reference does not wrap it: values lie in (-2pi, 2pi)).  A lost
+ * run of k samples shows as ONE spike of k*phase_rotate mod 2pi at the ratio behind which the samples are missing; a loss with
+ * k*phase_rotate mod 2pi below thr is invisible, so the CW offset is the operator's to choose.
+ * raw: D x 2N bytes, capture-major.  summary: [D][GSMCAL_CW_COLS] doubles, row =
+ *   [0] phase_rotate   [1] count of n with |r_n| > thr (strictly; it goes on past the capacity of the list)   [2] max |r_n|
+ *   [3] 1-based n of the first maximum (MATLAB's max)   [4] status
+ *   [5..] GSMCAL_CW_MAX_EVENTS pairs (1-based n, r_n) of the first exceeds in index order, NaN in unused slots.
+ * r: NULL (summary only) or D rows of r_stride >= N-1 doubles, N-1 written per row, the padding left alone.
+ * status GSMCAL_CW_OK; GSMCAL_CW_SHORT: N < 2, no ratio exists -- columns 0, 2, 3 and the events NaN, count 0, r untouched;
+ * GSMCAL_CW_ZERO: some s(n), n <= N-1, is exactly 0+0i (a sample equal to the capture's mean, or a constant capture).  The
+ * reference then computes with Inf and NaN and what comes out depends on the platform's complex division; that is NOT
+ * reproduced: columns 0, 2, 3 and the events are NaN, the count is 0 and every r_n of that capture is NaN.
+ * A phase_rotate of exactly +-pi sits on atan2's branch cut and r is then defined modulo 2pi only; a byte capture of N = 2 always
+ * is such a case (raw2iq makes s(2) = -s(1), the one ratio is -1).
+ * thr must be finite and > 0, d >= 1, n >= 1, no NULL raw / summary: anything else GSMCAL_E_ARG with a message, decided before
+ * anything is enqueued.  No atomics and a tiling that depends on N only (GSMCAL_CW_TILE ratios per workgroup): a capture's row
+ * and residuals are bit-identical at any position in a batch of any size, with or without r.  Workspaces of their own:
+ * gsmcal_last_batch_details / _snr and gsmcal_last_call_report keep answering for the call before.  _dev: enqueues on the
+ * context's stream only; d_summary and d_r may be device or pinned host memory.
+ * gsmcal_CW_check is the MATLAB signature r = CW_check(s) on a complex array (len >= 2; r: len-1 doubles; *phase_rotate too
+ * unless NULL): the same kernels behind another load stage, so CW_check(raw2iq(bytes)) equals the batch r bit for bit.  A zero
+ * sample among s(1..len-1) gives NaN in every r_n and in *phase_rotate, as above. */
+#define GSMCAL_CW_MAX_EVENTS 16
+#define GSMCAL_CW_COLS (5 + 2 * GSMCAL_CW_MAX_EVENTS)     /* 37 doubles per stream */
+#define GSMCAL_CW_TILE 2048
+#define GSMCAL_CW_OK 0
+#define GSMCAL_CW_SHORT 1
+#define GSMCAL_CW_ZERO 2
+int gsmcal_CW_check(gsmcal_ctx* ctx, const double* s, long len, double* r, double* phase_rotate);
+int gsmcal_cw_check_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, double thr, double* summary, double* r,
+                          long r_stride);
+int gsmcal_cw_check_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, double thr, double* d_summary,
+                              double* d_r, long r_stride);
+
 /* Scanner detect loop for D captures (multi_rtl_sdr_gsm_FCCH_scanner.m:132-135 front end,
  * :164 FCCH_coarse_position, :168-185 acceptance).  Outputs per capture: snr, num_hit (as the
  * driver's arrays), optional positions/snrs [D][GSMCAL_MAX_HITS] and counts [D] (NULL to skip). */

@@ -7,8 +7,8 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan gsmcal_band_power \
- *            gsmcal_subband_power; do
+ *            carrier_correct_post_SCH FCCH_demod CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
+ *            gsmcal_band_power gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
  *
@@ -266,6 +266,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (k = 0; k < (mwSize)nb; ++k) REAL_PTR(plhs[i])[k] = v[i * GSMCAL_MAX_HITS + k];
     }
     if (nlhs > 3) plhs[3] = scalar(cp);
+
+#elif defined(GSMCAL_FN_CW_check)
+    /* r = CW_check(s)     CW_check.m:6-8: s a complex vector of N >= 2 samples (raw2iq's output, check_CW_samples_loss_tcp.m:70,
+     * 89-90), r an (N-1) x 1 real column, not wrapped.  [r, phase_rotate] = CW_check(s) also hands back the mean phase step. */
+    mwSize n = 0;
+    const double* s;
+    double pr;
+    if (nrhs < 1 || mxGetNumberOfElements(prhs[0]) < 2) mexErrMsgIdAndTxt("gsmcal:args", "usage: r = CW_check(s) with at least two samples");
+    s = cplx_in(prhs[0], &n);
+    plhs[0] = mxCreateDoubleMatrix(n - 1, 1, mxREAL);
+    chk(gsmcal_CW_check(ctx(), s, (long)n, REAL_PTR(plhs[0]), &pr), "CW_check");
+    if (nlhs > 1) plhs[1] = scalar(pr);
 
 #elif defined(GSMCAL_FN_total_ppm_calculation)
     /* ppm_out = total_ppm_calculation(ppm_in) */

@@ -17,6 +17,10 @@ MAX_HITS = 24
 MAX_POS_ROWS = 6 * MAX_HITS
 TABLE_COLS = 10
 MAX_SUBBANDS = 16
+CW_MAX_EVENTS = 16
+CW_COLS = 5 + 2 * CW_MAX_EVENTS    # one row of cw_check_batch: phase_rotate, count, max |r|, n of the maximum, status, (n, r_n) pairs
+CW_TILE = 2048                     # ratios per workgroup of the CW check (GSMCAL_CW_TILE)
+CW_OK, CW_SHORT, CW_ZERO = 0, 1, 2
 DEMOD_COLS = 4 + 3 * MAX_HITS      # one row of fcch_demod_batch: num_fcch, mean_freq, carrier_ppm, status, freq[], snr[], max_idx[]
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
@@ -78,6 +82,10 @@ SIGNATURES = {
                                              c_double_p, C.c_int, c_double_p]),
     "gsmcal_subband_power_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                                  c_double_p, C.c_int, C.c_void_p]),
+    "gsmcal_CW_check": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_double_p, c_double_p]),
+    "gsmcal_cw_check_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, C.c_double, c_double_p, c_double_p, C.c_long]),
+    "gsmcal_cw_check_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_void_p, C.c_void_p,
+                                            C.c_long]),
     "gsmcal_fcch_scan_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_int_p]),
     "gsmcal_fcch_scan_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int,

@@ -28,7 +28,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import DEMOD_COLS, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -508,6 +508,58 @@ def subband_power_batch_dev(d_raw, d, n, coef, phase_rotate, d_power, decim=1, c
     coef, w = _subband_args(coef, phase_rotate, int(d))
     ctx.check(ctx.lib.gsmcal_subband_power_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), _dp(coef), len(coef), int(decim),
                                                      _dp(w), w.shape[1], C.c_void_p(d_power)), "subband_power_batch_dev")
+
+
+CW_FIELDS = ("phase_rotate", "count", "max_abs", "max_n", "status")   # columns 0..4 of a CW-check row; then the (n, r_n) pairs
+
+
+def cw_rows(table):
+    """(D, CW_COLS) summary of cw_check_batch[_dev] -> one dict per capture: the CW_FIELDS (count, max_n and status as ints,
+    max_n None where it is NaN) and "events", the listed (1-based n, r_n) pairs of the first exceeds."""
+    rows = []
+    for t in np.asarray(table, dtype=np.float64).reshape(-1, CW_COLS):
+        ev = t[5:].reshape(CW_MAX_EVENTS, 2)
+        ev = ev[~np.isnan(ev[:, 0])]
+        rows.append({"phase_rotate": float(t[0]), "count": int(t[1]), "max_abs": float(t[2]),
+                     "max_n": None if np.isnan(t[3]) else int(t[3]), "status": int(t[4]),
+                     "events": [(int(n), float(v)) for n, v in ev]})
+    return rows
+
+
+def CW_check(s, ctx=None):
+    """r = CW_check(s) -- CW_check.m:6-8: angle(s(2:end)./s(1:end-1)) minus the angle of the mean ratio, not wrapped.  s: complex
+    (N,), N >= 2 -> (N-1,) doubles.  A sample among s(1..N-1) that is exactly 0 gives NaN everywhere (include/gsmcal.h)."""
+    ctx = ctx or default_context()
+    buf, n, _ = _cplx_in(np.asarray(s).ravel())
+    r = np.empty(max(n - 1, 0))
+    ctx.check(ctx.lib.gsmcal_CW_check(ctx.h, _dp(buf), n, _dp(r), None), "CW_check")
+    return r
+
+
+def cw_check_batch(raw, thr, want_r=False, ctx=None):
+    """raw: (D, 2N) uint8 -> the (D, CW_COLS) summary of the CW sample-loss check (cw_rows names its columns): phase_rotate, the
+    count of |r_n| > thr, max |r_n| and where, a status, the first CW_MAX_EVENTS exceeds.  want_r: returns (summary, r) with r
+    (D, N-1), the residuals CW_check(raw2iq(.)) of every capture."""
+    ctx = ctx or default_context()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    if raw.ndim != 2 or raw.shape[1] % 2:
+        raise ValueError("raw must be (D, 2N) bytes")
+    d, two_n = raw.shape
+    n = two_n // 2
+    out = np.empty((d, CW_COLS))
+    r = np.empty((d, max(n - 1, 0))) if want_r else None
+    ctx.check(ctx.lib.gsmcal_cw_check_batch(ctx.h, raw.ctypes.data_as(_lib.c_u8_p), d, n, float(thr), _dp(out),
+                                            _dp(r) if want_r else None, max(n - 1, 0)), "cw_check_batch")
+    return (out, r) if want_r else out
+
+
+def cw_check_batch_dev(d_raw, d, n, thr, d_summary, d_r=None, r_stride=0, ctx=None):
+    """Device-pointer form of cw_check_batch: only enqueues on the context's stream (ctx.sync() before reading).  d_raw: [d][2n]
+    bytes; d_summary: [d][CW_COLS] doubles; d_r: None (summary only) or d rows of r_stride >= n-1 doubles (n-1 written per row);
+    device or pinned host memory."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.gsmcal_cw_check_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), float(thr), C.c_void_p(d_summary),
+                                                C.c_void_p(d_r) if d_r else None, int(r_stride)), "cw_check_batch_dev")
 
 
 DEMOD_FIELDS = ("num_fcch", "mean_freq", "carrier_ppm", "status")      # columns 0..3 of a demod row; then freq | snr | max_idx

@@ -151,7 +151,8 @@ void gsmcal_ctx_destroy(gsmcal_ctx* c) {
     DevBuf* bufs[] = {&c->coef, &c->ts, &c->cf, &c->table, &c->snrhit, &c->arr_in, &c->arr_out, &c->posinfo, &c->rlen,
                       &c->misc, &c->tw, &c->csum_head, &c->tw_sch, &c->bp_coef, &c->bp_state, &c->bp_part, &c->bp_raw,
                       &c->bp_out, &c->fd_tw, &c->fd_cf, &c->fd_part, &c->fd_in, &c->fd_len, &c->fd_pos, &c->fd_out,
-                      &c->sb_taps, &c->sb_idx, &c->sb_state, &c->sb_part, &c->sb_raw, &c->sb_out};
+                      &c->sb_taps, &c->sb_idx, &c->sb_state, &c->sb_part, &c->sb_raw, &c->sb_out,
+                      &c->cw_state, &c->cw_part, &c->cw_rec, &c->cw_mean, &c->cw_raw, &c->cw_in, &c->cw_out, &c->cw_r};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < MAX_LANES; ++i) {
@@ -999,6 +1000,126 @@ int gsmcal_subband_power_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n,
     RET_IF(gsmcal_subband_power_batch_dev(c, (const uint8_t*)c->sb_raw.p, d, n, coef, ntaps, decim, phase_rotate, nsub, (double*)c->sb_out.p));
     HIPCHK(c, hipMemcpyAsync(power, c->sb_out.p, nout, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- CW sample-loss check: CW_check.m:6-8 (check_CW_samples_loss_tcp.m:70,89-90) ------------------------------------------------
+// Passes (kernels_cwcheck.h): k_band_power_clear + k_dc_sum (exact byte sums), k_cw_ratio_sum, k_cw_finish_mean, k_cw_residual,
+// k_cw_finish_summary.  The first pass's bytes are read again by the second: plain loads there, non-temporal ones in the second.
+// `arr` != nullptr: one complex array instead of raw bytes (gsmcal_CW_check) -- the same kernels behind another load stage.
+static const auto k_cw_ratio_sum_raw = &k_cw_ratio_sum<true>;
+static const auto k_cw_ratio_sum_arr = &k_cw_ratio_sum<false>;
+static const auto k_cw_residual_raw = &k_cw_residual<true, true>;
+static const auto k_cw_residual_arr = &k_cw_residual<false, false>;
+static const auto k_cw_finish_summary_raw = &k_cw_finish_summary<true>;
+static const auto k_cw_finish_summary_arr = &k_cw_finish_summary<false>;
+static_assert(CW_TILE == GSMCAL_CW_TILE && CW_MAX_EVENTS == GSMCAL_CW_MAX_EVENTS && CW_COLS == GSMCAL_CW_COLS && CW_ST_SHORT == GSMCAL_CW_SHORT &&
+              CW_ST_ZERO == GSMCAL_CW_ZERO, "kernels_cwcheck.h and include/gsmcal.h disagree");
+
+static int cw_enqueue(gsmcal_ctx* c, const uint8_t* d_raw, const cplx* arr, int d, long n, double thr, double* d_summary, double* d_r,
+                      long r_stride) {
+    c->cur = &c->lanes[0];                              // the context's stream; the lane's buffers are not touched
+    const long nblk = n >= 2 ? (n - 1 + CW_TILE - 1) / CW_TILE : 0;
+    if (nblk > (1L << 30)) return GSMCAL_E_ARG;
+    RET_IF(ensure(c, c->cw_state, (size_t)d * sizeof(StreamState)));
+    RET_IF(ensure(c, c->cw_part, (size_t)d * std::max(nblk, 1L) * sizeof(CwPart)));
+    RET_IF(ensure(c, c->cw_rec, (size_t)d * std::max(nblk, 1L) * sizeof(CwRec)));
+    RET_IF(ensure(c, c->cw_mean, (size_t)d * sizeof(CwMean)));
+    StreamState* st = (StreamState*)c->cw_state.p;
+    CwPart* part = (CwPart*)c->cw_part.p;
+    CwRec* rec = (CwRec*)c->cw_rec.p;
+    CwMean* mean = (CwMean*)c->cw_mean.p;
+    const long chunk = 65535;                           // (the grid's y limit)
+    if (nblk > 0) {
+        if (!arr) LAUNCH(c, k_band_power_clear, dim3((d + 255) / 256), dim3(256), 0, st, d);
+        for (long lo = 0; lo < d; lo += chunk) {
+            const int S = (int)std::min(chunk, (long)d - lo);
+            const dim3 grid((unsigned)nblk, S);
+            if (arr) {
+                LAUNCH(c, k_cw_ratio_sum_arr, grid, dim3(256), 0, (const uint8_t*)nullptr, 0L, (const StreamState*)st, arr, n, n, part);
+            } else {
+                const uint8_t* raw = d_raw + (size_t)lo * 2 * n;
+                int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));       // dc_means()'s geometry
+                blocks = std::max(1, std::min(blocks, std::max(1, 4096 / S)));
+                LAUNCH(c, k_dc_sum, dim3(blocks, S), dim3(256), 0, raw, 2 * n, st + lo);
+                LAUNCH(c, k_cw_ratio_sum_raw, grid, dim3(256), 0, raw, 2 * n, (const StreamState*)(st + lo), (const cplx*)nullptr, 0L, n,
+                       part + lo * nblk);
+            }
+        }
+        LAUNCH(c, k_cw_finish_mean, dim3((d + 63) / 64), dim3(64), 0, (const CwPart*)part, (int)nblk, d, n, mean);
+        for (long lo = 0; lo < d; lo += chunk) {
+            const int S = (int)std::min(chunk, (long)d - lo);
+            const dim3 grid((unsigned)nblk, S);
+            double* r_lo = d_r ? d_r + (size_t)lo * r_stride : nullptr;
+            if (arr)
+                LAUNCH(c, k_cw_residual_arr, grid, dim3(256), 0, (const uint8_t*)nullptr, 0L, (const StreamState*)st, arr, n, n,
+                       (const CwMean*)mean, thr, r_lo, r_stride, rec);
+            else
+                LAUNCH(c, k_cw_residual_raw, grid, dim3(256), 0, d_raw + (size_t)lo * 2 * n, 2 * n, (const StreamState*)(st + lo),
+                       (const cplx*)nullptr, 0L, n, (const CwMean*)(mean + lo), thr, r_lo, r_stride, rec + lo * nblk);
+        }
+    }
+    if (arr)
+        LAUNCH(c, k_cw_finish_summary_arr, dim3(d), dim3(256), 0, (const uint8_t*)nullptr, 0L, (const StreamState*)st, arr, n, n,
+               (const CwMean*)mean, (const CwRec*)rec, (int)nblk, thr, d_summary);
+    else
+        LAUNCH(c, k_cw_finish_summary_raw, dim3(d), dim3(256), 0, d_raw, 2 * n, (const StreamState*)st, (const cplx*)nullptr, 0L, n,
+               (const CwMean*)mean, (const CwRec*)rec, (int)nblk, thr, d_summary);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+static int cw_args_ok(gsmcal_ctx* c, const void* raw, int d, long n, double thr, const void* summary, const void* r, long r_stride) {
+    if (!c) return GSMCAL_E_ARG;
+    const char* why = nullptr;
+    if (!raw || !summary) why = "cw_check: raw and summary must not be NULL";
+    else if (d < 1) why = "cw_check: d must be at least 1";
+    else if (n < 1 || n > (1L << 40)) why = "cw_check: n must be 1 .. 2^40";
+    else if (!(thr > 0.0) || std::isinf(thr)) why = "cw_check: thr must be finite and > 0";
+    else if (r && r_stride < n - 1) why = "cw_check: r_stride is below n - 1";
+    if (why) { c->err = why; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+int gsmcal_cw_check_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n, double thr, double* d_summary, double* d_r,
+                              long r_stride) {
+    RET_IF(cw_args_ok(c, d_raw, d, n, thr, d_summary, d_r, r_stride));
+    ENTER(c);
+    return cw_enqueue(c, d_raw, nullptr, d, n, thr, d_summary, d_r, r_stride);
+}
+
+int gsmcal_cw_check_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, double thr, double* summary, double* r, long r_stride) {
+    RET_IF(cw_args_ok(c, raw, d, n, thr, summary, r, r_stride));
+    ENTER(c);
+    const size_t nsum = (size_t)d * GSMCAL_CW_COLS * sizeof(double);
+    RET_IF(ensure(c, c->cw_raw, (size_t)2 * n * d));
+    RET_IF(ensure(c, c->cw_out, nsum));
+    if (r && n >= 2) RET_IF(ensure(c, c->cw_r, (size_t)d * (n - 1) * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(c->cw_raw.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
+    RET_IF(cw_enqueue(c, (const uint8_t*)c->cw_raw.p, nullptr, d, n, thr, (double*)c->cw_out.p, r && n >= 2 ? (double*)c->cw_r.p : nullptr, n - 1));
+    HIPCHK(c, hipMemcpyAsync(summary, c->cw_out.p, nsum, hipMemcpyDeviceToHost, c->stream));
+    if (r && n >= 2)                                    // the device rows are packed; the caller's padding is not written
+        HIPCHK(c, hipMemcpy2DAsync(r, (size_t)r_stride * sizeof(double), c->cw_r.p, (size_t)(n - 1) * sizeof(double),
+                                   (size_t)(n - 1) * sizeof(double), (size_t)d, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int gsmcal_CW_check(gsmcal_ctx* c, const double* s, long len, double* r, double* phase_rotate) {
+    if (!c) return GSMCAL_E_ARG;
+    if (!s || !r || len < 2 || len > (1L << 36)) { c->err = "CW_check: s and r must not be NULL and len must be 2 .. 2^36"; return GSMCAL_E_ARG; }
+    ENTER(c);
+    RET_IF(ensure(c, c->cw_in, (size_t)len * sizeof(cplx)));
+    RET_IF(ensure(c, c->cw_out, (size_t)GSMCAL_CW_COLS * sizeof(double)));
+    RET_IF(ensure(c, c->cw_r, (size_t)(len - 1) * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(c->cw_in.p, s, (size_t)len * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
+    // (no threshold in the MATLAB signature: one nothing exceeds, so no block is evaluated again for the event list)
+    RET_IF(cw_enqueue(c, nullptr, (const cplx*)c->cw_in.p, 1, len, 1e300, (double*)c->cw_out.p, (double*)c->cw_r.p, len - 1));
+    double row[GSMCAL_CW_COLS];
+    HIPCHK(c, hipMemcpyAsync(row, c->cw_out.p, sizeof(row), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r, c->cw_r.p, (size_t)(len - 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (phase_rotate) *phase_rotate = row[0];
     return 0;
 }
 

@@ -156,6 +156,9 @@ struct gsmcal_ctx {
     DevBuf sb_taps, sb_idx, sb_state, sb_part, sb_raw, sb_out;
     std::vector<double> h_sb_coef, h_sb_w, h_sb_rows;
     std::vector<int> h_sb_idx;
+    // CW sample-loss check (gsmcal_CW_check, gsmcal_cw_check_batch*): workspaces of its own again.  cw_state: the byte sums;
+    // cw_part / cw_rec: one record per (capture, tile) of the two passes; cw_mean: phase_rotate and status per capture
+    DevBuf cw_state, cw_part, cw_rec, cw_mean, cw_raw, cw_in, cw_out, cw_r;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream
     static constexpr int AG_SLOTS = 4;

@@ -173,3 +173,27 @@ class Ring:
         if getattr(self, "h", None):
             self.ctx.lib.gsmcal_ring_destroy(self.h)
             self.h = None
+
+
+def check_sample_loss(ring, slot, d, n, thr, ctx=None):
+    """check_CW_samples_loss_tcp.m:56-70,89-90 without the plots, on a ring slot that has been submitted: the CW sample-loss
+    check of the slot's d captures of n samples each (dongle-major bytes, as capture_all fills them) on the device copy,
+    returned as api.cw_rows -- one dict per dongle with the count of |r| > thr and the first events.  The slot is acquired and
+    released here; the call returns when the rows are on the host."""
+    from . import api
+    ctx = ctx or ring.ctx
+    if 2 * int(n) * int(d) > ring.bytes:
+        raise ValueError("the slot holds fewer than d captures of n samples")
+    out = np.empty((int(d), api.CW_COLS))
+    d_out = C.c_void_p()
+    ctx.check(ctx.lib.gsmcal_dev_alloc(ctx.h, out.nbytes, C.byref(d_out)), "gsmcal_dev_alloc")
+    try:
+        d_raw = ring.acquire(slot)
+        try:
+            api.cw_check_batch_dev(d_raw, d, n, thr, d_out.value, ctx=ctx)
+            ctx.check(ctx.lib.gsmcal_memcpy_d2h(ctx.h, out.ctypes.data_as(C.c_void_p), d_out, out.nbytes), "gsmcal_memcpy_d2h")
+        finally:
+            ring.release(slot)
+    finally:
+        ctx.lib.gsmcal_dev_free(ctx.h, d_out)
+    return api.cw_rows(out)

@@ -216,6 +216,26 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     return raw, truth
 
 
+def make_cw(n, step=0.7, amp=100.0, dc=(127.4, 127.6), noise=0.5, drops=(), seed=DEFAULT_SEED):
+    """A CW capture as check_CW_samples_loss_tcp.m records one from a signal generator: the tone amp*exp(1i*(step*t + phi)) plus
+    white Gaussian noise (standard deviation `noise` per component) plus DC, rounded and clipped to bytes; returns the 2n
+    interleaved uint8 I,Q bytes.  drops = [(pos, k), ...] removes k samples of the source after output index pos (0-based), so
+    CW_check's spike of k*step (mod 2 pi) lands at n = pos + 1 (1-based)."""
+    rng = np.random.Generator(np.random.Philox(key=[int(seed), 0x4357 ^ int(n)]))
+    gap = np.zeros(n, dtype=np.int64)
+    for pos, k in drops:
+        if not 0 <= pos < n - 1:
+            raise ValueError("a drop must lie between two output samples")
+        gap[pos + 1] += int(k)
+    t = np.arange(n, dtype=np.float64) + np.cumsum(gap)
+    y = amp * np.exp(1j * (step * t + rng.uniform(0, 2 * math.pi)))
+    y = y + noise * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    raw = np.empty(2 * n, dtype=np.float64)
+    raw[0::2] = y.real + dc[0]
+    raw[1::2] = y.imag + dc[1]
+    return np.clip(np.floor(raw + 0.5), 0, 255).astype(np.uint8)
+
+
 # ------------------------------------------------------------------------------------------------
 # Host twin of the device-side capture expansion (csrc/kernels_frontend.h: k_synth_expand).
 # ------------------------------------------------------------------------------------------------
