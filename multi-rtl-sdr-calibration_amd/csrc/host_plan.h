@@ -66,6 +66,7 @@ struct gsmcal_ctx {
     bool graph_always = false;      // GSMCAL_GRAPH=2: also single-stream plans (default: only plans that fork onto internal streams)
     bool prescreen = true;          // GSMCAL_PRESCREEN=0: run the fp64 fine search on every bin
     int n_cu = 256;                 // compute units of the device (persistent-grid sizing)
+    size_t lds_per_cu = 160 * 1024; // LDS bytes of one compute unit (lean_tail_lds)
     int snr_inline_min = 1;         // GSMCAL_SNR_INLINE_MIN: streams per lane from which k_coarse_scan computes the window SNRs itself when the full table is not built (0: never)
     int snr_inline_keep = 0;        // GSMCAL_SNR_INLINE_KEEP=1: ... and still writes the table out (gsmcal_last_batch_snr)
     int front_nt = -1;              // GSMCAL_FRONT_NT: non-temporal raw loads in k_front_fast (-1: by the size of the call, see front_fused())
@@ -335,6 +336,18 @@ GatherArgs gather_args(const Source& src, int level, int len) {
 // LDS of a fused gather + estimator kernel: the gather carve followed by `scratch` bytes
 size_t fused_lds(const Source& src, int level, int len, size_t scratch, bool compact_xs = false) {
     return (gather_carve(len, level, src.kind, src.ntaps, true, compact_xs).total + scratch + 15) & ~(size_t)15;
+}
+
+// Dynamic LDS of a reference-geometry per-window kernel of the four-launch tail (k_burst_tone<G, 8, 47>, k_window_sch<8, 512, 47>):
+// the workgroup's copy of its stream's state in front of the fused carve, the burst kernels with the compact input staging.
+// 0: three such workgroups do not fit one CU (or one does not fit a launch) -- the caller launches the generic instantiation,
+// which keeps the state in global memory and gather_core.  LEAN_TAIL_STATIC_LDS stands for the kernels' static LDS (the
+// reduction and plan words of the bodies and of stream_tail: 432 B in the burst kernels, 192 B in k_window_sch --
+// tools/resource_usage.sh) and the allocation granule, so that "three per CU" holds for what a workgroup really takes.
+#define LEAN_TAIL_STATIC_LDS 1536
+size_t lean_tail_lds(const gsmcal_ctx* c, const Source& src, int level, int len, size_t scratch, bool compact_xs) {
+    const size_t lds = fused_lds(src, level, len, scratch, compact_xs) + PCR_STATE_BYTES;
+    return (lds <= 159 * 1024 && 3 * (lds + LEAN_TAIL_STATIC_LDS) <= c->lds_per_cu) ? lds : 0;
 }
 
 int launch_gather(gsmcal_ctx* c, int S, const Source& src, int level, int len, bool tiles, int nwin_grid,
@@ -716,7 +729,8 @@ int run_fine(gsmcal_ctx* c, int S, const Source& src, int lvl, const Geom& g, in
         TailArgs tl;   // FCCH_fine_correction's carrier decision (+ the SCH stage's window setup) rides on the last burst
         RET_IF(make_tail(c, S, sa, next_sch_lvl >= 0 ? (STEP_CARRIER_DECIDE | STEP_SCH_SETUP) : STEP_CARRIER_DECIDE, lvl,
                          next_sch_lvl >= 0 ? next_sch_lvl : 0, tl));
-        LAUNCH_GEOM(g.ov == 8 && src.kind == SRC_RAW && src.ntaps == 47 && lvl == 0, c, (k_burst_tone<1, 8, 47>), (k_burst_tone<1, 0, 0>), dim3(H, S), dim3(BT_THREADS), fused_lds(src, lvl + 1, g.nfft, burst_scratch(g)), st, ga,
+        const size_t lean = (g.ov == 8 && src.kind == SRC_RAW && src.ntaps == 47 && lvl == 0) ? lean_tail_lds(c, src, lvl + 1, g.nfft, burst_scratch(g), true) : 0;
+        LAUNCH_GEOM(lean > 0, c, (k_burst_tone<1, 8, 47>), (k_burst_tone<1, 0, 0>), dim3(H, S), dim3(BT_THREADS), lean > 0 ? lean : fused_lds(src, lvl + 1, g.nfft, burst_scratch(g)), st, ga,
                g.nfft, (const cplx*)c->tw.p, g.ov, 1, tl);
     }
     CHECK_LAUNCH(c);
@@ -738,7 +752,8 @@ int run_sch(gsmcal_ctx* c, int S, const Source& src, int lvl, const Geom& g, int
         TailArgs tl;   // SCH_corr_rate_correction's decisions (+ the post stage's window setup) ride on the last window
         RET_IF(make_tail(c, S, sa, next_post_lvl >= 0 ? (STEP_SCH_DECIDE | STEP_POST_SETUP) : STEP_SCH_DECIDE, lvl,
                          next_post_lvl >= 0 ? next_post_lvl : 0, tl));
-        LAUNCH_GEOM(g.ov == 8 && len_ts == 512 && src.kind == SRC_RAW && src.ntaps == 47 && lvl == 2, c, (k_window_sch<8, 512, 47>), (k_window_sch<0, 0, 0>), dim3(H, S), dim3(512), fused_lds(src, lvl, wl, scratch), st, ga, (const cplx*)c->ts.p,
+        const size_t lean = (g.ov == 8 && len_ts == 512 && src.kind == SRC_RAW && src.ntaps == 47 && lvl == 2) ? lean_tail_lds(c, src, lvl, wl, scratch, false) : 0;
+        LAUNCH_GEOM(lean > 0, c, (k_window_sch<8, 512, 47>), (k_window_sch<0, 0, 0>), dim3(H, S), dim3(512), lean > 0 ? lean : fused_lds(src, lvl, wl, scratch), st, ga, (const cplx*)c->ts.p,
                len_ts, g.sch_nshift, tl);
     }
     CHECK_LAUNCH(c);
@@ -765,7 +780,8 @@ int run_post(gsmcal_ctx* c, int S, const Source& src, int lvl, const Geom& g, in
         }
         TailArgs tl;   // carrier_correct_post_SCH's decision (+ the calibration table row) rides on the last burst
         RET_IF(make_tail(c, S, sa, table ? (STEP_POST_DECIDE | STEP_TOTALS) : STEP_POST_DECIDE, lvl, 0, tl));
-        LAUNCH_GEOM(g.ov == 8 && src.kind == SRC_RAW && src.ntaps == 47 && lvl == 3, c, (k_burst_tone<0, 8, 47>), (k_burst_tone<0, 0, 0>), dim3(H, S), dim3(BT_THREADS), fused_lds(src, lvl, g.nfft, burst_scratch(g)), st, ga,
+        const size_t lean = (g.ov == 8 && src.kind == SRC_RAW && src.ntaps == 47 && lvl == 3) ? lean_tail_lds(c, src, lvl, g.nfft, burst_scratch(g), true) : 0;
+        LAUNCH_GEOM(lean > 0, c, (k_burst_tone<0, 8, 47>), (k_burst_tone<0, 0, 0>), dim3(H, S), dim3(BT_THREADS), lean > 0 ? lean : fused_lds(src, lvl, g.nfft, burst_scratch(g)), st, ga,
                g.nfft, (const cplx*)c->tw.p, g.ov, 0, tl);
     }
     CHECK_LAUNCH(c);

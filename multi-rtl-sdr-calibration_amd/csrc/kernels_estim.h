@@ -69,6 +69,7 @@ __device__ __forceinline__ PeakOut merge_peaks_coherent(const PeakOut* p, int NB
 // first): none 66.4 us, LLEE 64.8, LELE 64.4, LEEL 67.8, EELL 64.9, ELEL 66.2, ELLL 62.7, ELLE 62.0 -- the one used.
 #define PCR_PRIO(P0, P1, P2) { const unsigned rnd_ = (blockIdx.y * gridDim.x + blockIdx.x) >> 8; if (rnd_ == 0) __builtin_amdgcn_s_setprio(P0); else if (rnd_ == 1) __builtin_amdgcn_s_setprio(P1); else __builtin_amdgcn_s_setprio(P2); }
 #define BT_THREADS 512
+#define PCR_STATE_BYTES ((sizeof(StreamState) + 15) & ~(size_t)15)   /* a workgroup's LDS copy of its stream's state (k_post_chain_r, k_burst_tone, k_window_sch) */
 
 // ------------------------------------------------------------------------------------------------
 // burst_gather_fast: gather_core for the case k_post_chain_r's burst stages nearly always see -- the stream's state is
@@ -203,12 +204,139 @@ __device__ __forceinline__ int burst_gather_fast(const StreamState* __restrict__
     if (tid + 2 * NT < nfft) buf1[tid + 2 * NT] = tw2;
     return 1;
 }
+
+// ------------------------------------------------------------------------------------------------
+// sch_gather_fast: gather_core for the SCH search window of the reference chain -- raw source, level 2 = LERP | MIX, the
+// stream's state in this workgroup's LDS copy.  Same arithmetic per sample as gather_core (same expressions in the same
+// order: identical bits), in three barrier-separated phases where gather_core has seven:
+//   1. every wave works the plan out itself from LDS (gather_core's backward range propagation, the n0 - 1 clamp
+//      included).  The lanes of the first waves fetch one 16-byte-aligned raw chunk each (eight samples, zero outside
+//      [0, n0)) straight into registers, issued before anything that can wait; the waves WITHOUT a chunk meanwhile build
+//      the MIX rotator table S | A[] | B[] (where gather_core stages the raw bytes: free here) and stage the taps; the
+//      chunk lanes then convert their registers into the padded FIR input (raw2iq.m:6-8);
+//   2. filter(coef,1,.) -> buf0: gather_core's loop (fir4_lds, every accumulator oldest tap first);
+//   3. one pass that interpolates level 1 from buf0 and applies (T[0]*A[i>>5])*B[i&31] as it goes -> region 1.
+// gather_core's shortcut for level 0 -- a copy from a fine-search window (a.l0) that holds all of [lo0, hi0] -- is
+// deliberately not taken: run_sch hands no such buffer over (the SCH windows lie a frame behind the fine windows), and
+// where one is given the raw bytes are filtered all the same: the same taps in the same order, the same bits.
+// Returns 1: window in region 1 (smem + off_region1), NO trailing barrier; 0: not this case (the caller falls back to
+// gather_core); -1: this workgroup has no window.  All three block-uniform.
+// ------------------------------------------------------------------------------------------------
+template <int NT, int FIR_UNR = 1>
+__device__ __forceinline__ int sch_gather_fast(const StreamState* __restrict__ st, const GatherArgs& a, unsigned char* smem,
+                                               int widx, int s) {
+    const int tid = threadIdx.x;
+    const int L = a.len;
+    if (a.src_kind != SRC_RAW || a.tiles || a.level != 2 || a.ntaps != 47 || a.pad != 0 || L > 32 * GC_ROT_A) return 0;
+    if (widx >= MAXH) return -1;
+    typedef const __attribute__((address_space(3))) StreamState* LdsState;
+    LdsState sl = (LdsState)st;
+    const int v_nwin = sl->n_win, v_t1 = sl->op[1].type, v_t2 = sl->op[2].type;
+    const double v_f1 = sl->op[1].param, v_c2 = sl->op[2].param, v_mr = sl->mean_re, v_mi = sl->mean_im;
+    const long v_ws = sl->win_start[widx], v_n0 = sl->n0;
+    if (widx >= uni_i(v_nwin)) return -1;
+    if (uni_i(v_t1) != OP_LERP || uni_i(v_t2) != OP_MIX) return 0;
+    const double f1 = uni_d(v_f1), c2 = uni_d(v_c2);
+    const long n0 = uni_l(v_n0);
+    const long lo1 = uni_l(v_ws), hi1 = lo1 + L - 1;             // levels 2 and 1 (a MIX keeps the range)
+    const long lo0 = (long)floor((double)lo1 * f1);
+    long hi0 = (long)floor((double)hi1 * f1) + 1;
+    hi0 = hi0 > n0 - 1 ? n0 - 1 : hi0;
+    if (hi0 < lo0 || hi0 - lo0 + 1 > (long)L + 8) return 0;      // (the staged span has to fit the carve; a LERP factor far from 1 goes the generic way)
+    const int cnt0 = (int)(hi0 - lo0 + 1);
+    const GatherCarve gc = gather_carve(L, 2, SRC_RAW, a.ntaps, true, false);
+    cplx* buf0 = (cplx*)smem;
+    cplx* buf1 = (cplx*)(smem + gc.off_region1);
+    cplx* xs = buf1;                                             // the padded FIR input, dead before level 2 is written there
+    double* c_s = (double*)(smem + gc.off_coef);
+    cplx* T = (cplx*)(smem + gc.off_rot);
+    // ---- phase 1 ----
+    const unsigned short* base = (const unsigned short*)(a.raw + (size_t)s * a.raw_stride);
+    const int ntp = a.ntaps;
+    const long first = lo0 - (ntp - 1);
+    const int span = cnt0 + ntp - 1;
+    const long ao = (long)(((uintptr_t)base >> 1) & 7);          // stage_raw's alignment: sample first_al sits on a 16-byte boundary
+    long m = (first + ao) % 8;
+    if (m < 0) m += 8;
+    const long first_al = first - m;
+    const int nchunk = (int)((m + span + 8 + 7) >> 3);           // chunks that cover staged entries 0 .. span+7 (<= (7 + L+8+46 + 15) / 8 < NT)
+    const int nwc = (nchunk + 63) >> 6;                          // waves that hold a chunk
+    if (nchunk > NT - 128) return 0;                             // (one chunk per lane, and two waves left for the table and the taps)
+    if (tid < 64 * nwc) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        const long g0 = first_al + 8L * tid;
+        if (tid < nchunk) {
+            if (g0 >= 0 && g0 + 8 <= n0) {
+                v = *(const uint4*)(base + g0);
+            } else {
+                unsigned short t[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) t[i] = (g0 + i >= 0 && g0 + i < n0) ? base[g0 + i] : (unsigned short)0;
+                v.x = t[0] | ((unsigned)t[1] << 16); v.y = t[2] | ((unsigned)t[3] << 16);
+                v.z = t[4] | ((unsigned)t[5] << 16); v.w = t[6] | ((unsigned)t[7] << 16);
+            }
+            // raw2iq.m:6-8 from the registers: staged entry i = 8*tid - m + u is sample g0 + u; (I - mean) + 1i (Q - mean), zero
+            // before the stream starts (filter()'s zero initial state), past its end, and in entries span .. span+7
+            const double mr = uni_d(v_mr), mi = uni_d(v_mi);
+            const int i_base = 8 * tid - (int)m;
+            const unsigned wv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i_base + u;
+                const long g = g0 + u;
+                const unsigned q = (wv[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
+                cplx x = make_double2(0.0, 0.0);
+                if (i < span && g >= 0 && g < n0) x = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
+                if (i >= 0 && i < span + 8) xs[xs_pad(i)] = x;
+            }
+        }
+    } else {
+        const int t = tid - 64 * nwc, nh = NT - 64 * nwc;
+        const int na = (L + 31) >> 5;
+        if (t >= 64) fir_stage_taps(c_s, a.coef, ntp, t - 64, nh - 64);
+        else {
+            for (int i = t; i < 1 + na + 32; i += 64) {
+                const double arg = i == 0 ? (double)lo1 * c2 : (i <= na ? (double)(32 * (i - 1)) * c2 : (double)(i - 1 - na) * c2);
+                double sn, cs;
+                sincos_large(arg, &sn, &cs);
+                T[i == 0 ? 0 : (i <= na ? i : 1 + GC_ROT_A + (i - 1 - na))] = make_double2(cs, sn);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase 2: filter(coef,1,.), four consecutive outputs per lane ----
+    for (int i0 = 4 * tid; i0 < cnt0; i0 += 4 * NT) {
+        cplx y0, y1, y2, y3;
+        fir4_lds<0, true, FIR_UNR>(xs, c_s, i0, ntp, &y0, &y1, &y2, &y3);
+        buf0[i0] = y0;
+        if (i0 + 1 < cnt0) buf0[i0 + 1] = y1;
+        if (i0 + 2 < cnt0) buf0[i0 + 2] = y2;
+        if (i0 + 3 < cnt0) buf0[i0 + 3] = y3;
+    }
+    __syncthreads();
+    // ---- phase 3: level 1 (interp1) and level 2 (the derotation from the table) in one pass ----
+    for (int i = tid; i < L; i += NT) {
+        const long k = lo1 + i;
+        const double xq = lerp_pos((double)k, f1);               // interp_seq = (0:max_len-1)'.*(1+e)
+        const long i0 = (long)floor(xq);
+        const long i1 = i0 + 1 > hi0 ? hi0 : i0 + 1;             // beyond the last sample the weight is 0
+        const double t = xq - (double)i0;
+        const cplx v0 = buf0[i0 - lo0], v1 = buf0[i1 - lo0];
+        const cplx l1 = make_double2(v0.x + t * (v1.x - v0.x), v0.y + t * (v1.y - v0.y));
+        buf1[i] = cmul(l1, cmul(cmul(T[0], T[1 + (i >> 5)]), T[1 + GC_ROT_A + (i & 31)]));
+    }
+    return 1;
+}
 #define BT_STAMP(i) DEV_STAMP(GATE ? KID_BT1 : KID_BT0, blockIdx.y * gridDim.x + blockIdx.x, i)
-template <int GATE, int FIR_UNR = 1>
+// LEAN (k_burst_tone of the reference geometry): sts + blockIdx.y is this workgroup's LDS copy of the state, as for
+// state_in_lds, so burst_gather_fast serves the window; the results go to the global state st_out + blockIdx.y (the
+// stream's last arriver reads them there) and the issue priorities stay as they are (state_in_lds = false).
+template <int GATE, int FIR_UNR = 1, bool LEAN = false>
 __device__ __forceinline__ void burst_tone_body(StreamState* __restrict__ sts, const GatherArgs& a, int nfft,
                                                 const cplx* __restrict__ tw_g, int ov, int prior_mode,
                                                 unsigned char* smem, double* res = nullptr,    // res: {fo, snr} instead of the stores into the state
-                                                bool state_in_lds = false) {                   // sts + blockIdx.y is this workgroup's LDS copy
+                                                bool state_in_lds = false,                     // k_post_chain_r: sts + blockIdx.y is this workgroup's LDS copy
+                                                StreamState* __restrict__ st_out = nullptr) {  // LEAN: the global state
     __shared__ double red_p[BT_THREADS / 64];
     __shared__ int red_t[BT_THREADS / 64];
     __shared__ double red[2 * (BT_THREADS / 64)];
@@ -216,7 +344,7 @@ __device__ __forceinline__ void burst_tone_body(StreamState* __restrict__ sts, c
     __shared__ int sh_key;
     const int s = blockIdx.y, w = blockIdx.x, tid = threadIdx.x;
     BT_STAMP(0);
-    const int fast = state_in_lds ? burst_gather_fast<BT_THREADS, GATE ? KID_BT1 : KID_BT0>(sts + s, a, smem, w, s, tw_g, nfft) : 0;
+    const int fast = (LEAN || state_in_lds) ? burst_gather_fast<BT_THREADS, GATE ? KID_BT1 : KID_BT0>(sts + s, a, smem, w, s, tw_g, nfft) : 0;
     if (fast < 0) return;                                           // block-uniform, like the two below
     cplx* xs = (cplx*)smem;                                         // nfft samples of the burst, in LDS
     if (!fast) {
@@ -226,6 +354,7 @@ __device__ __forceinline__ void burst_tone_body(StreamState* __restrict__ sts, c
     }
     BT_STAMP(1);
     StreamState* st = sts + s;
+    StreamState* sto = LEAN ? st_out + s : st;                      // where the results go
     const int N2 = nfft / 37, ldb = N2 + 1;
     // the window sits in one of the two gather buffers; the other one holds B, the tables go behind the carve
     const GatherCarve gc = gather_carve(a.len, a.level, a.src_kind, a.ntaps, true, a.pad != 0);
@@ -357,7 +486,7 @@ __device__ __forceinline__ void burst_tone_body(StreamState* __restrict__ sts, c
         const double phase = atan2(ti / cnt, tr / cnt);
         sh_phase = phase;
         const double fo = sampling_rate * (ipr + phase) / TWO_PI_D;                    // :155
-        if (res) res[0] = fo; else coherent_store(&st->fo_burst[w], fo);
+        if (res) res[0] = fo; else coherent_store(&sto->fo_burst[w], fo);
     }
     BT_STAMP(3);
     if (!GATE) return;
@@ -408,7 +537,7 @@ __device__ __forceinline__ void burst_tone_body(StreamState* __restrict__ sts, c
             for (int k = 0; k < 3; ++k) sig += P[k];
             for (int k = nb - 2; k < nb; ++k) sig += P[k];
             const double sn = 10.0 * log10(sig / noi);
-            if (res) res[1] = sn; else coherent_store(&st->snr_burst[w], sn);
+            if (res) res[1] = sn; else coherent_store(&sto->snr_burst[w], sn);
         }
     }
     BT_STAMP(4);
@@ -482,13 +611,19 @@ __device__ __forceinline__ void sch_corr_rows(cplx* __restrict__ xs_w, const cpl
 }
 
 // FAST: the drivers' geometry (11*8+1 = 89 offsets, 512-sample training sequence): sch_corr_rows
-template <int FIR_UNR = 1, bool FAST = false>
+// LEAN (k_window_sch of the reference geometry): sts + blockIdx.y is this workgroup's LDS copy of the state, the window
+// comes from sch_gather_fast where it applies, and the results go to the global state st_out + blockIdx.y.
+template <int FIR_UNR = 1, bool FAST = false, bool LEAN = false>
 __device__ __forceinline__ void window_sch_body(StreamState* __restrict__ sts, const GatherArgs& a,
                                                 const cplx* __restrict__ ts, int len_ts, int nshift,
-                                                unsigned char* smem, double* res = nullptr) {   // res: {SCH_pos, edge flag}
+                                                unsigned char* smem, double* res = nullptr,     // res: {SCH_pos, edge flag}
+                                                StreamState* __restrict__ st_out = nullptr) {   // LEAN: the global state
     const int s = blockIdx.y, w = blockIdx.x, tid = threadIdx.x;
     DEV_STAMP(KID_SCH, blockIdx.y * gridDim.x + blockIdx.x, 0);
-    cplx* xs = gather_core<512, -1, FIR_UNR>(sts, a, smem, w, s, true);
+    const int fast = LEAN ? sch_gather_fast<512, FIR_UNR>(sts + s, a, smem, w, s) : 0;
+    if (fast < 0) return;                                                 // block-uniform, like the one below
+    cplx* xs = fast ? (cplx*)(smem + gather_carve(a.len, a.level, a.src_kind, a.ntaps, true, a.pad != 0).off_region1)
+                    : gather_core<512, -1, FIR_UNR>(sts, a, smem, w, s, true);
     if (!xs) return;
     DEV_STAMP(KID_SCH, blockIdx.y * gridDim.x + blockIdx.x, 1);
     const GatherCarve gc = gather_carve(a.len, a.level, a.src_kind, a.ntaps, true, a.pad != 0);
@@ -497,6 +632,7 @@ __device__ __forceinline__ void window_sch_body(StreamState* __restrict__ sts, c
     double* cv = (double*)(part + nshift * SCH_PARTS);                    // nshift correlation powers
     __syncthreads();
     StreamState* st = sts + s;
+    StreamState* sto = LEAN ? st_out + s : st;                            // where the results go
     if (FAST) {
         // (its zero-padded tap copy, 92 + 624 entries, and the 89 powers take less room than tc | part | cv above)
         sch_corr_rows<89, 512>(xs, ts, tc, cv, tid, 512);
@@ -562,8 +698,8 @@ __device__ __forceinline__ void window_sch_body(StreamState* __restrict__ sts, c
             const bool edge = mi == 0 || mi == nshift - 1;                    // :59
             if (res) { res[0] = sp; res[1] = edge ? 1.0 : 0.0; }
             else {
-                coherent_store(&st->sch_first[w], sp);
-                if (edge) atomicOr(&st->sch_edge, 1);
+                coherent_store(&sto->sch_first[w], sp);
+                if (edge) atomicOr(&sto->sch_edge, 1);
             }
         }
     }
@@ -1038,8 +1174,23 @@ k_burst_tone(StreamState* __restrict__ sts, GatherArgs a_in, int nfft_rt, const 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GatherArgs a = a_in;
     const int nfft = OV > 0 ? 148 * OV : nfft_rt, ov = OV > 0 ? OV : ov_rt;
-    if (OV > 0) { a.len = 148 * OV; a.ntaps = NTAPS; a.src_kind = SRC_RAW; a.tiles = 0; a.level = GATE ? 1 : 3; }   // (the chain on raw bytes from level 0: bursts at levels 1 and 3)
-    burst_tone_body<GATE, (OV > 0 ? 2 : 1)>(sts, a, nfft, tw_g, ov, prior_mode, smem);
+    if (OV > 0) {
+        // the reference geometry (the chain on raw bytes from level 0: bursts at levels 1 and 3): the stream's state is copied
+        // into LDS in front of the work area (one round of 16-byte loads, as in k_post_chain_r) and the body runs against the
+        // copy, so that burst_gather_fast builds the window; the raw-byte fallback stages its input compactly (pad = 1) and
+        // three workgroups still fit a CU (host_plan.h: lean_tail_lds).  Results and stream_tail use the global state.
+        a.len = 148 * OV; a.ntaps = NTAPS; a.src_kind = SRC_RAW; a.tiles = 0; a.level = GATE ? 1 : 3; a.pad = 1;
+        StreamState* sh = (StreamState*)smem;
+        {
+            const uint4* src = (const uint4*)(sts + blockIdx.y);
+            uint4* dst = (uint4*)sh;
+            for (int i = threadIdx.x; i < (int)(sizeof(StreamState) / 16); i += BT_THREADS) dst[i] = src[i];
+        }
+        __syncthreads();
+        burst_tone_body<GATE, 2, true>(sh - blockIdx.y, a, nfft, tw_g, ov, prior_mode, smem + PCR_STATE_BYTES, nullptr, false, sts);
+    } else {
+        burst_tone_body<GATE, 1>(sts, a, nfft, tw_g, ov, prior_mode, smem);
+    }
     DEV_STAMP(GATE ? KID_BT1 : KID_BT0, blockIdx.y * gridDim.x + blockIdx.x, 5);
     stream_tail(sts, tail, smem, GATE ? KID_BT1 : KID_BT0);
     DEV_STAMP(GATE ? KID_BT1 : KID_BT0, blockIdx.y * gridDim.x + blockIdx.x, 6);
@@ -1051,8 +1202,20 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6, 8))
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GatherArgs a = a_in;
     const int len_ts = OV > 0 ? LT : len_ts_rt, nshift = OV > 0 ? 11 * OV + 1 : nshift_rt;
-    if (OV > 0) { a.len = 11 * OV + LT; a.ntaps = NTAPS; a.src_kind = SRC_RAW; a.tiles = 0; a.level = 2; }
-    window_sch_body<(OV > 0 ? 2 : 1), (OV == 8 && LT == 512)>(sts, a, ts, len_ts, nshift, smem);
+    if (OV > 0) {
+        // the reference geometry: state copy in LDS and sch_gather_fast, as in k_burst_tone above
+        a.len = 11 * OV + LT; a.ntaps = NTAPS; a.src_kind = SRC_RAW; a.tiles = 0; a.level = 2; a.pad = 0;
+        StreamState* sh = (StreamState*)smem;
+        {
+            const uint4* src = (const uint4*)(sts + blockIdx.y);
+            uint4* dst = (uint4*)sh;
+            for (int i = threadIdx.x; i < (int)(sizeof(StreamState) / 16); i += 512) dst[i] = src[i];
+        }
+        __syncthreads();
+        window_sch_body<2, (OV == 8 && LT == 512), true>(sh - blockIdx.y, a, ts, len_ts, nshift, smem + PCR_STATE_BYTES, nullptr, sts);
+    } else {
+        window_sch_body<1, false>(sts, a, ts, len_ts, nshift, smem);
+    }
     DEV_STAMP(KID_SCH, blockIdx.y * gridDim.x + blockIdx.x, 3);
     stream_tail(sts, tail, smem, KID_SCH);
     DEV_STAMP(KID_SCH, blockIdx.y * gridDim.x + blockIdx.x, 4);
@@ -1122,7 +1285,6 @@ struct PostChainArgs {
 // of every wave: NOTES_r05.md.)
 // ------------------------------------------------------------------------------------------------
 #define PCR_EMPTY 0xFFFFFFFFFFFFFFFFull
-#define PCR_STATE_BYTES ((sizeof(StreamState) + 15) & ~(size_t)15)
 
 __device__ __forceinline__ unsigned long long pcr_word(double v) {
     return v != v ? 0x7FF8000000000000ull : (unsigned long long)__double_as_longlong(v);
