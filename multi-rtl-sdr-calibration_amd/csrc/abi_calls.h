@@ -149,27 +149,17 @@ void gsmcal_ctx_destroy(gsmcal_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipDeviceSynchronize();
     fused_gate_unregister(c);
-    DevBuf* bufs[] = {&c->coef, &c->ts, &c->cf, &c->table, &c->snrhit, &c->arr_in, &c->arr_out, &c->posinfo, &c->rlen,
-                      &c->misc, &c->tw, &c->csum_head, &c->tw_sch, &c->bp_coef, &c->bp_state, &c->bp_part, &c->bp_raw,
-                      &c->bp_out, &c->fd_tw, &c->fd_cf, &c->fd_part, &c->fd_in, &c->fd_len, &c->fd_pos, &c->fd_out,
-                      &c->sb_taps, &c->sb_idx, &c->sb_state, &c->sb_part, &c->sb_raw, &c->sb_out,
-                      &c->cw_state, &c->cw_part, &c->cw_rec, &c->cw_mean, &c->cw_raw, &c->cw_in, &c->cw_out, &c->cw_r};
-    for (DevBuf* b : bufs)
-        if (b->p) (void)hipFree(b->p);
+    const auto free_buf = [](DevBuf& b) { if (b.p) (void)hipFree(b.p); };
+    c->for_each_buf(free_buf);
     for (int i = 0; i < MAX_LANES; ++i) {
         Lane& L = c->lanes[i];
-        DevBuf* lb[] = {&L.state, &L.dec, &L.win, &L.peaks, &L.snrbuf, &L.x0, &L.chunkrec, &L.openlist, &L.cert, &L.partial, &L.tailctr, &L.xch, &L.xepoch};
-        for (DevBuf* b : lb)
-            if (b->p) (void)hipFree(b->p);
+        L.for_each_buf(free_buf);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.front_done) (void)hipEventDestroy(L.front_done);
         if (i > 0 && L.stream) (void)hipStreamDestroy(L.stream);
     }
     for (int i = 0; i < gsmcal_ctx::PIPE_MAX_DEPTH; ++i) {
-        Lane& L = c->pipe[i];
-        DevBuf* lb[] = {&L.state, &L.dec, &L.win, &L.peaks, &L.snrbuf, &L.x0, &L.chunkrec, &L.openlist, &L.cert, &L.partial, &L.tailctr, &L.xch, &L.xepoch};
-        for (DevBuf* b : lb)
-            if (b->p) (void)hipFree(b->p);
+        c->pipe[i].for_each_buf(free_buf);
         if (c->pipe_done[i]) (void)hipEventDestroy(c->pipe_done[i]);
         if (c->side_in[i]) (void)hipEventDestroy(c->side_in[i]);
     }
@@ -713,20 +703,13 @@ int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, c
         LAUNCH(c, k_make_twiddles, dim3((nfft + 255) / 256), dim3(256), 0, (cplx*)c->fd_tw.p, nfft);
         c->fd_tw_n = nfft;
     }
-    if ((int)c->h_fd_cf.size() != d || !c->fd_cf.p || memcmp(c->h_fd_cf.data(), carrier_freq, (size_t)d * sizeof(double)) != 0) {
-        RET_IF(ensure(c, c->fd_cf, (size_t)d * sizeof(double)));
-        c->h_fd_cf.assign(carrier_freq, carrier_freq + d);
-        const hipError_t e = hipMemcpyAsync(c->fd_cf.p, c->h_fd_cf.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { c->h_fd_cf.clear(); c->err = std::string("hipMemcpyAsync (FCCH_demod carrier_freq): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
-    }
+    RET_IF(upload_if_changed(c, c->fd_cf, c->h_fd_cf, carrier_freq, (size_t)d, "FCCH_demod carrier_freq"));
     RET_IF(ensure(c, c->fd_part, (size_t)d * MAXH * FD_PART * sizeof(double)));
     double* part = (double*)c->fd_part.p;
-    const long chunk = 65535;                                   // (the grid's y limit)
-    for (long lo = 0; lo < d; lo += chunk) {
-        const int S = (int)std::min(chunk, (long)d - lo);
+    for_capture_chunks(d, [&](long lo, int S) {
         LAUNCH(c, k_fcch_demod, dim3(MAXH, S), dim3(FD_THREADS), lds, (const cplx*)d_r + (size_t)lo * stride, stride, d_r_len + lo,
                d_pos_info + (size_t)lo * 2 * MAXROWS, nfft, ov, hnl, (const cplx*)c->fd_tw.p, part + (size_t)lo * MAXH * FD_PART);
-    }
+    });
     LAUNCH(c, k_fcch_demod_finish, dim3(d), dim3(64), 0, d_r_len, d_pos_info, (const double*)c->fd_cf.p, (const double*)part, d_out);
     CHECK_LAUNCH(c);
     return 0;
@@ -736,19 +719,14 @@ int gsmcal_fcch_demod_batch(gsmcal_ctx* c, const double* r, long stride, const l
                             const double* carrier_freq, double* out) {
     if (!c || !r || !r_len || !pos_info || !carrier_freq || !out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
     ENTER(c);
-    const size_t nr = (size_t)d * stride * sizeof(cplx), np = (size_t)d * 2 * MAXROWS * sizeof(double);
-    RET_IF(ensure(c, c->fd_in, nr));
-    RET_IF(ensure(c, c->fd_len, (size_t)d * sizeof(long)));
-    RET_IF(ensure(c, c->fd_pos, np));
-    RET_IF(ensure(c, c->fd_out, (size_t)d * GSMCAL_DEMOD_COLS * sizeof(double)));
-    HIPCHK(c, hipMemcpyAsync(c->fd_in.p, r, nr, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->fd_len.p, r_len, (size_t)d * sizeof(long), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->fd_pos.p, pos_info, np, hipMemcpyHostToDevice, c->stream));
+    const Stage io[] = {STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),
+                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
+                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
+                        STAGE(fd_out, (size_t)d * GSMCAL_DEMOD_COLS * sizeof(double), nullptr, out, 0)};
+    RET_IF(stage_up(c, io));
     RET_IF(gsmcal_fcch_demod_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d, ov,
                                        carrier_freq, (double*)c->fd_out.p));
-    HIPCHK(c, hipMemcpyAsync(out, c->fd_out.p, (size_t)d * GSMCAL_DEMOD_COLS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return stage_down(c, io);
 }
 
 int gsmcal_FCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* pos_info, int rows, int ld, int ov, double carrier_freq,
@@ -817,13 +795,10 @@ int gsmcal_frontend_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, cons
     if (!c || !raw || !out || d < 1 || n < 1 || decim < 1) return GSMCAL_E_ARG;
     ENTER(c);
     const long nd = (n + decim - 1) / decim;
-    RET_IF(ensure(c, c->misc, (size_t)2 * n * d));
-    RET_IF(ensure(c, c->arr_out, (size_t)nd * d * sizeof(cplx)));
-    HIPCHK(c, hipMemcpyAsync(c->misc.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
+    const Stage io[] = {STAGE(misc, (size_t)2 * n * d, raw, nullptr, 0), STAGE(arr_out, (size_t)nd * d * sizeof(cplx), nullptr, out, 0)};
+    RET_IF(stage_up(c, io));
     RET_IF(gsmcal_frontend_batch_dev(c, (const uint8_t*)c->misc.p, d, n, coef, ntaps, decim, (double*)c->arr_out.p));
-    HIPCHK(c, hipMemcpyAsync(out, c->arr_out.p, (size_t)nd * d * sizeof(cplx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return stage_down(c, io);
 }
 
 // ---- band power: multi_rtl_sdr_split_scanner.m:154-156, multi_rtl_sdr_diversity_scanner.m:156-158, scan_band_power_spectrum.m:80-84
@@ -842,23 +817,11 @@ int gsmcal_band_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long
     ENTER(c);
     c->cur = &c->lanes[0];                              // the context's stream; the lane's buffers are not touched
     const long nd = (n + decim - 1) / decim;
-    bool sym = ntaps == 32 || ntaps == 64 || ntaps == 128;
-    for (int k = 0; sym && k < ntaps / 2; ++k) sym = coef[k] == coef[ntaps - 1 - k];
-    // kept rows per block: enough for a span of ~BP_SPAN samples (small decimations: several rows per lane), at most what the
-    // LDS budget admits
-    int rows = (int)std::min<long>(BP_MAX_ROWS, std::max<long>(BP_ROWS, (BP_SPAN / decim) / BP_ROWS * BP_ROWS));
-    if (bp_lds_bytes(rows, decim, ntaps, !sym) > BP_LDS_BYTES) {
-        const long fit = ((long)(BP_LDS_BYTES - ((ntaps * 8 + 15) & ~15)) / 2 - 8 - 24 - ntaps) / decim + 1;
-        rows = (int)std::max(1L, std::min<long>(rows, fit));
-    }
+    const bool sym = (ntaps == 32 || ntaps == 64 || ntaps == 128) && taps_symmetric(coef, ntaps);
+    const int rows = kept_rows(decim, ntaps, (size_t)((ntaps * 8 + 15) & ~15), [&](int r) { return bp_lds_bytes(r, decim, ntaps, !sym); });
     const long nblk = (nd + rows - 1) / rows;
     if (nblk > (1L << 30)) return GSMCAL_E_ARG;
-    if ((int)c->h_bp_coef.size() != ntaps || memcmp(c->h_bp_coef.data(), coef, (size_t)ntaps * sizeof(double)) != 0) {
-        RET_IF(ensure(c, c->bp_coef, (size_t)ntaps * sizeof(double)));
-        c->h_bp_coef.assign(coef, coef + ntaps);
-        const hipError_t e = hipMemcpyAsync(c->bp_coef.p, c->h_bp_coef.data(), (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { c->h_bp_coef.clear(); c->err = std::string("hipMemcpyAsync (band-power taps): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
-    }
+    RET_IF(upload_if_changed(c, c->bp_coef, c->h_bp_coef, coef, (size_t)ntaps, "band-power taps"));
     RET_IF(ensure(c, c->bp_state, (size_t)d * sizeof(StreamState)));
     RET_IF(ensure(c, c->bp_part, (size_t)d * nblk * sizeof(double)));
     StreamState* st = (StreamState*)c->bp_state.p;
@@ -866,13 +829,9 @@ int gsmcal_band_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long
     const double* dcoef = (const double*)c->bp_coef.p;
     const size_t lds = bp_lds_bytes(rows, decim, ntaps, !sym);
     LAUNCH(c, k_band_power_clear, dim3((d + 255) / 256), dim3(256), 0, st, d);
-    const long chunk = 65535;                           // (the grid's y limit)
-    for (long lo = 0; lo < d; lo += chunk) {
-        const int S = (int)std::min(chunk, (long)d - lo);
+    for_capture_chunks(d, [&](long lo, int S) {
         const uint8_t* raw = d_raw + (size_t)lo * 2 * n;
-        int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));           // dc_means()'s geometry
-        blocks = std::max(1, std::min(blocks, std::max(1, 4096 / S)));
-        LAUNCH(c, k_dc_sum, dim3(blocks, S), dim3(256), 0, raw, 2 * n, st + lo);
+        launch_dc_sums(c, raw, S, n, st + lo);
         const dim3 grid((unsigned)nblk, S);
         const StreamState* st_lo = st + lo;
         double* part_lo = part + lo * nblk;
@@ -880,7 +839,7 @@ int gsmcal_band_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long
         else if (ntaps == 32) LAUNCH(c, k_band_power32, grid, dim3(256), lds, raw, 2 * n, st_lo, dcoef, ntaps, decim, nd, rows, part_lo);
         else if (ntaps == 64) LAUNCH(c, k_band_power64, grid, dim3(256), lds, raw, 2 * n, st_lo, dcoef, ntaps, decim, nd, rows, part_lo);
         else LAUNCH(c, k_band_power128, grid, dim3(256), lds, raw, 2 * n, st_lo, dcoef, ntaps, decim, nd, rows, part_lo);
-    }
+    });
     LAUNCH(c, k_band_power_finish, dim3((d + 63) / 64), dim3(64), 0, (const double*)part, (int)nblk, d, n, nd, d_power);
     CHECK_LAUNCH(c);
     return 0;
@@ -890,13 +849,10 @@ int gsmcal_band_power_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, co
                             double* power) {
     if (!c || !raw || !coef || !power || d < 1 || n < 1 || ntaps < 1 || ntaps > BP_MAX_TAPS || decim < 1) return GSMCAL_E_ARG;
     ENTER(c);
-    RET_IF(ensure(c, c->bp_raw, (size_t)2 * n * d));
-    RET_IF(ensure(c, c->bp_out, (size_t)d * sizeof(double)));
-    HIPCHK(c, hipMemcpyAsync(c->bp_raw.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
-    RET_IF(gsmcal_band_power_batch_dev(c, (const uint8_t*)c->bp_raw.p, d, n, coef, ntaps, decim, (double*)c->bp_out.p));
-    HIPCHK(c, hipMemcpyAsync(power, c->bp_out.p, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const Stage io[] = {STAGE(stage_raw, (size_t)2 * n * d, raw, nullptr, 0), STAGE(stage_out, (size_t)d * sizeof(double), nullptr, power, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_band_power_batch_dev(c, (const uint8_t*)c->stage_raw.p, d, n, coef, ntaps, decim, (double*)c->stage_out.p));
+    return stage_down(c, io);
 }
 
 // ---- sub-band power: multi_rtl_sdr_diversity_scanner_another_bak.m:186-210, every grid point inside a capture out of that capture
@@ -921,11 +877,7 @@ int gsmcal_subband_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, l
     const long nd = (n + decim - 1) / decim;
     // kept rows per block as in gsmcal_band_power_batch_dev, with the LDS of GSMCAL_MAX_SUBBANDS tap rows set aside whatever nsub
     // is: the tiling -- and with it every bit of a sub-band's power -- depends on n, decim and ntaps only
-    int rows = (int)std::min<long>(BP_MAX_ROWS, std::max<long>(BP_ROWS, (BP_SPAN / decim) / BP_ROWS * BP_ROWS));
-    if (sb_lds_bytes(rows, decim, ntaps, SB_MAX_SUBBANDS) > BP_LDS_BYTES) {
-        const long fit = ((long)(BP_LDS_BYTES - SB_MAX_SUBBANDS * ntaps * sizeof(cplx)) / 2 - 8 - 24 - ntaps) / decim + 1;
-        rows = (int)std::max(1L, std::min<long>(rows, fit));
-    }
+    const int rows = kept_rows(decim, ntaps, SB_MAX_SUBBANDS * ntaps * sizeof(cplx), [&](int r) { return sb_lds_bytes(r, decim, ntaps, SB_MAX_SUBBANDS); });
     const long nblk = (nd + rows - 1) / rows;
     if (nblk > (1L << 30)) return GSMCAL_E_ARG;
     // distinct finite phases in order of first appearance (-0 counts as 0: the same taps) and the index table
@@ -947,10 +899,7 @@ int gsmcal_subband_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, l
     const bool same_coef = (int)c->h_sb_coef.size() == ntaps && memcmp(c->h_sb_coef.data(), coef, (size_t)ntaps * sizeof(double)) == 0;
     const bool same_w = c->h_sb_w.size() == w.size() && (w.empty() || memcmp(c->h_sb_w.data(), w.data(), w.size() * sizeof(double)) == 0);
     if (!w.empty() && (!same_coef || !same_w || !c->sb_taps.p)) {
-        const size_t nb = w.size() * ntaps * sizeof(cplx);
-        RET_IF(ensure(c, c->sb_taps, nb));
-        c->h_sb_coef.assign(coef, coef + ntaps);
-        c->h_sb_w = w;
+        c->h_sb_coef.clear(); c->h_sb_w.clear();           // (what the rows are built from is the cache's key: set once they have gone up)
         c->h_sb_rows.resize(w.size() * ntaps * 2);
         for (size_t u = 0; u < w.size(); ++u)
             for (int m = 0; m < ntaps; ++m) {              // row[m] multiplies the sample m after the oldest: tap k = ntaps-1-m
@@ -958,15 +907,11 @@ int gsmcal_subband_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, l
                 c->h_sb_rows[(u * ntaps + m) * 2] = coef[k] * cos((double)k * w[u]);
                 c->h_sb_rows[(u * ntaps + m) * 2 + 1] = -(coef[k] * sin((double)k * w[u]));
             }
-        const hipError_t e = hipMemcpyAsync(c->sb_taps.p, c->h_sb_rows.data(), nb, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { c->h_sb_coef.clear(); c->h_sb_w.clear(); c->err = std::string("hipMemcpyAsync (sub-band taps): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
+        RET_IF(upload_host_copy(c, c->sb_taps, c->h_sb_rows, "sub-band taps"));
+        c->h_sb_coef.assign(coef, coef + ntaps);
+        c->h_sb_w = w;
     }
-    if (c->h_sb_idx != idx || !c->sb_idx.p) {
-        RET_IF(ensure(c, c->sb_idx, cells * sizeof(int)));
-        c->h_sb_idx.swap(idx);
-        const hipError_t e = hipMemcpyAsync(c->sb_idx.p, c->h_sb_idx.data(), cells * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { c->h_sb_idx.clear(); c->err = std::string("hipMemcpyAsync (sub-band index table): ") + hipGetErrorString(e); return GSMCAL_E_HIP; }
-    }
+    RET_IF(upload_if_changed(c, c->sb_idx, c->h_sb_idx, idx.data(), cells, "sub-band index table"));
     RET_IF(ensure(c, c->sb_state, (size_t)d * sizeof(StreamState)));
     RET_IF(ensure(c, c->sb_part, (size_t)d * nblk * nsub * sizeof(double)));
     StreamState* st = (StreamState*)c->sb_state.p;
@@ -974,16 +919,12 @@ int gsmcal_subband_power_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, l
     const int* didx = (const int*)c->sb_idx.p;
     const size_t lds = sb_lds_bytes(rows, decim, ntaps, nsub);
     LAUNCH(c, k_band_power_clear, dim3((d + 255) / 256), dim3(256), 0, st, d);
-    const long chunk = 65535;                           // (the grid's y limit)
-    for (long lo = 0; lo < d; lo += chunk) {
-        const int S = (int)std::min(chunk, (long)d - lo);
+    for_capture_chunks(d, [&](long lo, int S) {
         const uint8_t* raw = d_raw + (size_t)lo * 2 * n;
-        int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));           // dc_means()'s geometry
-        blocks = std::max(1, std::min(blocks, std::max(1, 4096 / S)));
-        LAUNCH(c, k_dc_sum, dim3(blocks, S), dim3(256), 0, raw, 2 * n, st + lo);
+        launch_dc_sums(c, raw, S, n, st + lo);
         LAUNCH(c, k_subband_power, dim3((unsigned)nblk, S), dim3(256), lds, raw, 2 * n, (const StreamState*)(st + lo),
                (const cplx*)c->sb_taps.p, didx + lo * nsub, ntaps, nsub, decim, nd, rows, part + lo * nblk * nsub);
-    }
+    });
     LAUNCH(c, k_subband_power_finish, dim3((unsigned)((cells + 63) / 64)), dim3(64), 0, (const double*)part, didx, (int)nblk, d, nsub,
            n, nd, d_power);
     CHECK_LAUNCH(c);
@@ -994,14 +935,10 @@ int gsmcal_subband_power_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n,
                                const double* phase_rotate, int nsub, double* power) {
     if (!c || !sb_args_ok(raw, d, n, coef, ntaps, decim, phase_rotate, nsub, power)) return GSMCAL_E_ARG;
     ENTER(c);
-    const size_t nout = (size_t)d * nsub * sizeof(double);
-    RET_IF(ensure(c, c->sb_raw, (size_t)2 * n * d));
-    RET_IF(ensure(c, c->sb_out, nout));
-    HIPCHK(c, hipMemcpyAsync(c->sb_raw.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
-    RET_IF(gsmcal_subband_power_batch_dev(c, (const uint8_t*)c->sb_raw.p, d, n, coef, ntaps, decim, phase_rotate, nsub, (double*)c->sb_out.p));
-    HIPCHK(c, hipMemcpyAsync(power, c->sb_out.p, nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const Stage io[] = {STAGE(stage_raw, (size_t)2 * n * d, raw, nullptr, 0), STAGE(stage_out, (size_t)d * nsub * sizeof(double), nullptr, power, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_subband_power_batch_dev(c, (const uint8_t*)c->stage_raw.p, d, n, coef, ntaps, decim, phase_rotate, nsub, (double*)c->stage_out.p));
+    return stage_down(c, io);
 }
 
 // ---- CW sample-loss check: CW_check.m:6-8 (check_CW_samples_loss_tcp.m:70,89-90) ------------------------------------------------
@@ -1030,26 +967,21 @@ static int cw_enqueue(gsmcal_ctx* c, const uint8_t* d_raw, const cplx* arr, int 
     CwPart* part = (CwPart*)c->cw_part.p;
     CwRec* rec = (CwRec*)c->cw_rec.p;
     CwMean* mean = (CwMean*)c->cw_mean.p;
-    const long chunk = 65535;                           // (the grid's y limit)
     if (nblk > 0) {
         if (!arr) LAUNCH(c, k_band_power_clear, dim3((d + 255) / 256), dim3(256), 0, st, d);
-        for (long lo = 0; lo < d; lo += chunk) {
-            const int S = (int)std::min(chunk, (long)d - lo);
+        for_capture_chunks(d, [&](long lo, int S) {
             const dim3 grid((unsigned)nblk, S);
             if (arr) {
                 LAUNCH(c, k_cw_ratio_sum_arr, grid, dim3(256), 0, (const uint8_t*)nullptr, 0L, (const StreamState*)st, arr, n, n, part);
             } else {
                 const uint8_t* raw = d_raw + (size_t)lo * 2 * n;
-                int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));       // dc_means()'s geometry
-                blocks = std::max(1, std::min(blocks, std::max(1, 4096 / S)));
-                LAUNCH(c, k_dc_sum, dim3(blocks, S), dim3(256), 0, raw, 2 * n, st + lo);
+                launch_dc_sums(c, raw, S, n, st + lo);
                 LAUNCH(c, k_cw_ratio_sum_raw, grid, dim3(256), 0, raw, 2 * n, (const StreamState*)(st + lo), (const cplx*)nullptr, 0L, n,
                        part + lo * nblk);
             }
-        }
+        });
         LAUNCH(c, k_cw_finish_mean, dim3((d + 63) / 64), dim3(64), 0, (const CwPart*)part, (int)nblk, d, n, mean);
-        for (long lo = 0; lo < d; lo += chunk) {
-            const int S = (int)std::min(chunk, (long)d - lo);
+        for_capture_chunks(d, [&](long lo, int S) {
             const dim3 grid((unsigned)nblk, S);
             double* r_lo = d_r ? d_r + (size_t)lo * r_stride : nullptr;
             if (arr)
@@ -1058,7 +990,7 @@ static int cw_enqueue(gsmcal_ctx* c, const uint8_t* d_raw, const cplx* arr, int 
             else
                 LAUNCH(c, k_cw_residual_raw, grid, dim3(256), 0, d_raw + (size_t)lo * 2 * n, 2 * n, (const StreamState*)(st + lo),
                        (const cplx*)nullptr, 0L, n, (const CwMean*)(mean + lo), thr, r_lo, r_stride, rec + lo * nblk);
-        }
+        });
     }
     if (arr)
         LAUNCH(c, k_cw_finish_summary_arr, dim3(d), dim3(256), 0, (const uint8_t*)nullptr, 0L, (const StreamState*)st, arr, n, n,
@@ -1092,14 +1024,14 @@ int gsmcal_cw_check_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n
 int gsmcal_cw_check_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, double thr, double* summary, double* r, long r_stride) {
     RET_IF(cw_args_ok(c, raw, d, n, thr, summary, r, r_stride));
     ENTER(c);
-    const size_t nsum = (size_t)d * GSMCAL_CW_COLS * sizeof(double);
-    RET_IF(ensure(c, c->cw_raw, (size_t)2 * n * d));
-    RET_IF(ensure(c, c->cw_out, nsum));
-    if (r && n >= 2) RET_IF(ensure(c, c->cw_r, (size_t)d * (n - 1) * sizeof(double)));
-    HIPCHK(c, hipMemcpyAsync(c->cw_raw.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
-    RET_IF(cw_enqueue(c, (const uint8_t*)c->cw_raw.p, nullptr, d, n, thr, (double*)c->cw_out.p, r && n >= 2 ? (double*)c->cw_r.p : nullptr, n - 1));
-    HIPCHK(c, hipMemcpyAsync(summary, c->cw_out.p, nsum, hipMemcpyDeviceToHost, c->stream));
-    if (r && n >= 2)                                    // the device rows are packed; the caller's padding is not written
+    const bool want_r = r && n >= 2;
+    const Stage io[] = {STAGE(stage_raw, (size_t)2 * n * d, raw, nullptr, 0),
+                        STAGE(stage_out, (size_t)d * GSMCAL_CW_COLS * sizeof(double), nullptr, summary, 0),
+                        STAGE(cw_r, want_r ? (size_t)d * (n - 1) * sizeof(double) : 0, nullptr, nullptr, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(cw_enqueue(c, (const uint8_t*)c->stage_raw.p, nullptr, d, n, thr, (double*)c->stage_out.p, want_r ? (double*)c->cw_r.p : nullptr, n - 1));
+    RET_IF(stage_down(c, io, false));
+    if (want_r)                                         // the device rows are packed; the caller's padding is not written
         HIPCHK(c, hipMemcpy2DAsync(r, (size_t)r_stride * sizeof(double), c->cw_r.p, (size_t)(n - 1) * sizeof(double),
                                    (size_t)(n - 1) * sizeof(double), (size_t)d, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1110,16 +1042,13 @@ int gsmcal_CW_check(gsmcal_ctx* c, const double* s, long len, double* r, double*
     if (!c) return GSMCAL_E_ARG;
     if (!s || !r || len < 2 || len > (1L << 36)) { c->err = "CW_check: s and r must not be NULL and len must be 2 .. 2^36"; return GSMCAL_E_ARG; }
     ENTER(c);
-    RET_IF(ensure(c, c->cw_in, (size_t)len * sizeof(cplx)));
-    RET_IF(ensure(c, c->cw_out, (size_t)GSMCAL_CW_COLS * sizeof(double)));
-    RET_IF(ensure(c, c->cw_r, (size_t)(len - 1) * sizeof(double)));
-    HIPCHK(c, hipMemcpyAsync(c->cw_in.p, s, (size_t)len * sizeof(cplx), hipMemcpyHostToDevice, c->stream));
-    // (no threshold in the MATLAB signature: one nothing exceeds, so no block is evaluated again for the event list)
-    RET_IF(cw_enqueue(c, nullptr, (const cplx*)c->cw_in.p, 1, len, 1e300, (double*)c->cw_out.p, (double*)c->cw_r.p, len - 1));
     double row[GSMCAL_CW_COLS];
-    HIPCHK(c, hipMemcpyAsync(row, c->cw_out.p, sizeof(row), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(r, c->cw_r.p, (size_t)(len - 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const Stage io[] = {STAGE(cw_in, (size_t)len * sizeof(cplx), s, nullptr, 0), STAGE(stage_out, sizeof(row), nullptr, row, 0),
+                        STAGE(cw_r, (size_t)(len - 1) * sizeof(double), nullptr, r, 0)};
+    RET_IF(stage_up(c, io));
+    // (no threshold in the MATLAB signature: one nothing exceeds, so no block is evaluated again for the event list)
+    RET_IF(cw_enqueue(c, nullptr, (const cplx*)c->cw_in.p, 1, len, 1e300, (double*)c->stage_out.p, (double*)c->cw_r.p, len - 1));
+    RET_IF(stage_down(c, io));
     if (phase_rotate) *phase_rotate = row[0];
     return 0;
 }
@@ -1140,11 +1069,7 @@ int gsmcal_fcch_scan_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long 
     // workgroups -- sits underneath the bandwidth-bound front kernel of call i+1 (multi_rtl_sdr_gsm_FCCH_scanner.m:132-135,163-186
     // over consecutive sweeps).  Same semantics as for calibration calls: outputs complete at call i + depth / gsmcal_sync / any other
     // entry point.
-    bool pipelined = c->pipe_depth > 1 && !c->prof && c->stream != nullptr && plan_lanes(c, d, false) == 1;
-    if (pipelined) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); pipelined = false; }
-    }
+    const bool pipelined = pipe_may_fly(c, d, false);
     const bool same_taps = (int)c->h_coef.size() == ntaps && memcmp(c->h_coef.data(), coef, (size_t)ntaps * sizeof(double)) == 0 && c->head_epoch == c->coef_epoch;
     if (!pipelined || !same_taps) RET_IF(pipe_join(c));
     c->cur = &c->lanes[0];
@@ -1154,37 +1079,14 @@ int gsmcal_fcch_scan_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long 
     c->last_raw = d_raw;
     RET_IF(upload_cached(c, c->coef, c->h_coef, coef, ntaps));
     RET_IF(ensure_head(c, decim));
-    if (pipelined) {
-        RET_IF(pipe_prepare(c));
-        const int slot = (int)(c->pipe_calls % (unsigned long)c->pipe_depth);
-        Lane& L = c->pipe[slot];
-        if (c->pipe_pending[slot]) {
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->pipe_done[slot], 0));
-            c->pipe_pending[slot] = false;
-        }
-        HIPCHK(c, hipEventRecord(c->side_in[slot], c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->side_stream[slot], c->side_in[slot], 0));
-        L.stream = c->side_stream[slot];
-        L.lo = 0; L.n = d;
-        c->cur = &L;
-        c->n_lanes_used = 1;
-        int rc = ensure(c, L.dec, (size_t)d * nd * sizeof(cplx));
-        if (rc >= 0) rc = front_fused(c, d_raw, d, n, (const double*)c->coef.p, ntaps, decim, (cplx*)L.dec.p, nd, 0, d);
-        if (rc >= 0) {
+    if (pipelined)
+        return pipe_call(c, d, [&](Lane& L) -> int {
+            RET_IF(ensure(c, L.dec, (size_t)d * nd * sizeof(cplx)));
+            RET_IF(front_fused(c, d_raw, d, n, (const double*)c->coef.p, ntaps, decim, (cplx*)L.dec.p, nd, 0, d));
             ScanAccept acc;
             acc.snr_numhit = d_snr_numhit; acc.positions = d_positions; acc.pos_snr = d_pos_snr; acc.counts = d_counts;
-            rc = coarse(c, d, (const cplx*)L.dec.p, nd, nd, dec_ratio, 0, true, n, decim, &acc, true);
-        }
-        if (hipEventRecord(c->pipe_done[slot], L.stream) != hipSuccess) { c->err = "hipEventRecord (calls in flight)"; rc = GSMCAL_E_HIP; }
-        c->pipe_pending[slot] = true;
-        c->pipe_last_slot = slot;
-        ++c->pipe_calls;
-        c->detail_lane = &L;
-        c->cur = &c->lanes[0];
-        c->last_S = d;
-        if (rc < 0) { (void)pipe_drain(c); return rc; }
-        return 0;
-    }
+            return coarse(c, d, (const cplx*)L.dec.p, nd, nd, dec_ratio, 0, true, n, decim, &acc, true);
+        });
     const std::vector<uintptr_t> key = {(uintptr_t)d_raw, (uintptr_t)d, (uintptr_t)n, (uintptr_t)ntaps,
                                         (uintptr_t)d_snr_numhit, (uintptr_t)d_positions, (uintptr_t)d_pos_snr,
                                         (uintptr_t)d_counts, (uintptr_t)c->n_lanes_cfg, (uintptr_t)c->params_epoch};
@@ -1231,21 +1133,20 @@ int gsmcal_fcch_scan_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, con
                            double* num_hit, double* positions, double* pos_snr, int* counts) {
     if (!c || !raw || !snr || !num_hit || d < 1 || n < 1) return GSMCAL_E_ARG;
     ENTER(c);
-    RET_IF(ensure(c, c->misc, (size_t)2 * n * d));
-    RET_IF(ensure(c, c->snrhit, (size_t)d * (2 + 2 * MAXH) * sizeof(double) + (size_t)d * sizeof(int)));
-    HIPCHK(c, hipMemcpyAsync(c->misc.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
+    // snrhit: [d][2] SNR and hit count | [d][MAXH] positions | [d][MAXH] their SNRs | [d] counts
+    const size_t nsn = (size_t)2 * d * sizeof(double), npos = (size_t)d * MAXH * sizeof(double);
+    std::vector<double> sn((size_t)2 * d);
+    const Stage io[] = {STAGE(misc, (size_t)2 * n * d, raw, nullptr, 0), STAGE(snrhit, nsn + 2 * npos + (size_t)d * sizeof(int), nullptr, nullptr, 0),
+                        STAGE(snrhit, nsn, nullptr, sn.data(), 0), STAGE(snrhit, npos, nullptr, positions, nsn),
+                        STAGE(snrhit, npos, nullptr, pos_snr, nsn + npos), STAGE(snrhit, (size_t)d * sizeof(int), nullptr, counts, nsn + 2 * npos)};
+    RET_IF(stage_up(c, io));
     double* d_sn = (double*)c->snrhit.p;
     double* d_pos = d_sn + (size_t)2 * d;
     double* d_ps = d_pos + (size_t)d * MAXH;
     int* d_cnt = (int*)(d_ps + (size_t)d * MAXH);
     RET_IF(gsmcal_fcch_scan_batch_dev(c, (const uint8_t*)c->misc.p, d, n, coef, ntaps, d_sn, d_pos, d_ps, d_cnt));
     RET_IF(pipe_join(c));                      // (a pipelined context: the copies below wait for this call like for any other)
-    std::vector<double> sn((size_t)2 * d);
-    HIPCHK(c, hipMemcpyAsync(sn.data(), d_sn, sn.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (positions) HIPCHK(c, hipMemcpyAsync(positions, d_pos, (size_t)d * MAXH * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pos_snr) HIPCHK(c, hipMemcpyAsync(pos_snr, d_ps, (size_t)d * MAXH * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (counts) HIPCHK(c, hipMemcpyAsync(counts, d_cnt, (size_t)d * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    RET_IF(stage_down(c, io));
     for (int i = 0; i < d; ++i) { snr[i] = sn[2 * i]; num_hit[i] = sn[2 * i + 1]; }
     return 0;
 }
@@ -1256,9 +1157,7 @@ static int launch_r_correct(gsmcal_ctx* c, Lane& L, const Source& src, const uin
     ta.raw = raw_i; ta.raw_stride = 2 * n; ta.coef = (const double*)c->coef.p; ta.ntaps = ntaps;
     ta.dst = (cplx*)d_r_correct_lane; ta.dst_stream_stride = n;
     const size_t tlds = stream_tile_lds(ntaps);
-    bool sym = (int)c->h_coef.size() == ntaps;         // exactly mirrored taps (what fir1 returns)
-    for (int k = 0; sym && k < ntaps / 2; ++k) sym = c->h_coef[k] == c->h_coef[ntaps - 1 - k];
-    if (ntaps == 47 && sym) {                           // the drivers' filter: taps in registers, every sample read once
+    if (ntaps == 47 && (int)c->h_coef.size() == ntaps && taps_symmetric(c->h_coef.data(), ntaps)) {   // the drivers' filter: taps in registers, every sample read once
         LAUNCH(c, k_stream_tile_s47<ST47_TILE>, dim3((unsigned)((n + (long)ST47_TILE * ST_TPB - 1) / ((long)ST47_TILE * ST_TPB)), S), dim3(ST_THREADS), stream_tile_s47_lds(), (const StreamState*)L.state.p, ta);
         CHECK_LAUNCH(c);
     } else if (tlds <= 64 * 1024) {
@@ -1293,12 +1192,8 @@ int gsmcal_calibrate_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long 
     // Calls in flight (gsmcal_ctx_set_pipeline_depth > 1): calls that run on one lane.  Anything that would touch what the calls in
     // flight still read (new taps / training sequence / carrier frequencies, a workspace that must grow, the twiddle table) joins
     // them into the context's stream first.
-    const bool want_pipe = c->pipe_depth > 1 && c->stream != nullptr && plan_lanes(c, d) == 1;
-    bool pipelined = want_pipe && !c->prof;
-    if (pipelined) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); pipelined = false; }
-    }
+    bool want_pipe;
+    const bool pipelined = pipe_may_fly(c, d, true, &want_pipe);
     // (events on every dispatch -- gsmcal_profile_enable -- or the caller's own stream capture: one call at a time, but with the
     // kernels the calls in flight run, so that a per-kernel profile of a depth-4 context describes what the depth-4 loop launches)
     const bool same_kernels_unpipelined = want_pipe && !pipelined;
@@ -1318,47 +1213,22 @@ int gsmcal_calibrate_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long 
     RET_IF(upload_cached(c, c->cf, c->h_cf, carrier_freq, d));
     RET_IF(ensure_head(c, decim));
     RET_IF(ensure_twiddles(c, g.nfft));
-    if (pipelined) {
-        // slot = workspace and stream of this call; the context's stream first waits for the call that used it `depth` calls ago
-        // (that call's outputs are complete in the context's stream order from here on), then the slot's stream takes the call behind
-        // whatever the context's stream holds now: front end + coarse detector (:107,110,117), fine search (:118), four-launch tail
-        RET_IF(pipe_prepare(c));
-        const int slot = (int)(c->pipe_calls % (unsigned long)c->pipe_depth);
-        Lane& L = c->pipe[slot];
-        if (c->pipe_pending[slot]) {
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->pipe_done[slot], 0));
-            c->pipe_pending[slot] = false;
-        }
-        c->cur = &L;
-        c->n_lanes_used = 1;
-        L.lo = 0; L.n = d;
-        HIPCHK(c, hipEventRecord(c->side_in[slot], c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->side_stream[slot], c->side_in[slot], 0));
-        L.stream = c->side_stream[slot];
-        c->no_fuse_now = true;
-        RET_IF(ensure(c, L.dec, (size_t)d * nd * sizeof(cplx)));
-        RET_IF(front_fused(c, d_raw, d, n, (const double*)c->coef.p, ntaps, decim, (cplx*)L.dec.p, nd));
-        RET_IF(coarse(c, d, (const cplx*)L.dec.p, nd, nd, dec_ratio, ov, true, n, decim));
-        Source src{SRC_RAW, d_raw, 2 * n, nullptr, 0, (const double*)c->coef.p, ntaps};
-        c->cf_lane = (const double*)c->cf.p;
-        ChainOut co{d_table, d_pos_info, d_r_len, false};
-        int rc = run_fine(c, d, src, 0, g, H, true, 2, len_ts, &co);
-        if (rc >= 0 && !co.fused) {
-            rc = run_sch(c, d, src, 2, g, H, len_ts, true, 3);
-            if (rc >= 0) rc = run_post(c, d, src, 3, g, H, true, co.table, co.pos_info_out, co.r_len_out);
-        }
-        if (rc >= 0 && d_r_correct) rc = launch_r_correct(c, L, src, d_raw, d, n, ntaps, d_r_correct);
-        c->cf_lane = nullptr; c->no_fuse_now = false;
-        if (hipEventRecord(c->pipe_done[slot], L.stream) != hipSuccess) { c->err = "hipEventRecord (calls in flight)"; rc = GSMCAL_E_HIP; }
-        c->pipe_pending[slot] = true;
-        c->pipe_last_slot = slot;
-        ++c->pipe_calls;
-        c->detail_lane = &L;
-        c->cur = &c->lanes[0];
-        c->last_S = d;
-        if (rc < 0) { (void)pipe_drain(c); return rc; }
-        return 0;
-    }
+    if (pipelined)      // front end + coarse detector (:107,110,117), fine search (:118), four-launch tail
+        return pipe_call(c, d, [&](Lane& L) -> int {
+            c->no_fuse_now = true;
+            RET_IF(ensure(c, L.dec, (size_t)d * nd * sizeof(cplx)));
+            RET_IF(front_fused(c, d_raw, d, n, (const double*)c->coef.p, ntaps, decim, (cplx*)L.dec.p, nd));
+            RET_IF(coarse(c, d, (const cplx*)L.dec.p, nd, nd, dec_ratio, ov, true, n, decim));
+            Source src{SRC_RAW, d_raw, 2 * n, nullptr, 0, (const double*)c->coef.p, ntaps};
+            c->cf_lane = (const double*)c->cf.p;
+            ChainOut co{d_table, d_pos_info, d_r_len, false};
+            RET_IF(run_fine(c, d, src, 0, g, H, true, 2, len_ts, &co));
+            if (!co.fused) {
+                RET_IF(run_sch(c, d, src, 2, g, H, len_ts, true, 3));
+                RET_IF(run_post(c, d, src, 3, g, H, true, co.table, co.pos_info_out, co.r_len_out));
+            }
+            return d_r_correct ? launch_r_correct(c, L, src, d_raw, d, n, ntaps, d_r_correct) : 0;
+        });
     // independent streams: split over lanes (HIP streams) so latency-bound stages of one group overlap the
     // compute-bound fine search of another; a repeated call is replayed as one hipGraph
     const std::vector<uintptr_t> key = {(uintptr_t)d_raw, (uintptr_t)d, (uintptr_t)n, (uintptr_t)ntaps, (uintptr_t)len_ts,
@@ -1416,12 +1286,12 @@ int gsmcal_calibrate_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, con
                            double* pos_info, double* r_correct, long* r_len) {
     if (!c || !raw || !table || d < 1 || n < 1) return GSMCAL_E_ARG;
     ENTER(c);
-    RET_IF(ensure(c, c->misc, (size_t)2 * n * d));
-    RET_IF(ensure(c, c->table, (size_t)d * GSMCAL_TABLE_COLS * sizeof(double)));
-    RET_IF(ensure(c, c->posinfo, (size_t)d * 2 * MAXROWS * sizeof(double)));
-    RET_IF(ensure(c, c->rlen, (size_t)d * sizeof(long)));
-    if (r_correct) RET_IF(ensure(c, c->arr_out, (size_t)d * n * sizeof(cplx)));
-    HIPCHK(c, hipMemcpyAsync(c->misc.p, raw, (size_t)2 * n * d, hipMemcpyHostToDevice, c->stream));
+    const Stage io[] = {STAGE(misc, (size_t)2 * n * d, raw, nullptr, 0),
+                        STAGE(table, (size_t)d * GSMCAL_TABLE_COLS * sizeof(double), nullptr, table, 0),
+                        STAGE(posinfo, (size_t)d * 2 * MAXROWS * sizeof(double), nullptr, pos_info, 0),
+                        STAGE(rlen, (size_t)d * sizeof(long), nullptr, r_len, 0),
+                        STAGE(arr_out, r_correct ? (size_t)d * n * sizeof(cplx) : 0, nullptr, r_correct, 0)};
+    RET_IF(stage_up(c, io));
     RET_IF(gsmcal_calibrate_batch_dev(c, (const uint8_t*)c->misc.p, d, n, coef, ntaps, sch_ts, len_ts, carrier_freq,
                                       (double*)c->table.p, (double*)c->posinfo.p,
                                       r_correct ? (double*)c->arr_out.p : nullptr, (long*)c->rlen.p));
@@ -1430,13 +1300,6 @@ int gsmcal_calibrate_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, con
         HIPCHK(c, hipStreamSynchronize(c->stream));
         RET_IF(fused_recover(c));
     }
-    HIPCHK(c, hipMemcpyAsync(table, c->table.p, (size_t)d * GSMCAL_TABLE_COLS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pos_info)
-        HIPCHK(c, hipMemcpyAsync(pos_info, c->posinfo.p, (size_t)d * 2 * MAXROWS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (r_len) HIPCHK(c, hipMemcpyAsync(r_len, c->rlen.p, (size_t)d * sizeof(long), hipMemcpyDeviceToHost, c->stream));
-    if (r_correct)
-        HIPCHK(c, hipMemcpyAsync(r_correct, c->arr_out.p, (size_t)d * n * sizeof(cplx), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return stage_down(c, io);
 }
 

@@ -22,9 +22,19 @@ struct ProfRec {
 // lanes so that one group's latency-bound stages (coarse scan, decisions, small FFTs) run underneath
 // another group's compute-bound fine search.  Lane 0 runs on the context's own stream.
 #define MAX_LANES 32
-struct Lane {
-    hipStream_t stream = nullptr;
+// Device buffers live in structs of nothing else; for_each_buf (gsmcal_ctx_destroy frees through it) must list every one to compile.
+#define ALL_BUFS(Owner, ...)                                                                                                        \
+    template <class F> void for_each_buf(F f) {                                                                                     \
+        DevBuf* all[] = {__VA_ARGS__};                                                                                              \
+        static_assert(sizeof(all) / sizeof(all[0]) == sizeof(Owner) / sizeof(DevBuf), #Owner ": a DevBuf is missing from for_each_buf"); \
+        for (DevBuf* b : all) f(*b);                                                                                                \
+    }
+struct LaneBufs {
     DevBuf state, dec, win, peaks, snrbuf, x0, chunkrec, openlist, cert, partial, tailctr, xch, xepoch;
+    ALL_BUFS(LaneBufs, &state, &dec, &win, &peaks, &snrbuf, &x0, &chunkrec, &openlist, &cert, &partial, &tailctr, &xch, &xepoch)
+};
+struct Lane : LaneBufs {
+    hipStream_t stream = nullptr;
     int npartial = 0;           // front-kernel blocks per stream of the last front_fused()
     hipEvent_t done = nullptr;
     hipEvent_t front_done = nullptr;   // scanner pipeline: this stage's front kernel has finished
@@ -33,7 +43,30 @@ struct Lane {
     int win_l0_len = 0, win_l0_H = 0;  // > 0: `win` holds the fine search's level-0 windows (this length each, H per stream) of the call in progress
 };
 
-struct gsmcal_ctx {
+struct CtxBufs {
+    // shared workspace
+    DevBuf coef, ts, cf, table, snrhit, arr_in, arr_out, posinfo, rlen, misc, tw, csum_head, tw_sch;
+    // The add-on entry points below keep workspaces of their own, so that a call leaves the lanes, the shared taps and every answer
+    // about the calibration / scan call before it untouched.  Their host-buffer wrappers share two staging buffers, raw bytes in and
+    // results out: each wrapper has read its results back before it returns, so no call finds another's in them.  (`misc` is not
+    // among them: the raw bytes of a calibrate / scan batch stay in place for the calls that ask about that batch later.)
+    DevBuf stage_raw, stage_out;
+    // band power (gsmcal_band_power_batch*)
+    DevBuf bp_coef, bp_state, bp_part;
+    // FCCH_demod (gsmcal_FCCH_demod, gsmcal_fcch_demod_batch*) -- its twiddle table too, the oversampling ratio may differ from the chain's
+    DevBuf fd_tw, fd_cf, fd_part, fd_in, fd_len, fd_pos, fd_out;
+    // sub-band power (gsmcal_subband_power_batch*).  sb_taps: one modulated tap row per distinct phase_rotate value, built on the
+    // host; sb_idx: the [capture][slot] table into them
+    DevBuf sb_taps, sb_idx, sb_state, sb_part;
+    // CW sample-loss check (gsmcal_CW_check, gsmcal_cw_check_batch*).  cw_state: the byte sums; cw_part / cw_rec: one record per
+    // (capture, tile) of the two passes; cw_mean: phase_rotate and status per capture
+    DevBuf cw_state, cw_part, cw_rec, cw_mean, cw_in, cw_r;
+    ALL_BUFS(CtxBufs, &coef, &ts, &cf, &table, &snrhit, &arr_in, &arr_out, &posinfo, &rlen, &misc, &tw, &csum_head, &tw_sch, &stage_raw,
+             &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &sb_taps, &sb_idx,
+             &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r)
+};
+
+struct gsmcal_ctx : CtxBufs {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -135,31 +168,15 @@ struct gsmcal_ctx {
     int post_slots_cap = 0;           // GSMCAL_POST_SLOTS: upper bound on the fused tail's workgroups per CU (0: the occupancy calculator's figure)
     gsmcal_params params;           // thresholds (defaults = the reference's literals)
     unsigned long params_epoch = 0; // bumped by gsmcal_set_params: captured graphs carry the old values
-    // shared workspace
-    DevBuf coef, ts, cf, table, snrhit, arr_in, arr_out, posinfo, rlen, misc, tw, csum_head, tw_sch;
     int tw_sch_n = 0;                        // length the SCH-demodulator twiddle table was built for
     std::vector<double> h_head;              // partial tap sums uploaded to csum_head (see coarse())
     unsigned long coef_epoch = 0, head_epoch = ~0ul;   // coef_epoch: bumped whenever h_coef changes
     int tw_n = 0;                            // length the twiddle table was built for
     std::vector<double> h_coef, h_ts, h_cf;   // host copies: upload only when changed
-    // band power (gsmcal_band_power_batch*): workspaces of its own, so that a band-power call leaves the lanes, the shared
-    // taps and every answer about the calibration / scan call before it untouched
-    DevBuf bp_coef, bp_state, bp_part, bp_raw, bp_out;
-    std::vector<double> h_bp_coef;
-    // FCCH_demod (gsmcal_FCCH_demod, gsmcal_fcch_demod_batch*): workspaces of its own for the same reason -- its twiddle table too,
-    // the oversampling ratio may differ from the chain's
-    DevBuf fd_tw, fd_cf, fd_part, fd_in, fd_len, fd_pos, fd_out;
-    int fd_tw_n = 0;
-    std::vector<double> h_fd_cf;
-    // sub-band power (gsmcal_subband_power_batch*): workspaces of its own again.  sb_taps: one modulated tap row per distinct
-    // phase_rotate value, built on the host (h_sb_coef / h_sb_w: what the rows on the device were built from); sb_idx: the
-    // [capture][slot] table into them (h_sb_idx: its host copy, uploaded only when it changes)
-    DevBuf sb_taps, sb_idx, sb_state, sb_part, sb_raw, sb_out;
-    std::vector<double> h_sb_coef, h_sb_w, h_sb_rows;
+    // host copies of the add-on caches (upload_if_changed); h_sb_coef / h_sb_w: what the rows in sb_taps were built from
+    std::vector<double> h_bp_coef, h_fd_cf, h_sb_coef, h_sb_w, h_sb_rows;
     std::vector<int> h_sb_idx;
-    // CW sample-loss check (gsmcal_CW_check, gsmcal_cw_check_batch*): workspaces of its own again.  cw_state: the byte sums;
-    // cw_part / cw_rec: one record per (capture, tile) of the two passes; cw_mean: phase_rotate and status per capture
-    DevBuf cw_state, cw_part, cw_rec, cw_mean, cw_raw, cw_in, cw_out, cw_r;
+    int fd_tw_n = 0;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream
     static constexpr int AG_SLOTS = 4;
@@ -292,6 +309,8 @@ struct ProfScope {
 
 #define CHECK_LAUNCH(c) HIPCHK(c, hipGetLastError())
 
+// (not upload_if_changed below: an upload here bumps ws_epoch / coef_epoch, which gate graph replay and ensure_head(), and a copy
+// that fails keeps its host copy and HIPCHK's error text)
 int upload_cached(gsmcal_ctx* c, DevBuf& b, std::vector<double>& host, const double* src, size_t n) {
     if (host.size() == n && b.p && memcmp(host.data(), src, n * sizeof(double)) == 0) return 0;
     RET_IF(ensure(c, b, n * sizeof(double)));
@@ -300,6 +319,58 @@ int upload_cached(gsmcal_ctx* c, DevBuf& b, std::vector<double>& host, const dou
     if (&host == &c->h_coef) ++c->coef_epoch;
     HIPCHK(c, hipMemcpyAsync(b.p, host.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return 0;
+}
+
+// The caches of the add-on entry points (taps, carrier frequencies, index tables).  upload_host_copy: the host copy goes to the device;
+// if that fails it is forgotten, so that the next call uploads again.  upload_if_changed: `src`, when it differs from the host copy.
+template <class T>
+int upload_host_copy(gsmcal_ctx* c, DevBuf& b, std::vector<T>& host, const char* what) {
+    int rc = ensure(c, b, host.size() * sizeof(T));
+    const hipError_t e = rc < 0 ? hipSuccess : hipMemcpyAsync(b.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { c->err = std::string("hipMemcpyAsync (") + what + "): " + hipGetErrorString(e); rc = GSMCAL_E_HIP; }
+    if (rc < 0) host.clear();
+    return rc;
+}
+template <class T>
+int upload_if_changed(gsmcal_ctx* c, DevBuf& b, std::vector<T>& host, const T* src, size_t n, const char* what) {
+    if (host.size() == n && b.p && memcmp(host.data(), src, n * sizeof(T)) == 0) return 0;
+    host.assign(src, src + n);
+    return upload_host_copy(c, b, host, what);
+}
+
+// The host-buffer wrappers: `bytes` of device staging at `off` in `b`, filled from `up` before the _dev call and / or read back into
+// `down` after it (either may be NULL).  stage_up sizes every buffer before the first copy is enqueued; stage_down leaves the
+// outputs complete on the host.  A copy that fails names its buffer.
+struct Stage { DevBuf* b; const char* name; size_t bytes; const void* up; void* down; size_t off; };
+#define STAGE(buf, bytes, up, down, off) Stage{&c->buf, #buf, bytes, up, down, off}
+template <size_t N>
+int stage_copies(gsmcal_ctx* c, const Stage (&io)[N], bool to_host) {
+    for (const Stage& s : io) {
+        char* dev = (char*)s.b->p + s.off;
+        hipError_t e = hipSuccess;
+        if (to_host && s.down) e = hipMemcpyAsync(s.down, dev, s.bytes, hipMemcpyDeviceToHost, c->stream);
+        if (!to_host && s.up) e = hipMemcpyAsync(dev, s.up, s.bytes, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { c->err = std::string("hipMemcpyAsync (") + (to_host ? "from " : "to ") + s.name + "): " + hipGetErrorString(e); return GSMCAL_E_HIP; }
+    }
+    return 0;
+}
+template <size_t N>
+int stage_up(gsmcal_ctx* c, const Stage (&io)[N]) {
+    for (const Stage& s : io) RET_IF(ensure(c, *s.b, s.off + s.bytes));
+    return stage_copies(c, io, false);
+}
+template <size_t N>
+int stage_down(gsmcal_ctx* c, const Stage (&io)[N], bool sync = true) {
+    RET_IF(stage_copies(c, io, true));
+    if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// exactly mirrored taps (what fir1 and the .fda designs return): the kernels with half the multiplications apply
+bool taps_symmetric(const double* coef, int ntaps) {
+    for (int k = 0; k < ntaps / 2; ++k)
+        if (coef[k] != coef[ntaps - 1 - k]) return false;
+    return true;
 }
 
 struct Geom {  // burst geometry for an oversampling ratio
@@ -487,6 +558,14 @@ void fused_gate_rollback(gsmcal_ctx* c, int streams) {
     if (c->n_fused_launches > 0) --c->n_fused_launches;
 }
 
+// Is the caller capturing the context's stream (our own capture is `c->capturing`), or can the runtime not tell?  Clears the probe's error.
+bool stream_capturing(gsmcal_ctx* c) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return false;
+    (void)hipGetLastError();
+    return true;
+}
+
 // May context c enqueue a fused tail over `streams` streams now?  false: take the four-launch tail.
 bool fused_gate_enter(gsmcal_ctx* c, int streams) {
     if (c->capturing) {
@@ -496,9 +575,7 @@ bool fused_gate_enter(gsmcal_ctx* c, int streams) {
         c->capture_fused_streams = streams;
         return true;
     }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (c->stream && (hipStreamIsCapturing(c->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)) {
-        (void)hipGetLastError();                          // the CALLER is capturing: the library will not see the replays -- never fuse
+    if (c->stream && stream_capturing(c)) {                // the CALLER is capturing: the library will not see the replays -- never fuse
         ++c->n_gate_fallbacks;
         return false;
     }
@@ -580,9 +657,7 @@ int run_fine(gsmcal_ctx* c, int S, const Source& src, int lvl, const Geom& g, in
             if ((per + src.ntaps + 14) / 8 + 1 <= fc_thr && fc_stage_bytes(per, src.ntaps) <= avail) {
                 fg.raw = src.raw; fg.raw_stride = src.raw_stride; fg.coef = src.coef; fg.win_out = win;
                 fg.ntaps = src.ntaps; fg.per = per;
-                bool sym = src.ntaps == 47 && (int)c->h_coef.size() == 47;
-                for (int k = 0; sym && k < 23; ++k) sym = c->h_coef[k] == c->h_coef[46 - k];
-                fg.sym47 = sym ? 1 : 0;
+                fg.sym47 = src.ntaps == 47 && (int)c->h_coef.size() == 47 && taps_symmetric(c->h_coef.data(), 47) ? 1 : 0;
                 break;
             }
         }
@@ -796,13 +871,33 @@ int init_states(gsmcal_ctx* c, int S, long n0) {
     return 0;
 }
 
+// Exact byte sums of S captures of n samples into st[0 .. S): k_dc_sum, 2 048 sixteen-byte words per block, at most 4 096 blocks in all
+void launch_dc_sums(gsmcal_ctx* c, const uint8_t* d_raw, int S, long n, StreamState* st) {
+    const int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));
+    LAUNCH(c, k_dc_sum, dim3(std::max(1, std::min(blocks, std::max(1, 4096 / std::max(S, 1)))), S), dim3(256), 0, d_raw, 2 * n, st);
+}
+
+// A launch takes at most GRID_Y_MAX captures (one per grid row): f(lo, S) for captures [lo, lo + S) of a batch of d
+constexpr long GRID_Y_MAX = 65535;
+template <class F>
+void for_capture_chunks(int d, F f) {
+    for (long lo = 0; lo < d; lo += GRID_Y_MAX) f(lo, (int)std::min(GRID_Y_MAX, (long)d - lo));
+}
+
+// Kept rows per block of the band-power / sub-band-power kernels: enough for a span of ~BP_SPAN samples (small decimations: several
+// rows per lane), at most what BP_LDS_BYTES admits next to the `fixed` bytes of taps (lds(rows): the kernel's LDS at that tiling).
+template <class F>
+int kept_rows(int decim, int ntaps, size_t fixed, F lds) {
+    int rows = (int)std::min<long>(BP_MAX_ROWS, std::max<long>(BP_ROWS, (BP_SPAN / decim) / BP_ROWS * BP_ROWS));
+    if (lds(rows) > BP_LDS_BYTES) {
+        const long fit = ((long)(BP_LDS_BYTES - fixed) / 2 - 8 - 24 - ntaps) / decim + 1;
+        rows = (int)std::max(1L, std::min<long>(rows, fit));
+    }
+    return rows;
+}
+
 int dc_means(gsmcal_ctx* c, const uint8_t* d_raw, int S, long n) {
-    int blocks = (int)((2 * n / 16 + 256 * 8 - 1) / (256 * 8));
-    if (blocks < 1) blocks = 1;
-    int cap = 4096 / (S > 0 ? S : 1);
-    if (cap < 1) cap = 1;
-    if (blocks > cap) blocks = cap;
-    LAUNCH(c, k_dc_sum, dim3(blocks, S), dim3(256), 0, d_raw, 2 * n, (StreamState*)c->cur->state.p);
+    launch_dc_sums(c, d_raw, S, n, (StreamState*)c->cur->state.p);
     LAUNCH(c, k_finish_mean, dim3((S + 63) / 64), dim3(64), 0, (StreamState*)c->cur->state.p, S, n);
     CHECK_LAUNCH(c);
     return 0;
@@ -851,8 +946,7 @@ int front_fused(gsmcal_ctx* c, const uint8_t* d_raw, int S, long n, const double
     c->last_S = S_all;
     d_raw += (size_t)s_off * 2 * n;
     d_out += (size_t)s_off * out_stride;
-    bool sym = (int)c->h_coef.size() == ntaps;                 // linear-phase taps? (fir1 and the .fda designs are)
-    for (int k = 0; sym && k < ntaps / 2; ++k) sym = c->h_coef[k] == c->h_coef[ntaps - 1 - k];
+    const bool sym = (int)c->h_coef.size() == ntaps && taps_symmetric(c->h_coef.data(), ntaps);
     if ((ntaps == 47 || ntaps == 31) && decim == 64 && ((uintptr_t)d_raw & 15) == 0 && ((2 * n) & 15) == 0 &&
         !c->front_generic) {
         // the production geometries (fir1(46) / fir1(30), 8x oversampling, aligned captures): rows in registers
@@ -1182,6 +1276,44 @@ int pipe_drain(gsmcal_ctx* c) {
     return pipe_join(c);
 }
 
+// May this batch call of d units go in flight?  One-lane calls at depth > 1, unless events sit on every dispatch
+// (gsmcal_profile_enable) or the caller is capturing the context's stream.  *wanted: depth and batch size alone would have let it.
+bool pipe_may_fly(gsmcal_ctx* c, int d, bool latency_bound, bool* wanted = nullptr) {
+    const bool want = c->pipe_depth > 1 && c->stream != nullptr && plan_lanes(c, d, latency_bound) == 1;
+    if (wanted) *wanted = want;
+    return want && !c->prof && !stream_capturing(c);
+}
+
+// One call in flight: slot = workspace and stream of this call.  The context's stream first waits for the call that used the slot
+// `depth` calls ago (that call's outputs are complete in the context's stream order from here on), then the slot's stream takes
+// `body(L)` -- which enqueues on c->cur = &L and returns a status -- behind whatever the context's stream holds now.  Whatever the
+// body returns, the slot is released: its end recorded and pending, the context back on lane 0 with nothing of a call being
+// enqueued left set; after an error the calls in flight are drained as well.  (The lane fields are set before side_in is recorded,
+// as the calibration call had it; the scanner set them behind it.  The HIP calls and their order are those of both.)
+template <class F>
+int pipe_call(gsmcal_ctx* c, int d, F body) {
+    RET_IF(pipe_prepare(c));
+    const int slot = (int)(c->pipe_calls % (unsigned long)c->pipe_depth);
+    Lane& L = c->pipe[slot];
+    L.stream = c->side_stream[slot]; L.lo = 0; L.n = d;
+    c->cur = &L; c->n_lanes_used = 1;
+    int rc = [&]() -> int {
+        if (c->pipe_pending[slot]) {
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->pipe_done[slot], 0));
+            c->pipe_pending[slot] = false;
+        }
+        HIPCHK(c, hipEventRecord(c->side_in[slot], c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->side_stream[slot], c->side_in[slot], 0));
+        return body(L);
+    }();
+    c->cf_lane = nullptr; c->no_fuse_now = false;
+    if (hipEventRecord(c->pipe_done[slot], L.stream) != hipSuccess) { c->err = "hipEventRecord (calls in flight)"; rc = GSMCAL_E_HIP; }
+    c->pipe_pending[slot] = true; c->pipe_last_slot = slot; ++c->pipe_calls;
+    c->detail_lane = &L; c->cur = &c->lanes[0]; c->last_S = d;
+    if (rc < 0) { (void)pipe_drain(c); return rc; }
+    return 0;
+}
+
 #define ENTER(c)                                   \
     do {                                           \
         HIPCHK(c, hipSetDevice((c)->device));      \
@@ -1200,7 +1332,7 @@ int run_maybe_graph(gsmcal_ctx* c, gsmcal_ctx::GraphSlot& slot, const std::vecto
     // 64 streams, 0.125 vs 0.129 at 2, 0.101 vs 0.107 for 200 captures).  Plans that fork onto internal streams replay as a
     // graph: the event choreography costs more launched piecemeal (12 800 captures: 4.06 vs 4.33 ms).  GSMCAL_GRAPH=2: always.
     bool can_graph = c->use_graph && (multi_stream || c->graph_always) && !c->prof && c->stream != nullptr;
-    if (can_graph) {
+    if (can_graph) {     // (not stream_capturing(): a caller's capture in progress is no error here, and no error state is cleared for it)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); can_graph = false; }
         else if (cs != hipStreamCaptureStatusNone) can_graph = false;       // the caller is capturing: just enqueue
