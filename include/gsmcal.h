@@ -48,6 +48,7 @@ enum {
     GSMCAL_S_POST_NO_POS = 10,    /* carrier_correct_post_SCH.m:10-13                             */
     GSMCAL_S_POST_FEW_BCCH = 11,  /* carrier_correct_post_SCH.m:15-19                             */
     GSMCAL_S_ALL_INF = 12,        /* total_ppm_calculation.m:7-11                                 */
+    GSMCAL_S_BCCH_TSC_MIXED = 13, /* BCCH_demod.m:103-105: the first four BCCH bursts disagree     */
     /* < 0: failures */
     GSMCAL_E_ARG = -1,
     GSMCAL_E_HIP = -2,
@@ -61,6 +62,8 @@ enum {
 #define GSMCAL_MAX_POS_ROWS (6 * GSMCAL_MAX_HITS)
 #define GSMCAL_TABLE_COLS 10
 #define GSMCAL_DEMOD_COLS (4 + 3 * GSMCAL_MAX_HITS)   /* one row of gsmcal_fcch_demod_batch[_dev]: 76 doubles */
+#define GSMCAL_MAX_BCCH (4 * GSMCAL_MAX_HITS)         /* BCCH bursts (type-2 rows of pos_info) gsmcal_bcch_demod_batch evaluates */
+#define GSMCAL_BCCH_COLS (6 + 4 * GSMCAL_MAX_BCCH)    /* one row of gsmcal_bcch_demod_batch[_dev]: 390 doubles */
 
 /* columns of one row of the calibration table (doubles; this row is what ranks all-gather) */
 enum {
@@ -85,6 +88,20 @@ enum {
     GSMCAL_D_FREQ = 4,                              /* [GSMCAL_MAX_HITS] tone frequency per burst :42             */
     GSMCAL_D_SNR = 4 + GSMCAL_MAX_HITS,             /* [GSMCAL_MAX_HITS] in-band SNR, dB          :62             */
     GSMCAL_D_MAX_IDX = 4 + 2 * GSMCAL_MAX_HITS      /* [GSMCAL_MAX_HITS] max_idx - (fft_len/2+1)  :66             */
+};
+
+/* columns of one row of the BCCH_demod table (doubles) */
+enum {
+    GSMCAL_B_NUM_BCCH = 0,                          /* type-2 rows of pos_info (0 at GSMCAL_S_POST_NO_POS)    BCCH_demod.m:13  */
+    GSMCAL_B_TSC_IDX = 1,                           /* normal_training_sequence_idx: 1..8, or -1              :102             */
+    GSMCAL_B_MEAN_FO = 2,                           /* mean(fo) of the FCCH bursts, NaN without one           :70              */
+    GSMCAL_B_CARRIER_PPM = 3,                       /* 1e6*(fo - symbol_rate/4)/carrier_freq                  :71              */
+    GSMCAL_B_STATUS = 4,                            /* 0, GSMCAL_S_POST_NO_POS, _S_POST_FEW_BCCH, _S_BCCH_TSC_MIXED, _E_CAPACITY, _E_INDEX */
+    GSMCAL_B_NUM_AGREE = 5,                         /* evaluated bursts whose idx equals the first burst's                     */
+    GSMCAL_B_IDX = 6,                               /* [GSMCAL_MAX_BCCH] first maximum of |corr_val| per burst, 1..8  :99      */
+    GSMCAL_B_PEAK = 6 + GSMCAL_MAX_BCCH,            /* [GSMCAL_MAX_BCCH] |corr_val| of the winner                              */
+    GSMCAL_B_RUNNER_UP = 6 + 2 * GSMCAL_MAX_BCCH,   /* [GSMCAL_MAX_BCCH] the second largest |corr_val|                         */
+    GSMCAL_B_PHASE = 6 + 3 * GSMCAL_MAX_BCCH        /* [GSMCAL_MAX_BCCH] angle of the winning correlation                      */
 };
 
 /* ---- algorithm thresholds (the constants the reference hard-codes inside its functions) ---------- */
@@ -144,7 +161,7 @@ const char* gsmcal_last_error(gsmcal_ctx* ctx);
  * SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79) -- and a MEX file that shadows one
  * would otherwise run silent.  After gsmcal_FCCH_coarse_position / _FCCH_fine_correction / _SCH_corr_rate_correction /
  * _carrier_correct_post_SCH this returns the lines that call's .m file would have printed, '\n'-separated, numbers formatted as
- * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  gsmcal_FCCH_demod leaves its lines too.  buf may be NULL; the return value is the
+ * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  gsmcal_FCCH_demod and gsmcal_BCCH_demod leave their lines too.  buf may be NULL; the return value is the
  * text's length without the terminator.  The gateway mexPrintf()s it; the Python mirror prints it when GSMCAL_VERBOSE=1. */
 long gsmcal_last_call_report(gsmcal_ctx* ctx, char* buf, size_t cap);
 long gsmcal_num2str(const double* x, int n, char* buf, size_t cap);
@@ -319,6 +336,28 @@ int gsmcal_FCCH_demod(gsmcal_ctx* ctx, const double* s, long len, const double* 
                       int oversampling_ratio, double carrier_freq, double* freq, double* snr, double* max_idx, int cap,
                       int* num_fcch, double* mean_freq, double* carrier_ppm);
 
+/* [normal_training_sequence_idx, r, carrier_ppm] = BCCH_demod(s,pos_info,normal_training_sequence,ov,carrier_freq)   BCCH_demod.m
+ * Which of the eight GSM normal training sequences the BCCH bursts carry -- the cell's base-station colour code.  The .m file uses
+ * two names it does not define: carrier_freq (:71), the argument every sibling function takes and the fifth one here, and
+ * normal_training_sequence (:97), its third parameter: 26*ov x 8 complex as gsm_normal_training_sequence_gen returns it, passed
+ * column by column ([8][len_ts] complex, len_ts = 26*ov; any other len_ts: GSMCAL_E_ARG, MATLAB's inner dimensions would disagree).
+ * :49-72 the tone estimate of every FCCH row (type 0), fo = mean, carrier_ppm -- the estimator of gsmcal_FCCH_demod; :74-76
+ * r = s .* exp(1i*(0:len-1)'*comp_phase_rotate); :84-97 for the first four BCCH rows (type 2, start p) the window r(p+61*ov :
+ * p+87*ov-1) against the conjugated templates; :99-106 the first maximum of |corr_val| per burst: all four equal gives *idx = 1..8
+ * and status 0, otherwise *idx = -1 and GSMCAL_S_BCCH_TSC_MIXED -- r and carrier_ppm are valid then, the .m file has them by :76.
+ * pos_info all -1 (:9): GSMCAL_S_POST_NO_POS; fewer than 4 type-2 rows (:14): GSMCAL_S_POST_FEW_BCCH -- the literal 4 of :14 and
+ * :80, not gsmcal_params.post_min_bcch: num_bcch_used = 4 rows are read unconditionally afterwards.  Both leave *idx = -1,
+ * *len_r = -1 and *carrier_ppm = -1, the values of :6-8.  No type-0 row: mean([]) = NaN, r, corr_val and carrier_ppm are NaN and
+ * *idx = -1 with GSMCAL_S_BCCH_TSC_MIXED (MATLAB's max over an all-NaN column answers 1, a number without a meaning).
+ * An FCCH window or one of the four BCCH windows outside the stream: GSMCAL_E_INDEX, decided before a sample is read.
+ * r (may be NULL): cap_r complex, *len_r = len written; must not overlap s (GSMCAL_E_ARG).  corr_val (may be NULL): the 8 x 4
+ * matrix of :97, column-major.  table_row (may be NULL): GSMCAL_BCCH_COLS doubles, the row gsmcal_bcch_demod_batch writes for
+ * this stream -- every type-2 row evaluated, not only four.  gsmcal_last_call_report then returns the lines of :15, :69, :72 and
+ * :101 or :104.  oversampling_ratio as for gsmcal_FCCH_demod. */
+int gsmcal_BCCH_demod(gsmcal_ctx* ctx, const double* s, long len, const double* pos_info, int rows, int ld,
+                      const double* normal_training_sequence, int len_ts, int oversampling_ratio, double carrier_freq,
+                      int* idx, double* r, long cap_r, long* len_r, double* carrier_ppm, double* corr_val, double* table_row);
+
 /* ppm_out = total_ppm_calculation(ppm_in)                           total_ppm_calculation.m:5-21
  * (pure host arithmetic; no context needed) */
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out);
@@ -443,6 +482,27 @@ int gsmcal_fcch_demod_batch(gsmcal_ctx* ctx, const double* r, long stride, const
                             int oversampling_ratio, const double* carrier_freq, double* out);
 int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
                                 int d, int oversampling_ratio, const double* carrier_freq, double* d_out);
+
+/* BCCH_demod for D streams, on the same inputs as gsmcal_fcch_demod_batch[_dev] plus the templates (host, [8][len_ts] complex,
+ * len_ts = 26*ov) and carrier_freq (host [D]).  out: [D][GSMCAL_BCCH_COLS], row = {num_bcch, tsc_idx, mean_fo, carrier_ppm, status,
+ * num_agree, idx[], peak[], runner_up[], phase[]} (GSMCAL_B_*): EVERY type-2 row is evaluated, up to GSMCAL_MAX_BCCH, the decision
+ * is the reference's on the first four; num_agree counts the evaluated rows whose idx equals the first row's; unused entries NaN.
+ * A row beyond the fourth whose window leaves the stream is NaN and no error: the reference never reads it.  Per-row outcomes go
+ * in the status column: GSMCAL_S_POST_NO_POS (r_len = -1 or an all -1 pos_info; num_bcch 0), GSMCAL_S_POST_FEW_BCCH,
+ * GSMCAL_S_BCCH_TSC_MIXED (mean_fo and carrier_ppm valid), GSMCAL_E_CAPACITY (more than GSMCAL_MAX_BCCH type-2 or GSMCAL_MAX_HITS
+ * type-0 rows), GSMCAL_E_INDEX; in all but MIXED tsc_idx is -1 and mean_fo, carrier_ppm, num_agree are NaN.
+ * Optional outputs (NULL to skip): corr [D][GSMCAL_MAX_BCCH][8] complex, the correlations of :97 (NaN where none was formed);
+ * r_out [D][stride] complex with r_len_out [D] (both or neither): the rotated stream of :76 and its length, -1 wherever the
+ * reference leaves r = -1 or stops (the _dev form leaves those rows of r_out untouched, the host form returns them as zeros).  r_out must not overlap r: GSMCAL_E_ARG.
+ * A row is bit-identical alone, at any position of a batch, and equal to what gsmcal_BCCH_demod returns.  _dev: device pointers,
+ * only enqueues on the context's stream; the calls share gsmcal_fcch_demod_batch's workspace and leave the lanes and every answer
+ * about the calibrate / scan call before untouched. */
+int gsmcal_bcch_demod_batch(gsmcal_ctx* ctx, const double* r, long stride, const long* r_len, const double* pos_info, int d,
+                            int oversampling_ratio, const double* normal_training_sequence, int len_ts,
+                            const double* carrier_freq, double* out, double* corr, double* r_out, long* r_len_out);
+int gsmcal_bcch_demod_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
+                                int d, int oversampling_ratio, const double* normal_training_sequence, int len_ts,
+                                const double* carrier_freq, double* d_out, double* d_corr, double* d_r_out, long* d_r_len_out);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,

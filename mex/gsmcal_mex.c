@@ -7,7 +7,7 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
+ *            carrier_correct_post_SCH FCCH_demod BCCH_demod CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
  *            gsmcal_band_power gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
@@ -266,6 +266,36 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (k = 0; k < (mwSize)nb; ++k) REAL_PTR(plhs[i])[k] = v[i * GSMCAL_MAX_HITS + k];
     }
     if (nlhs > 3) plhs[3] = scalar(cp);
+
+#elif defined(GSMCAL_FN_BCCH_demod)
+    /* [normal_training_sequence_idx, r, carrier_ppm, corr_val] = BCCH_demod(s,pos_info,normal_training_sequence,ov,carrier_freq)
+     * BCCH_demod.m with the two names it leaves undefined as arguments: carrier_freq (:71) is the fifth, the templates of
+     * gsm_normal_training_sequence_gen(ov) (26*ov x 8 complex, :97) the third.  Prints the lines of :15,69,72,101,104; the three
+     * outputs are the variables of :6-8 (-1 at the :9 and :14 exits), corr_val the 8 x 4 matrix of :97 (empty at those exits). */
+    mwSize n = 0, nt = 0;
+    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    const double* ts;
+    int rows = (int)mxGetM(prhs[1]), idx = -1, rc;
+    double cp = -1.0; long lr = -1;
+    double* r = n ? (double*)mxMalloc(2 * n * sizeof(double)) : NULL;
+    cplx_out cv;
+    double* cvb;
+    if (nrhs < 5 || mxGetN(prhs[2]) != 8)
+        mexErrMsgIdAndTxt("gsmcal:args", "usage: [idx, r, carrier_ppm] = BCCH_demod(s, pos_info, normal_training_sequence, ov, carrier_freq)");
+    ts = cplx_in(prhs[2], &nt);
+    cvb = cplx_out_begin(&cv, 8, 4);
+    rc = gsmcal_BCCH_demod(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, ts, (int)mxGetM(prhs[2]), (int)mxGetScalar(prhs[3]),
+                           mxGetScalar(prhs[4]), &idx, r, (long)n, &lr, &cp, cvb, NULL);
+    chk(rc, "BCCH_demod");
+    say();
+    plhs[0] = scalar((double)idx);
+    if (nlhs > 1) plhs[1] = lr < 0 ? scalar(-1.0) : cplx_col(r, (mwSize)lr);
+    if (nlhs > 2) plhs[2] = scalar(cp);
+    {
+        mxArray* m = cplx_out_end(&cv);
+        if (nlhs > 3) plhs[3] = rc == GSMCAL_S_POST_NO_POS || rc == GSMCAL_S_POST_FEW_BCCH ? mxCreateDoubleMatrix(0, 0, mxREAL) : m;
+    }
+    if (r) mxFree(r);
 
 #elif defined(GSMCAL_FN_CW_check)
     /* r = CW_check(s)     CW_check.m:6-8: s a complex vector of N >= 2 samples (raw2iq's output, check_CW_samples_loss_tcp.m:70,

@@ -22,6 +22,9 @@ CW_COLS = 5 + 2 * CW_MAX_EVENTS    # one row of cw_check_batch: phase_rotate, co
 CW_TILE = 2048                     # ratios per workgroup of the CW check (GSMCAL_CW_TILE)
 CW_OK, CW_SHORT, CW_ZERO = 0, 1, 2
 DEMOD_COLS = 4 + 3 * MAX_HITS      # one row of fcch_demod_batch: num_fcch, mean_freq, carrier_ppm, status, freq[], snr[], max_idx[]
+MAX_BCCH = 4 * MAX_HITS            # BCCH bursts per stream bcch_demod_batch evaluates (GSMCAL_MAX_BCCH)
+BCCH_COLS = 6 + 4 * MAX_BCCH       # one row of bcch_demod_batch: six scalars (api.BCCH_FIELDS), then idx[], peak[], runner_up[], phase[]
+S_POST_NO_POS, S_POST_FEW_BCCH, S_BCCH_TSC_MIXED = 10, 11, 13
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -69,6 +72,12 @@ SIGNATURES = {
                                           c_double_p, c_double_p]),
     "gsmcal_fcch_demod_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                               c_double_p, C.c_void_p]),
+    "gsmcal_BCCH_demod": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_double_p, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int,
+                                    C.c_double, c_int_p, c_double_p, C.c_long, c_long_p, c_double_p, c_double_p, c_double_p]),
+    "gsmcal_bcch_demod_batch": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_long_p, c_double_p, C.c_int, C.c_int, c_double_p,
+                                          C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_long_p]),
+    "gsmcal_bcch_demod_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_double_p,
+                                              C.c_int, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsmcal_total_ppm_calculation": (C.c_int, [c_double_p, C.c_int, c_double_p]),
     "gsmcal_frontend_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                         c_double_p]),

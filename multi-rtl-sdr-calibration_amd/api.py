@@ -15,6 +15,7 @@ sentinel returns (scalar -1.0 / inf, pos_info = [[-1, -1]]) so that tests read l
     [pos_info,r,sampling_ppm] = SCH_corr_rate_correction(s,FCCH_pos,sch_training_sequence,ov)
     [r,carrier_ppm] = carrier_correct_post_SCH(s,pos_info,ov,carrier_freq)
     FCCH_demod(s,pos_info,ov,carrier_freq)                           FCCH_demod.m:5 (what it prints, returned as a dict)
+    [idx,r,carrier_ppm] = BCCH_demod(s,pos_info,normal_training_sequence,ov,carrier_freq)     BCCH_demod.m:5 (a dict)
     ppm_out = total_ppm_calculation(ppm_in)
 
 Everything computes on the GPU through the C ABI; there is no CPU fallback.
@@ -28,7 +29,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -421,6 +422,48 @@ def FCCH_demod(s, pos_info, oversampling_ratio, carrier_freq, ctx=None):
     return {"freq": freq[:k], "snr": snr[:k], "max_idx": idx[:k].astype(np.int64), "mean_freq": mf.value, "carrier_ppm": cp.value}
 
 
+def _templates_in(normal_training_sequence, oversampling_ratio):
+    """(len_ts, 8) complex as gsm_normal_training_sequence_gen returns it -> (buf, len_ts): the columns one after the other"""
+    t = np.asarray(normal_training_sequence, dtype=np.complex128)
+    if t.ndim != 2 or t.shape[1] != 8:
+        raise ValueError("normal_training_sequence must be (26*oversampling_ratio, 8)")
+    return np.ascontiguousarray(t.T), t.shape[0]
+
+
+def BCCH_demod(s, pos_info, normal_training_sequence, oversampling_ratio, carrier_freq, ctx=None, want_r=True):
+    """[normal_training_sequence_idx, r, carrier_ppm] = BCCH_demod(s, pos_info, normal_training_sequence, ov, carrier_freq) --
+    BCCH_demod.m with the two names it leaves undefined as arguments (include/gsmcal.h): which of the eight normal training
+    sequences (synth.normal_training_sequences(ov), (26*ov, 8)) the BCCH bursts of pos_info carry.  Returns None at the :9 exit
+    (pos_info all -1), otherwise a dict: `idx` (1..8, or -1), `r` (the stream rotated at :76; -1.0 where the .m file leaves it, or
+    with want_r=False), `carrier_ppm`, `status` (0, 11 = fewer than 4 BCCH bursts, 13 = the first four disagree), `corr_val` (8, 4)
+    -- and, for every type-2 row, not only four: `num_bcch`, `mean_fo`, `num_agree`, `max_idx`, `peak`, `runner_up`, `phase`;
+    `row` is the (BCCH_COLS,) table row bcch_demod_batch holds for this stream."""
+    ctx = ctx or default_context()
+    buf, n = _r_in(s)
+    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
+    rows = pi.shape[0]
+    pic = np.ascontiguousarray(pi.T)
+    ts, len_ts = _templates_in(normal_training_sequence, oversampling_ratio)
+    r = np.empty(n, dtype=np.complex128) if want_r and n > 0 else None
+    idx, lr, cp = C.c_int(), C.c_long(), C.c_double()
+    corr = np.full((4, 8), np.nan + 0j)
+    row = np.full(BCCH_COLS, np.nan)
+    rc = ctx.check(ctx.lib.gsmcal_BCCH_demod(ctx.h, _dp(buf) if buf is not None else None, n, _dp(pic), rows, rows, _dp(ts), len_ts,
+                                             int(oversampling_ratio), float(carrier_freq), C.byref(idx), _dp(r) if r is not None else None,
+                                             n, C.byref(lr), C.byref(cp), _dp(corr), _dp(row)), "BCCH_demod")
+    _say(ctx)
+    if rc == _lib.S_POST_NO_POS:
+        return None
+    out = {"idx": idx.value, "r": r if r is not None and lr.value > 0 else -1.0, "carrier_ppm": cp.value, "status": rc,
+           "corr_val": corr.T.copy() if rc != _lib.S_POST_FEW_BCCH else None}
+    t = bcch_rows(row)
+    k = int(t["num_bcch"][0])
+    out.update(num_bcch=k, mean_fo=float(t["mean_fo"][0]), num_agree=t["num_agree"][0], row=row)
+    for name in ("max_idx", "peak", "runner_up", "phase"):
+        out[name] = t[name][0, :min(k, MAX_BCCH)].copy()
+    return out
+
+
 def total_ppm_calculation(ppm_in):
     lib = _lib.load()
     p = np.ascontiguousarray(np.atleast_1d(np.asarray(ppm_in, dtype=np.float64)))
@@ -599,6 +642,61 @@ def fcch_demod_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio
     ctx.check(ctx.lib.gsmcal_fcch_demod_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
                                                   int(d), int(oversampling_ratio), _dp(cf), C.c_void_p(d_out)),
               "fcch_demod_batch_dev")
+
+
+BCCH_FIELDS = ("num_bcch", "tsc_idx", "mean_fo", "carrier_ppm", "status", "num_agree")   # columns 0..5 of a BCCH_demod row
+
+
+def bcch_rows(table):
+    """(D, BCCH_COLS) table of bcch_demod_batch[_dev] -> dict of its columns (max_idx, peak, runner_up, phase: (D, MAX_BCCH), NaN
+    unused; max_idx is the 1-based winning template per burst)."""
+    t = np.asarray(table).reshape(-1, BCCH_COLS)
+    out = {k: t[:, i] for i, k in enumerate(BCCH_FIELDS)}
+    out["max_idx"], out["peak"], out["runner_up"], out["phase"] = (t[:, 6 + j * MAX_BCCH: 6 + (j + 1) * MAX_BCCH] for j in range(4))
+    return out
+
+
+def bcch_demod_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, normal_training_sequence, carrier_freq, ctx=None,
+                     want_corr=False, want_r=False):
+    """BCCH_demod.m for D streams, on what calibrate_batch(..., want_r=True) returns (as fcch_demod_batch) plus the (26*ov, 8)
+    templates.  Returns the (D, BCCH_COLS) table (bcch_rows names its columns; per-row outcomes are in its status column) -- or,
+    with want_corr / want_r, a dict: "table", "corr" (D, MAX_BCCH, 8) complex, "r" (D, N) complex and "r_len" (D,), -1 where the
+    reference leaves r = -1 (those rows of "r" are zeros)."""
+    ctx = ctx or default_context()
+    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
+    d, stride = r.shape
+    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
+    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
+    if len(rl) != d:
+        raise ValueError("r_len must have one entry per stream")
+    ts, len_ts = _templates_in(normal_training_sequence, oversampling_ratio)
+    cf = np.ascontiguousarray(np.broadcast_to(np.asarray(carrier_freq, dtype=np.float64), (d,)))
+    out = np.empty((d, BCCH_COLS))
+    corr = np.empty((d, MAX_BCCH, 8), dtype=np.complex128) if want_corr else None
+    ro = np.empty((d, stride), dtype=np.complex128) if want_r else None
+    rlo = np.empty(d, dtype=np.int64) if want_r else None
+    ctx.check(ctx.lib.gsmcal_bcch_demod_batch(ctx.h, _dp(r), stride, rl.ctypes.data_as(_lib.c_long_p), _dp(pi), d,
+                                              int(oversampling_ratio), _dp(ts), len_ts, _dp(cf), _dp(out),
+                                              _dp(corr) if want_corr else None, _dp(ro) if want_r else None,
+                                              rlo.ctypes.data_as(_lib.c_long_p) if want_r else None), "bcch_demod_batch")
+    if not (want_corr or want_r):
+        return out
+    return {"table": out, "corr": corr, "r": ro, "r_len": rlo}
+
+
+def bcch_demod_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio, normal_training_sequence, carrier_freq, d_out,
+                         d_corr=None, d_r_out=None, d_r_len_out=None, ctx=None):
+    """Device-pointer form of bcch_demod_batch: only enqueues on the context's stream, e.g. directly behind calibrate_batch_dev on
+    its d_r_correct / d_r_len / d_pos_info (ctx.sync() before reading).  d_out: [d][BCCH_COLS] doubles; optional d_corr:
+    [d][MAX_BCCH][8] complex; d_r_out [d][stride] complex with d_r_len_out [d] int64 (both or neither; d_r_out must not overlap
+    d_r).  Device or pinned host memory."""
+    ctx = ctx or default_context()
+    ts, len_ts = _templates_in(normal_training_sequence, oversampling_ratio)
+    cf = np.ascontiguousarray(np.broadcast_to(np.asarray(carrier_freq, dtype=np.float64), (int(d),)))
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(ctx.lib.gsmcal_bcch_demod_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
+                                                  int(d), int(oversampling_ratio), _dp(ts), len_ts, _dp(cf), C.c_void_p(d_out),
+                                                  opt(d_corr), opt(d_r_out), opt(d_r_len_out)), "bcch_demod_batch_dev")
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

@@ -687,14 +687,13 @@ int gsmcal_SCH_equalise(gsmcal_ctx* c, const double* s, long len, const double* 
 // ---- FCCH_demod.m:5-66: the check behind the calibration ------------------------------------------------------
 // k_fcch_demod (one workgroup per burst slot and stream) + k_fcch_demod_finish (one wave per stream) on the context's stream;
 // nothing of the lanes, the shared taps or the state of the calibrate / scan call before is touched.
-int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
-                                int ov, const double* carrier_freq, double* d_out) {
-    if (!c || !d_r || !d_r_len || !d_pos_info || !carrier_freq || !d_out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
-    if (ov > 256) return GSMCAL_E_UNSUPPORTED;
+// The per-burst half, which gsmcal_bcch_demod_batch_dev runs too (BCCH_demod.m:49-68 is the same block): fd_part[d][MAXH][FD_PART]
+// and the carrier frequencies in fd_cf.  The caller has checked its arguments and the oversampling ratio (fcch_demod_ov_ok).
+static bool fcch_demod_ov_ok(int ov) { return ov <= 256 && fd_lds_bytes(148 * ov) <= 159 * 1024; }
+static int fcch_demod_parts(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d, int ov,
+                     const double* carrier_freq) {
     const int nfft = 148 * ov;                                  // FCCH_demod.m:13-16
     const size_t lds = fd_lds_bytes(nfft);
-    if (lds > 159 * 1024) return GSMCAL_E_UNSUPPORTED;
-    ENTER(c);
     c->cur = &c->lanes[0];                                      // the context's stream; the lane's buffers are not touched
     const double fs = GSM_SYMBOL_RATE * (double)ov;             // :30-31
     const int hnl = (int)ceil(((double)nfft * 200e3 / fs) / 2.0);   // :53 half_noise_len (55 for every ov)
@@ -710,7 +709,16 @@ int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, c
         LAUNCH(c, k_fcch_demod, dim3(MAXH, S), dim3(FD_THREADS), lds, (const cplx*)d_r + (size_t)lo * stride, stride, d_r_len + lo,
                d_pos_info + (size_t)lo * 2 * MAXROWS, nfft, ov, hnl, (const cplx*)c->fd_tw.p, part + (size_t)lo * MAXH * FD_PART);
     });
-    LAUNCH(c, k_fcch_demod_finish, dim3(d), dim3(64), 0, d_r_len, d_pos_info, (const double*)c->fd_cf.p, (const double*)part, d_out);
+    return 0;
+}
+
+int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
+                                int ov, const double* carrier_freq, double* d_out) {
+    if (!c || !d_r || !d_r_len || !d_pos_info || !carrier_freq || !d_out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    if (!fcch_demod_ov_ok(ov)) return GSMCAL_E_UNSUPPORTED;
+    ENTER(c);
+    RET_IF(fcch_demod_parts(c, d_r, stride, d_r_len, d_pos_info, d, ov, carrier_freq));
+    LAUNCH(c, k_fcch_demod_finish, dim3(d), dim3(64), 0, d_r_len, d_pos_info, (const double*)c->fd_cf.p, (const double*)c->fd_part.p, d_out);
     CHECK_LAUNCH(c);
     return 0;
 }
@@ -761,6 +769,124 @@ int gsmcal_FCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* po
     if (mean_freq) *mean_freq = row[GSMCAL_D_MEAN_FREQ];
     if (carrier_ppm) *carrier_ppm = row[GSMCAL_D_CARRIER_PPM];
     c->report = report_fcch_demod(row.data());
+    return status;
+}
+
+// ---- BCCH_demod.m: the training sequence code of the BCCH bursts ---------------------------------------------------
+// k_fcch_demod (the tone estimates of :49-68), k_bcch_corr (BC_GRID_X workgroups per stream, striding over its BCCH rows),
+// k_bcch_finish (one wave per stream) and, when r is asked for, k_bcch_rotate -- on the context's stream, in FCCH_demod's
+// workspace plus bc_*; nothing of the lanes or of the chain's state is touched.
+int gsmcal_bcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
+                                int ov, const double* nts, int len_ts, const double* carrier_freq, double* d_out, double* d_corr,
+                                double* d_r_out, long* d_r_len_out) {
+    if (!c || !d_r || !d_r_len || !d_pos_info || !nts || !carrier_freq || !d_out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    if (!fcch_demod_ov_ok(ov)) return GSMCAL_E_UNSUPPORTED;
+    if (len_ts != 26 * ov) { c->err = "BCCH_demod: the templates must be 26*oversampling_ratio samples long"; return GSMCAL_E_ARG; }
+    if ((d_r_out != nullptr) != (d_r_len_out != nullptr)) { c->err = "BCCH_demod: r_out and r_len_out go together"; return GSMCAL_E_ARG; }
+    if (d_r_out) {                                              // a stream rotated in place would be read after it was written
+        const uintptr_t a = (uintptr_t)d_r, b = (uintptr_t)d_r_out, bytes = (uintptr_t)d * (uintptr_t)stride * sizeof(cplx);
+        if (a < b + bytes && b < a + bytes) { c->err = "BCCH_demod: r_out overlaps r"; return GSMCAL_E_ARG; }
+    }
+    ENTER(c);
+    RET_IF(fcch_demod_parts(c, d_r, stride, d_r_len, d_pos_info, d, ov, carrier_freq));
+    RET_IF(upload_if_changed(c, c->bc_ts, c->h_bc_ts, nts, (size_t)2 * 8 * len_ts, "BCCH_demod templates"));
+    RET_IF(ensure(c, c->bc_corr, (size_t)d * BC_SLOTS * 8 * sizeof(cplx)));
+    RET_IF(ensure(c, c->bc_flag, (size_t)d * BC_SLOTS * sizeof(int)));
+    const double* part = (const double*)c->fd_part.p;
+    cplx* corr = (cplx*)c->bc_corr.p;
+    int* flag = (int*)c->bc_flag.p;
+    for_capture_chunks(d, [&](long lo, int S) {
+        LAUNCH(c, k_bcch_corr, dim3(BC_GRID_X, S), dim3(BC_THREADS), (size_t)len_ts * sizeof(cplx), (const cplx*)d_r + (size_t)lo * stride,
+               stride, d_r_len + lo, d_pos_info + (size_t)lo * 2 * MAXROWS, ov, (const cplx*)c->bc_ts.p, part + (size_t)lo * MAXH * FD_PART,
+               corr + (size_t)lo * BC_SLOTS * 8, flag + (size_t)lo * BC_SLOTS);
+    });
+    LAUNCH(c, k_bcch_finish, dim3(d), dim3(64), 0, d_r_len, stride, d_pos_info, (const double*)c->fd_cf.p, part, (const cplx*)corr,
+           (const int*)flag, d_out, (cplx*)d_corr, d_r_len_out);
+    if (d_r_out) {
+        const int gx = (int)std::max(1L, std::min(256L, (stride + 2047) / 2048));
+        for_capture_chunks(d, [&](long lo, int S) {
+            LAUNCH(c, k_bcch_rotate, dim3(gx, S), dim3(256), 0, (const cplx*)d_r + (size_t)lo * stride, stride, (const long*)d_r_len_out + lo,
+                   (const double*)d_out + (size_t)lo * GSMCAL_BCCH_COLS, ov, (cplx*)d_r_out + (size_t)lo * stride);
+        });
+    }
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_bcch_demod_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
+                            const double* nts, int len_ts, const double* carrier_freq, double* out, double* corr, double* r_out,
+                            long* r_len_out) {
+    if (!c || !r || !r_len || !pos_info || !nts || !carrier_freq || !out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    if ((r_out != nullptr) != (r_len_out != nullptr)) { c->err = "BCCH_demod: r_out and r_len_out go together"; return GSMCAL_E_ARG; }
+    if (r_out) {
+        const uintptr_t a = (uintptr_t)r, b = (uintptr_t)r_out, bytes = (uintptr_t)d * (uintptr_t)stride * sizeof(cplx);
+        if (a < b + bytes && b < a + bytes) { c->err = "BCCH_demod: r_out overlaps r"; return GSMCAL_E_ARG; }
+    }
+    ENTER(c);
+    const size_t nr = (size_t)d * stride * sizeof(cplx);
+    const Stage io[] = {STAGE(fd_in, nr, r, nullptr, 0),
+                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
+                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
+                        STAGE(bc_out, (size_t)d * GSMCAL_BCCH_COLS * sizeof(double), nullptr, out, 0),
+                        STAGE(bc_corr_out, corr ? (size_t)d * BC_SLOTS * 8 * sizeof(cplx) : 0, nullptr, corr, 0),
+                        STAGE(bc_r, r_out ? nr : 0, nullptr, r_out, 0),
+                        STAGE(bc_rlen, r_out ? (size_t)d * sizeof(long) : 0, nullptr, r_len_out, 0)};
+    RET_IF(stage_up(c, io));
+    if (r_out) HIPCHK(c, hipMemsetAsync(c->bc_r.p, 0, nr, c->stream));      // rows the reference leaves at r = -1 come back as zeros
+    RET_IF(gsmcal_bcch_demod_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d, ov,
+                                       nts, len_ts, carrier_freq, (double*)c->bc_out.p, corr ? (double*)c->bc_corr_out.p : nullptr,
+                                       r_out ? (double*)c->bc_r.p : nullptr, r_out ? (long*)c->bc_rlen.p : nullptr));
+    return stage_down(c, io);
+}
+
+int gsmcal_BCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* pos_info, int rows, int ld, const double* nts, int len_ts,
+                      int ov, double carrier_freq, int* idx, double* r, long cap_r, long* len_r, double* carrier_ppm, double* corr_val,
+                      double* table_row) {
+    if (!c || !pos_info || !nts || !idx || rows < 1 || ld < rows || ov < 1 || (r && !len_r)) return GSMCAL_E_ARG;
+    ENTER(c);
+    *idx = -1;                                                  // :6-8
+    if (len_r) *len_r = -1;
+    if (carrier_ppm) *carrier_ppm = -1.0;
+    std::vector<double> row(GSMCAL_BCCH_COLS, NAN);
+    bool all_m1 = true;                                         // :9 `if pos_info == -1`: every element
+    int n0 = 0;
+    for (int i = 0; i < rows; ++i) {
+        all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
+        n0 += pos_info[ld + i] == 0.0;
+    }
+    if (all_m1) {
+        row[GSMCAL_B_NUM_BCCH] = 0.0; row[GSMCAL_B_TSC_IDX] = -1.0; row[GSMCAL_B_STATUS] = GSMCAL_S_POST_NO_POS;
+        if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
+        c->report.clear();                                      // the .m file prints nothing at :9
+        return GSMCAL_S_POST_NO_POS;
+    }
+    if (!s || len < 1) return GSMCAL_E_ARG;
+    if (rows > MAXROWS) return GSMCAL_E_CAPACITY;
+    if (r && cap_r < len) return GSMCAL_E_CAPACITY;
+    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
+    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
+    std::vector<double> corr((size_t)BC_SLOTS * 8 * 2);
+    long lr = -1;
+    RET_IF(gsmcal_bcch_demod_batch(c, s, len, &len, pi.data(), 1, ov, nts, len_ts, &carrier_freq, row.data(), corr.data(), r,
+                                   r ? &lr : nullptr));
+    if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
+    const int status = (int)row[GSMCAL_B_STATUS];
+    if (status < 0) return status;                              // MATLAB: index exceeds matrix dimensions at :59 or :95
+    if (status == GSMCAL_S_POST_FEW_BCCH) {
+        c->report = report_bcch_demod(row.data(), nullptr, 0);
+        return status;
+    }
+    std::vector<double> fo((size_t)MAXH * FD_PART, 0.0);        // the per-burst frequencies :69 prints: stream 0 of the workspace
+    if (n0 > 0) {
+        HIPCHK(c, hipMemcpyAsync(fo.data(), c->fd_part.p, (size_t)n0 * FD_PART * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < n0; ++i) fo[i] = fo[(size_t)i * FD_PART];
+    }
+    *idx = (int)row[GSMCAL_B_TSC_IDX];
+    if (len_r) *len_r = r ? lr : len;
+    if (carrier_ppm) *carrier_ppm = row[GSMCAL_B_CARRIER_PPM];
+    if (corr_val) memcpy(corr_val, corr.data(), (size_t)4 * 8 * 2 * sizeof(double));     // :97, 8 x 4 column-major
+    c->report = report_bcch_demod(row.data(), fo.data(), n0);
     return status;
 }
 

@@ -1,5 +1,6 @@
 // abi_report.h -- the reference's console diagnostics (FCCH_coarse_position.m:6,28,92-94, FCCH_fine_correction.m:6,13,66,
-// 96-99,116,156-161,190-193, SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79, FCCH_demod.m:6,9,43-49,65-66) as TEXT:
+// 96-99,116,156-161,190-193, SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79, FCCH_demod.m:6,9,43-49,65-66,
+// BCCH_demod.m:15,69,72,101,104) as TEXT:
 // the per-function entry points of abi_calls.h have the stream's state on the host anyway and leave the lines the .m file would
 // have disp()ed in the context; gsmcal_last_call_report() hands them to the MEX gateway (mexPrintf) or the Python mirror.
 // Included by gsmcal.hip ahead of abi_calls.h (host code only).
@@ -136,6 +137,19 @@ std::string report_fcch_demod(const double* row) {
     r += "FCCH demod: carrier error ppm " + rep_num2str(row[GSMCAL_D_CARRIER_PPM]) + "\n";
     r += "FCCH demod: SNR " + rep_num2str(row + GSMCAL_D_SNR, nb) + "\n";
     r += "FCCH demod: max idx " + rep_num2str(row + GSMCAL_D_MAX_IDX, nb) + "\n";
+    return r;
+}
+
+// BCCH_demod.m:15,69,72,101,104.  row: one row of the BCCH_demod table (GSMCAL_B_*), status 0, GSMCAL_S_POST_FEW_BCCH or
+// GSMCAL_S_BCCH_TSC_MIXED (the .m file prints nothing at the :9 exit, and no blank line first); fo: the n0 per-burst frequencies.
+std::string report_bcch_demod(const double* row, const double* fo, int n0) {
+    const int status = (int)row[GSMCAL_B_STATUS];
+    if (status == GSMCAL_S_POST_FEW_BCCH) return "The number of BCCH bursts is less than 4!\n";
+    std::string r = "post SCH freq " + rep_num2str(fo, n0) + "\n";
+    const double both[2] = {row[GSMCAL_B_CARRIER_PPM], row[GSMCAL_B_MEAN_FO]};
+    r += "carrier ppm and mean fo " + rep_num2str(both, 2) + "\n";
+    if (status == 0) r += "Normal training sequence idx (BCCH) " + rep_num2str(row[GSMCAL_B_TSC_IDX]) + "\n";
+    else r += "Fail to identity normal training sequence idx (BCCH).\n";
     return r;
 }
 

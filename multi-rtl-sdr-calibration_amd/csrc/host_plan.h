@@ -55,6 +55,9 @@ struct CtxBufs {
     DevBuf bp_coef, bp_state, bp_part;
     // FCCH_demod (gsmcal_FCCH_demod, gsmcal_fcch_demod_batch*) -- its twiddle table too, the oversampling ratio may differ from the chain's
     DevBuf fd_tw, fd_cf, fd_part, fd_in, fd_len, fd_pos, fd_out;
+    // BCCH_demod (gsmcal_BCCH_demod, gsmcal_bcch_demod_batch*), on top of FCCH_demod's buffers: the templates, the correlations and
+    // window flags per (stream, burst slot), and the host wrapper's staging of the table, the correlations, r and its lengths
+    DevBuf bc_ts, bc_corr, bc_flag, bc_out, bc_corr_out, bc_r, bc_rlen;
     // sub-band power (gsmcal_subband_power_batch*).  sb_taps: one modulated tap row per distinct phase_rotate value, built on the
     // host; sb_idx: the [capture][slot] table into them
     DevBuf sb_taps, sb_idx, sb_state, sb_part;
@@ -62,7 +65,8 @@ struct CtxBufs {
     // (capture, tile) of the two passes; cw_mean: phase_rotate and status per capture
     DevBuf cw_state, cw_part, cw_rec, cw_mean, cw_in, cw_r;
     ALL_BUFS(CtxBufs, &coef, &ts, &cf, &table, &snrhit, &arr_in, &arr_out, &posinfo, &rlen, &misc, &tw, &csum_head, &tw_sch, &stage_raw,
-             &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &sb_taps, &sb_idx,
+             &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &bc_ts, &bc_corr, &bc_flag, &bc_out,
+             &bc_corr_out, &bc_r, &bc_rlen, &sb_taps, &sb_idx,
              &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r)
 };
 
@@ -174,7 +178,7 @@ struct gsmcal_ctx : CtxBufs {
     int tw_n = 0;                            // length the twiddle table was built for
     std::vector<double> h_coef, h_ts, h_cf;   // host copies: upload only when changed
     // host copies of the add-on caches (upload_if_changed); h_sb_coef / h_sb_w: what the rows in sb_taps were built from
-    std::vector<double> h_bp_coef, h_fd_cf, h_sb_coef, h_sb_w, h_sb_rows;
+    std::vector<double> h_bp_coef, h_fd_cf, h_bc_ts, h_sb_coef, h_sb_w, h_sb_rows;
     std::vector<int> h_sb_idx;
     int fd_tw_n = 0;
     int last_S = 0;

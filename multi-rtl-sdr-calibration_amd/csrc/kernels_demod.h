@@ -326,3 +326,215 @@ __global__ void __launch_bounds__(64) k_fcch_demod_finish(const long* __restrict
         o[GSMCAL_D_STATUS] = (double)status;
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// BCCH_demod.m -- which of the eight normal training sequences the BCCH bursts carry.  The function body is
+// carrier_correct_post_SCH.m:51-83 (:49-76 here: the tone estimate of every FCCH burst, mean(fo), carrier_ppm, the stream
+// rotated by comp_phase_rotate) followed by the correlation of :84-106 at the fixed position 61 symbols into each BCCH burst.
+// The tone estimate is k_fcch_demod's (FCCH_demod.m:28-42 is the same block): these kernels read its workspace.
+//
+// k_bcch_corr: grid (BC_GRID_X, D), block BC_THREADS.  Workgroup (g, s) takes the type-2 rows g, g + BC_GRID_X, ... of stream
+// s's pos_info (the slot-to-row mapping of k_fcch_demod with type 2 in place of type 0; every wave ranks the rows itself from
+// three ballots, so a workgroup without a row returns before the first barrier).  Per row: the 26*ov window r(sp:ep), sp =
+// bcch_pos + 61*ov (:93-95), read once, rotated by exp(1i*n*comp_phase_rotate) at its absolute sample index n (:76) and kept in
+// LDS; wave w forms the conjugated dot products with templates 2w and 2w+1 (:97) -- fp64 FMAs, lane l takes samples l, l+64,
+// ..., then the wave sum, lane 0 writes: a fixed order, the same for every template.  corr[s][slot][8], flag[s][slot] = 0 or
+// GSMCAL_E_INDEX (the window leaves the stream: decided before a sample is read, the eight sums NaN).
+// Every workgroup forms mean(fo) itself, left to right like k_bcch_finish: the same bits everywhere.
+// ------------------------------------------------------------------------------------------------
+#define BC_THREADS 256
+#define BC_GRID_X 8
+#define BC_SLOTS GSMCAL_MAX_BCCH
+
+__device__ __forceinline__ double bc_mean_fo(const double* __restrict__ ps, int n0) {
+    double acc = 0.0;
+    for (int i = 0; i < n0; ++i) acc += ps[i * FD_PART];                         // :70 mean(fo): left to right
+    return n0 > 0 ? acc / (double)n0 : __longlong_as_double(0x7ff8000000000000LL);   // mean([]) = NaN
+}
+__device__ __forceinline__ double bc_comp_phase(double mean_fo, int ov) {
+    return (GSM_SYMBOL_RATE / 4.0 - mean_fo) * 2.0 * PI_D / (GSM_SYMBOL_RATE * (double)ov);   // :74-75
+}
+
+__global__ void __launch_bounds__(BC_THREADS) k_bcch_corr(const cplx* __restrict__ r, long stride, const long* __restrict__ r_len,
+                                                          const double* __restrict__ pos_info, int ov, const cplx* __restrict__ nts,
+                                                          const double* __restrict__ fd_part, cplx* __restrict__ corr,
+                                                          int* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    cplx* win = (cplx*)smem;
+    const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long len = r_len[s] < stride ? r_len[s] : stride;
+    if (len < 1) return;                                           // block-uniform
+    const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
+    // ---- :13, :49  the type-2 and the type-0 rows, ranked by every wave on its own ----
+    constexpr int NCH = (MAXROWS + 63) / 64;
+    bool is2[NCH];
+    int rank[NCH];
+    int nb = 0, n0 = 0;
+    for (int c = 0; c < NCH; ++c) {
+        const int i = c * 64 + lane;
+        const double t = i < MAXROWS ? pi[MAXROWS + i] : -1.0;
+        is2[c] = t == 2.0;
+        const unsigned long long m2 = __ballot(is2[c]), m0 = __ballot(t == 0.0);
+        rank[c] = nb + __popcll(m2 & ((1ull << lane) - 1ull));
+        nb += __popcll(m2);
+        n0 += __popcll(m0);
+    }
+    if (nb < 4 || n0 > MAXH) return;                               // :14 / more FCCH rows than the workspace holds: k_bcch_finish says which
+    if (nb > BC_SLOTS) nb = BC_SLOTS;
+    if ((int)blockIdx.x >= nb) return;                             // no row for this workgroup
+    const double cpr = bc_comp_phase(bc_mean_fo(fd_part + (size_t)s * MAXH * FD_PART, n0), ov);
+    const int lts = 26 * ov;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (int b = blockIdx.x; b < nb; b += BC_GRID_X) {             // (uniform)
+        int row = 0;
+        for (int c = 0; c < NCH; ++c) {
+            const unsigned long long sel = __ballot(is2[c] && rank[c] == b);
+            if (sel) row = c * 64 + __ffsll((long long)sel) - 1;
+        }
+        cplx* oc = corr + ((size_t)s * BC_SLOTS + b) * 8;
+        int* of = flag + (size_t)s * BC_SLOTS + b;
+        const double spd = pi[row] + (double)(61 * ov);            // :93
+        if (!(spd >= 1.0) || !(spd <= (double)len) || (long)spd - 1 + lts > len) {   // :95 would stop with an index error
+            if (tid < 8) oc[tid] = make_double2(nan, nan);
+            if (tid == 0) *of = GSMCAL_E_INDEX;
+            continue;
+        }
+        const long n_abs = (long)spd - 1;                          // 0-based index of r(sp)
+        const cplx* x = r + (size_t)s * stride + n_abs;
+        for (int i = tid; i < lts; i += BC_THREADS) {
+            double sn, cs;
+            sincos((double)(n_abs + i) * cpr, &sn, &cs);           // :76 the rounded product, then sin and cos
+            win[i] = cmul(x[i], make_double2(cs, sn));
+        }
+        __syncthreads();
+        for (int q = 0; q < 2; ++q) {
+            const int k = 2 * wave + q;
+            const cplx* t = nts + (size_t)k * lts;
+            double ar = 0.0, ai = 0.0;
+            for (int i = lane; i < lts; i += 64) {                 // conj(t) * w
+                const cplx tv = t[i], w = win[i];
+                ar = fma(tv.x, w.x, fma(tv.y, w.y, ar));
+                ai = fma(tv.x, w.y, fma(-tv.y, w.x, ai));
+            }
+            ar = wave_sum(ar);
+            ai = wave_sum(ai);
+            if (lane == 0) oc[k] = make_double2(ar, ai);
+        }
+        if (tid == 0) *of = 0;
+        __syncthreads();                                           // win is rewritten for the next row
+    }
+}
+
+// k_bcch_finish: one wave per stream, grid D, block 64.  out[s] = one row of GSMCAL_BCCH_COLS doubles (GSMCAL_B_*), written here
+// and nowhere else: per evaluated burst the first maximum of |corr| (:99; a later equal value does not replace it), the second
+// largest value and the winner's angle; the decision of :100 on the first four; unused entries NaN.
+//   r_len < 1 or every element of pos_info -1 (:9)       status GSMCAL_S_POST_NO_POS, num_bcch 0
+//   fewer than 4 type-2 rows (:14)                        status GSMCAL_S_POST_FEW_BCCH
+//   more than BC_SLOTS type-2 or MAXH type-0 rows         status GSMCAL_E_CAPACITY
+//   an FCCH window or one of the first four BCCH windows outside the stream      status GSMCAL_E_INDEX
+//   the first four winners differ (:103)                  status GSMCAL_S_BCCH_TSC_MIXED, mean_fo and carrier_ppm valid
+// In the first four cases tsc_idx is -1 and mean_fo, carrier_ppm, num_agree NaN.  A row beyond the fourth with its window outside
+// the stream has NaN entries and is no error (the reference never reads it).  corr_out (may be NULL): [D][BC_SLOTS][8] complex, NaN
+// where no burst was evaluated.  r_len_out (may be NULL): the stream's length where the reference has formed r (status 0 or
+// GSMCAL_S_BCCH_TSC_MIXED), -1 elsewhere.
+__global__ void __launch_bounds__(64) k_bcch_finish(const long* __restrict__ r_len, long stride, const double* __restrict__ pos_info,
+                                                    const double* __restrict__ carrier_freq, const double* __restrict__ fd_part,
+                                                    const cplx* __restrict__ corr, const int* __restrict__ flag, double* __restrict__ out,
+                                                    cplx* __restrict__ corr_out, long* __restrict__ r_len_out) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
+    const double* ps = fd_part + (size_t)s * MAXH * FD_PART;
+    const cplx* cs = corr + (size_t)s * BC_SLOTS * 8;
+    const int* fs = flag + (size_t)s * BC_SLOTS;
+    double* o = out + (size_t)s * GSMCAL_BCCH_COLS;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    unsigned n0 = 0, n2 = 0, not_m1 = 0;
+    for (int i = lane; i < MAXROWS; i += 64) {
+        const double p = pi[i], t = pi[MAXROWS + i];
+        n0 += t == 0.0;
+        n2 += t == 2.0;
+        not_m1 += (p != -1.0) || (t != -1.0);
+    }
+    n0 = wave_sum_u32(n0);
+    n2 = wave_sum_u32(n2);
+    not_m1 = wave_sum_u32(not_m1);
+    const long len = r_len[s] < stride ? r_len[s] : stride;
+    int status = 0, nb = (int)n2;
+    if (len < 1 || not_m1 == 0) { status = GSMCAL_S_POST_NO_POS; nb = 0; }
+    else if (nb < 4) status = GSMCAL_S_POST_FEW_BCCH;              // the literal 4 of :14
+    else if (nb > BC_SLOTS || n0 > MAXH) status = GSMCAL_E_CAPACITY;
+    else {
+        for (unsigned i = 0; i < n0; ++i)                          // (uniform loops, uniform loads)
+            if (status == 0 && ps[i * FD_PART + 3] != 0.0) status = GSMCAL_E_INDEX;
+        for (int i = 0; i < 4; ++i)
+            if (status == 0 && fs[i] != 0) status = GSMCAL_E_INDEX;
+    }
+    const bool ok = status == 0;
+    double idx0 = nan, idx1 = nan, idx2 = nan, idx3 = nan;
+    unsigned agree = 0;
+    for (int b0 = 0; b0 < BC_SLOTS; b0 += 64) {                    // (uniform)
+        const int b = b0 + lane;
+        const bool use = ok && b < nb && b < BC_SLOTS && fs[b] == 0;
+        double best = -1.0, second = -1.0, ph = nan;
+        int bi = -1;
+        if (use) {
+            for (int k = 0; k < 8; ++k) {
+                const double m = hypot(cs[b * 8 + k].x, cs[b * 8 + k].y);       // abs()
+                if (m > best) { second = best; best = m; bi = k; }
+                else if (m > second) second = m;
+            }
+            if (bi >= 0) ph = atan2(cs[b * 8 + bi].y, cs[b * 8 + bi].x);
+        }
+        const double idx = bi >= 0 ? (double)(bi + 1) : nan;
+        if (b0 == 0) { idx0 = __shfl(idx, 0, 64); idx1 = __shfl(idx, 1, 64); idx2 = __shfl(idx, 2, 64); idx3 = __shfl(idx, 3, 64); }
+        agree += idx == idx0;
+        if (b < BC_SLOTS) {
+            o[GSMCAL_B_IDX + b] = idx;
+            o[GSMCAL_B_PEAK + b] = bi >= 0 ? best : nan;
+            o[GSMCAL_B_RUNNER_UP + b] = bi >= 0 ? second : nan;
+            o[GSMCAL_B_PHASE + b] = ph;
+        }
+    }
+    agree = wave_sum_u32(agree);
+    double tsc = -1.0;
+    if (ok) {
+        if (idx0 == idx1 && idx0 == idx2 && idx0 == idx3) tsc = idx0;            // :100 (NaN equals nothing)
+        else status = GSMCAL_S_BCCH_TSC_MIXED;
+    }
+    if (corr_out)
+        for (int i = lane; i < BC_SLOTS * 8; i += 64) {
+            const int b = i >> 3;
+            corr_out[(size_t)s * BC_SLOTS * 8 + i] = ok && b < nb && fs[b] == 0 ? cs[i] : make_double2(nan, nan);
+        }
+    if (lane == 0) {
+        double mean = nan, ppm = nan;
+        if (ok) {
+            mean = bc_mean_fo(ps, (int)n0);                                      // :70
+            ppm = 1e6 * (mean - GSM_SYMBOL_RATE / 4.0) / carrier_freq[s];        // :71
+        }
+        o[GSMCAL_B_NUM_BCCH] = (double)nb;
+        o[GSMCAL_B_TSC_IDX] = tsc;
+        o[GSMCAL_B_MEAN_FO] = mean;
+        o[GSMCAL_B_CARRIER_PPM] = ppm;
+        o[GSMCAL_B_STATUS] = (double)status;
+        o[GSMCAL_B_NUM_AGREE] = ok ? (double)agree : nan;
+        if (r_len_out) r_len_out[s] = ok ? len : -1;
+    }
+}
+
+// k_bcch_rotate: r = s .* exp(1i*(0:len-1)'*comp_phase_rotate) (:76) for the streams k_bcch_finish left a length for; launched only
+// when r is asked for.  grid (blocks, D), block 256, grid-stride over the stream.
+__global__ void __launch_bounds__(256) k_bcch_rotate(const cplx* __restrict__ r, long stride, const long* __restrict__ r_len_out,
+                                                     const double* __restrict__ table, int ov, cplx* __restrict__ r_out) {
+    const int s = blockIdx.y;
+    const long len = r_len_out[s];
+    if (len < 1) return;
+    const double cpr = bc_comp_phase(table[(size_t)s * GSMCAL_BCCH_COLS + GSMCAL_B_MEAN_FO], ov);
+    const cplx* x = r + (size_t)s * stride;
+    cplx* y = r_out + (size_t)s * stride;
+    for (long n = (long)blockIdx.x * 256 + threadIdx.x; n < len; n += (long)gridDim.x * 256) {
+        double sn, cs;
+        sincos((double)n * cpr, &sn, &cs);
+        y[n] = cmul(x[n], make_double2(cs, sn));
+    }
+}

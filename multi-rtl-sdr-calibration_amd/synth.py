@@ -35,6 +35,18 @@ SCH_TRAINING_BITS = np.array(
 # GSM 05.02 normal-burst training sequence code 0 (26 bits)
 TSC0 = np.array([0, 0, 1, 0, 0, 1, 0, 1, 1, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 1, 0, 1, 1, 1], dtype=np.int8)
 
+# GSM 05.02 table 5.2.3a: the eight normal-burst training sequence codes (the bits gsm_normal_training_sequence_gen.m:18-25
+# lists); TSC[k] is what a cell with base-station colour code k sends in every normal burst of its BCCH carrier
+TSC = np.array([
+    [0, 0, 1, 0, 0, 1, 0, 1, 1, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 1, 0, 1, 1, 1],
+    [0, 0, 1, 0, 1, 1, 0, 1, 1, 1, 0, 1, 1, 1, 1, 0, 0, 0, 1, 0, 1, 1, 0, 1, 1, 1],
+    [0, 1, 0, 0, 0, 0, 1, 1, 1, 0, 1, 1, 1, 0, 1, 0, 0, 1, 0, 0, 0, 0, 1, 1, 1, 0],
+    [0, 1, 0, 0, 0, 1, 1, 1, 1, 0, 1, 1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 1, 1, 0],
+    [0, 0, 0, 1, 1, 0, 1, 0, 1, 1, 1, 0, 0, 1, 0, 0, 0, 0, 0, 1, 1, 0, 1, 0, 1, 1],
+    [0, 1, 0, 0, 1, 1, 1, 0, 1, 0, 1, 1, 0, 0, 0, 0, 0, 1, 0, 0, 1, 1, 1, 0, 1, 0],
+    [1, 0, 1, 0, 0, 1, 1, 1, 1, 1, 0, 1, 1, 0, 0, 0, 1, 0, 1, 0, 0, 1, 1, 1, 1, 1],
+    [1, 1, 1, 0, 1, 1, 1, 1, 0, 0, 0, 1, 0, 0, 1, 0, 1, 1, 1, 0, 1, 1, 1, 1, 0, 0]], dtype=np.int8)
+
 DEFAULT_SEED = 20260101
 
 
@@ -79,6 +91,12 @@ def sch_training_sequence(sps=OV):
     return gmsk_modulate(diff_precode(SCH_TRAINING_BITS), sps)
 
 
+def normal_training_sequences(sps=OV):
+    """(26*sps, 8) complex templates, column k = TSC[k] modulated: stand-in for gsm_normal_training_sequence_gen(sps)."""
+    g = gmsk_frequency_pulse(sps=sps)
+    return np.stack([gmsk_modulate(diff_precode(TSC[k]), sps, g) for k in range(8)], axis=1)
+
+
 def fir1(n, wn):
     """Own statement of fir1(n, Wn) (low-pass, Hamming window, unit DC gain), as used at
     gsm_sync_demod.m:34 / multi_rtl_sdr_gsm_FCCH_scanner.m:53."""
@@ -94,7 +112,7 @@ def fir1(n, wn):
     return h / np.sum(h)
 
 
-def _burst_bits(kind, rng):
+def _burst_bits(kind, rng, tsc=0):
     if kind == "F":
         return np.zeros(BURST_BITS, dtype=np.int8)
     if kind == "S":
@@ -102,7 +120,7 @@ def _burst_bits(kind, rng):
                                SCH_TRAINING_BITS, rng.integers(0, 2, 39, dtype=np.int8),
                                np.zeros(3, np.int8)])
     # normal burst: 3 tail, 58 data(+stealing), 26 TSC, 58 data, 3 tail
-    return np.concatenate([np.zeros(3, np.int8), rng.integers(0, 2, 58, dtype=np.int8), TSC0,
+    return np.concatenate([np.zeros(3, np.int8), rng.integers(0, 2, 58, dtype=np.int8), TSC[tsc],
                            rng.integers(0, 2, 58, dtype=np.int8), np.zeros(3, np.int8)])
 
 
@@ -128,9 +146,10 @@ def _ramp(n_total, n_edge=8):
 _RAMP = _ramp(BURST_BITS * OV)
 
 
-def ideal_waveform(num_frames, start_frame, rng, bcch=True):
+def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0):
     """Complex baseband at exactly 8 samples/symbol, num_frames TDMA frames starting at frame
-    `start_frame` of the 51-multiframe.  bcch=False gives a traffic-only carrier (no FCCH/SCH)."""
+    `start_frame` of the 51-multiframe.  bcch=False gives a traffic-only carrier (no FCCH/SCH).
+    tsc: the training sequence code (0..7) every normal burst carries."""
     n = num_frames * FRAME_OV
     x = np.zeros(n, dtype=np.complex128)
     # all bursts of the stream are modulated in one vectorised pass: bits -> (nb, 148)
@@ -148,7 +167,7 @@ def ideal_waveform(num_frames, start_frame, rng, bcch=True):
     nbits = PRE + BURST_BITS + POST
     bits = np.zeros((nb, nbits), dtype=np.int8)
     for i, k in enumerate(kinds):
-        bits[i, PRE:PRE + BURST_BITS] = _burst_bits("N" if k == "I" else k, rng)
+        bits[i, PRE:PRE + BURST_BITS] = _burst_bits("N" if k == "I" else k, rng, tsc)
     prev = np.concatenate([np.zeros((nb, 1), np.int8), bits[:, :-1]], axis=1)
     pre = 1 - np.abs(bits - prev)                       # diff_precode per burst
     a = 2.0 * pre.astype(np.float64) - 1.0
@@ -171,10 +190,11 @@ def ideal_waveform(num_frames, start_frame, rng, bcch=True):
 
 def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
                 sampling_ppm=None, carrier_ppm=None, snr_db=None, carrier_freq=957.4e6,
-                start_frame=None, frac_start=None, tx_key=None):
+                start_frame=None, frac_start=None, tx_key=None, tsc=0):
     """One capture: returns (raw uint8 interleaved I,Q of length 2*num_frames*10000, truth dict).
     tx_key: dongles given the same key receive the SAME transmission (payload, multiframe phase, start instant) through
-    their own clocks, carrier offsets and noise -- what gsm_sync_demod.m's inter-dongle phase plot (:151-158) looks at."""
+    their own clocks, carrier offsets and noise -- what gsm_sync_demod.m's inter-dongle phase plot (:151-158) looks at.
+    tsc: the cell's training sequence code (0..7), planted in every normal burst."""
     rng = np.random.Generator(np.random.Philox(key=[int(seed), (int(dongle) << 20) ^ int(arfcn)]))
     eps_s = rng.uniform(-80.0, 80.0) if sampling_ppm is None else float(sampling_ppm)
     eps_c = rng.uniform(-40.0, 40.0) if carrier_ppm is None else float(carrier_ppm)
@@ -183,14 +203,14 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     fs0 = rng.uniform(0.0, FRAME_OV) if frac_start is None else float(frac_start)
     n = num_frames * FRAME_OV
     if tx_key is None:
-        ideal = ideal_waveform(num_frames + 2, sf, rng, bcch=bcch)
+        ideal = ideal_waveform(num_frames + 2, sf, rng, bcch=bcch, tsc=tsc)
     else:
         txr = np.random.Generator(np.random.Philox(key=[int(seed) ^ 0x5A5A5A5A, int(tx_key)]))
         if start_frame is None:
             sf = int(txr.integers(0, 51))
         if frac_start is None:
             fs0 = txr.uniform(0.0, FRAME_OV)
-        ideal = ideal_waveform(num_frames + 2, sf, txr, bcch=bcch)
+        ideal = ideal_waveform(num_frames + 2, sf, txr, bcch=bcch, tsc=tsc)
     # the dongle's clock runs (1+eps_s) fast => sample k is taken at ideal time k/(1+eps_s)... the
     # estimator's sign convention (FCCH_fine_correction.m:111-115): observed spacing = ideal*(1+e)
     # means the dongle takes MORE samples per GSM frame, i.e. query ideal time t_k = k/(1+e).
