@@ -49,6 +49,7 @@ enum {
     GSMCAL_S_POST_FEW_BCCH = 11,  /* carrier_correct_post_SCH.m:15-19                             */
     GSMCAL_S_ALL_INF = 12,        /* total_ppm_calculation.m:7-11                                 */
     GSMCAL_S_BCCH_TSC_MIXED = 13, /* BCCH_demod.m:103-105: the first four BCCH bursts disagree     */
+    GSMCAL_S_SCH_NO_DECODE = 14,  /* gsmcal_SCH_decode: fewer than two SCH bursts decode consistently */
     /* < 0: failures */
     GSMCAL_E_ARG = -1,
     GSMCAL_E_HIP = -2,
@@ -64,6 +65,7 @@ enum {
 #define GSMCAL_DEMOD_COLS (4 + 3 * GSMCAL_MAX_HITS)   /* one row of gsmcal_fcch_demod_batch[_dev]: 76 doubles */
 #define GSMCAL_MAX_BCCH (4 * GSMCAL_MAX_HITS)         /* BCCH bursts (type-2 rows of pos_info) gsmcal_bcch_demod_batch evaluates */
 #define GSMCAL_BCCH_COLS (6 + 4 * GSMCAL_MAX_BCCH)    /* one row of gsmcal_bcch_demod_batch[_dev]: 390 doubles */
+#define GSMCAL_SCH_COLS (8 + 7 * GSMCAL_MAX_HITS)      /* one row of gsmcal_sch_decode_batch[_dev]: 176 doubles */
 
 /* columns of one row of the calibration table (doubles; this row is what ranks all-gather) */
 enum {
@@ -102,6 +104,25 @@ enum {
     GSMCAL_B_PEAK = 6 + GSMCAL_MAX_BCCH,            /* [GSMCAL_MAX_BCCH] |corr_val| of the winner                              */
     GSMCAL_B_RUNNER_UP = 6 + 2 * GSMCAL_MAX_BCCH,   /* [GSMCAL_MAX_BCCH] the second largest |corr_val|                         */
     GSMCAL_B_PHASE = 6 + 3 * GSMCAL_MAX_BCCH        /* [GSMCAL_MAX_BCCH] angle of the winning correlation                      */
+};
+
+/* columns of one row of the SCH_decode table (doubles) */
+enum {
+    GSMCAL_C_NUM_SCH = 0,                           /* type-1 rows of pos_info (0 at GSMCAL_S_POST_NO_POS)                     */
+    GSMCAL_C_NUM_OK = 1,                            /* bursts whose decoded word passes every check                            */
+    GSMCAL_C_NUM_CONSISTENT = 2,                    /* c_anchor: ok bursts that agree with the anchor on BSIC and frame count  */
+    GSMCAL_C_BSIC = 3,                              /* the cell's BSIC (0..63; the low three bits are the colour code), or -1  */
+    GSMCAL_C_FN_ANCHOR = 4,                         /* GSM frame number of the anchor burst, or -1                             */
+    GSMCAL_C_POS_ANCHOR = 5,                        /* 1-based start sample of the anchor burst, or -1                         */
+    GSMCAL_C_STATUS = 6,                            /* 0, GSMCAL_S_POST_NO_POS, GSMCAL_S_SCH_NO_DECODE, GSMCAL_E_CAPACITY      */
+    GSMCAL_C_MEAN_SLOPE = 7,                        /* mean of slope[] over the ok bursts (rad/symbol), NaN without one        */
+    GSMCAL_C_OK = 8,                                /* [GSMCAL_MAX_HITS] 1 / 0; NaN: the burst was not evaluated               */
+    GSMCAL_C_BSIC_B = 8 + GSMCAL_MAX_HITS,          /* [GSMCAL_MAX_HITS] BSIC of an ok burst, NaN otherwise                    */
+    GSMCAL_C_FN = 8 + 2 * GSMCAL_MAX_HITS,          /* [GSMCAL_MAX_HITS] frame number of an ok burst, NaN otherwise            */
+    GSMCAL_C_TS_ERR = 8 + 3 * GSMCAL_MAX_HITS,      /* [GSMCAL_MAX_HITS] hard errors in the 64 training bits                   */
+    GSMCAL_C_CORRECTED = 8 + 4 * GSMCAL_MAX_HITS,   /* [GSMCAL_MAX_HITS] hard channel bits that differ from the re-encoded word */
+    GSMCAL_C_SLOPE = 8 + 5 * GSMCAL_MAX_HITS,       /* [GSMCAL_MAX_HITS] phase slope across the burst, rad/symbol              */
+    GSMCAL_C_AMP = 8 + 6 * GSMCAL_MAX_HITS          /* [GSMCAL_MAX_HITS] |h| / 64                                              */
 };
 
 /* ---- algorithm thresholds (the constants the reference hard-codes inside its functions) ---------- */
@@ -161,7 +182,7 @@ const char* gsmcal_last_error(gsmcal_ctx* ctx);
  * SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79) -- and a MEX file that shadows one
  * would otherwise run silent.  After gsmcal_FCCH_coarse_position / _FCCH_fine_correction / _SCH_corr_rate_correction /
  * _carrier_correct_post_SCH this returns the lines that call's .m file would have printed, '\n'-separated, numbers formatted as
- * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  gsmcal_FCCH_demod and gsmcal_BCCH_demod leave their lines too.  buf may be NULL; the return value is the
+ * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  gsmcal_FCCH_demod, gsmcal_BCCH_demod and gsmcal_SCH_decode leave their lines too.  buf may be NULL; the return value is the
  * text's length without the terminator.  The gateway mexPrintf()s it; the Python mirror prints it when GSMCAL_VERBOSE=1. */
 long gsmcal_last_call_report(gsmcal_ctx* ctx, char* buf, size_t cap);
 long gsmcal_num2str(const double* x, int n, char* buf, size_t cap);
@@ -358,6 +379,31 @@ int gsmcal_BCCH_demod(gsmcal_ctx* ctx, const double* s, long len, const double* 
                       const double* normal_training_sequence, int len_ts, int oversampling_ratio, double carrier_freq,
                       int* idx, double* r, long cap_r, long* len_r, double* carrier_ppm, double* corr_val, double* table_row);
 
+/* SCH_decode(s, pos_info, sch_training_sequence, ov): the payload of the SCH bursts that pos_info marks (type 1) -- the cell's BSIC
+ * and the GSM frame number of every burst.  The project's own function, NOT a port of SCH_demod.m, which has
+ * no outputs and demodulates with Communications Toolbox code.  Per burst with 1-based start p, ov in {2, 4, 8} (anything else:
+ * GSMCAL_E_UNSUPPORTED), delta = (5*ov - 1) div 2:
+ *   y_k = s(p + k*ov + delta) * (-j)^k for the symbols k = 3..144 -- one sample per symbol; a burst whose reads leave the stream, or
+ *   whose p is NaN or < 1, is not evaluated (NaN columns, no error);  h1, h2 = the correlations of y_42..73 and y_74..105 with the
+ *   two halves of the 64 training bits (1 - 2 bit), h = h1 + h2, slope = angle(h2 conj(h1)) / 32, amp = |h| / 64;
+ *   soft_k = Re(y_k conj(h)/|h| exp(-j slope (k - 73.5))), positive = bit 0;  a 16-state soft-decision Viterbi decoder (GSM 05.03
+ *   4.7: c(2k) = u(k)+u(k-3)+u(k-4), c(2k+1) = u(k)+u(k-1)+u(k-3)+u(k-4); burst bits 3..41 and 106..144) from state 0 to state 0;
+ *   ok = the 10-bit CRC leaves all ones, the four tail bits are zero, T3' <= 4 and T2 <= 25;  FN = 1326 T1 + 51 ((T3 - T2) mod 26) + T3.
+ * Per stream: the ok bursts that agree on the BSIC and whose frame numbers differ by what their positions say (1250*ov samples per
+ * frame, modulo the hyperframe of 2 715 648 frames) are counted per burst; the first burst with the largest count c is the anchor;
+ * status 0 needs c >= 2 (one pass of a 10-bit CRC is not evidence), otherwise GSMCAL_S_SCH_NO_DECODE and *bsic, *fn_anchor,
+ * *pos_anchor = -1.  pos_info all -1: GSMCAL_S_POST_NO_POS.  More than GSMCAL_MAX_HITS type-1 rows: GSMCAL_E_CAPACITY.
+ * sch_training_sequence: the template gsmcal_SCH_corr_rate_correction takes; the decoder works on the 64 training BITS, so only
+ * len_ts is looked at: len_ts != 64*ov is GSMCAL_E_ARG.  The bit map of the 25 information bits is unpinned against a real capture.
+ * table_row (may be NULL): GSMCAL_SCH_COLS doubles (GSMCAL_C_*), the row gsmcal_sch_decode_batch writes for this stream.  soft (may
+ * be NULL): [GSMCAL_MAX_HITS][148] doubles, NaN outside 3..144 and for bursts not evaluated.  u (may be NULL): [GSMCAL_MAX_HITS][39]
+ * bytes, the decoded words (25 information, 10 parity, 4 tail bits), 255 for bursts not evaluated.  gsmcal_last_call_report then
+ * returns "SCH bursts N decoded N consistent N" and "BSIC b frame number f at sample p" or "Fail to decode the SCH bursts."
+ * (nothing at GSMCAL_S_POST_NO_POS).  Returns the status. */
+int gsmcal_SCH_decode(gsmcal_ctx* ctx, const double* s, long len, const double* pos_info, int rows, int ld,
+                      const double* sch_training_sequence, int len_ts, int oversampling_ratio, int* bsic, long* fn_anchor,
+                      long* pos_anchor, double* table_row, double* soft, unsigned char* u);
+
 /* ppm_out = total_ppm_calculation(ppm_in)                           total_ppm_calculation.m:5-21
  * (pure host arithmetic; no context needed) */
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out);
@@ -503,6 +549,23 @@ int gsmcal_bcch_demod_batch(gsmcal_ctx* ctx, const double* r, long stride, const
 int gsmcal_bcch_demod_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
                                 int d, int oversampling_ratio, const double* normal_training_sequence, int len_ts,
                                 const double* carrier_freq, double* d_out, double* d_corr, double* d_r_out, long* d_r_len_out);
+
+/* SCH_decode for D streams, on the same inputs as gsmcal_bcch_demod_batch[_dev] with the SCH template (host, len_ts = 64*ov complex;
+ * only its length is looked at) in place of the normal templates and no carrier_freq.  out: [D][GSMCAL_SCH_COLS], row = {num_sch,
+ * num_ok, num_consistent, bsic, fn_anchor, pos_anchor, status, mean_slope, ok[], bsic[], fn[], ts_err[], corrected[], slope[], amp[]}
+ * (GSMCAL_C_*); unused entries and bursts that were not evaluated NaN.  Per-row outcomes go in the status column: 0,
+ * GSMCAL_S_POST_NO_POS (r_len = -1 or an all -1 pos_info; num_sch 0), GSMCAL_S_SCH_NO_DECODE, GSMCAL_E_CAPACITY (more than
+ * GSMCAL_MAX_HITS type-1 rows; nothing evaluated).  Optional outputs (NULL to skip): soft [D][GSMCAL_MAX_HITS][148] doubles, u
+ * [D][GSMCAL_MAX_HITS][39] bytes, as for gsmcal_SCH_decode.  ov other than 2, 4, 8: GSMCAL_E_UNSUPPORTED; len_ts != 64*ov:
+ * GSMCAL_E_ARG.  A row is bit-identical alone, at any position of a batch, and equal to what gsmcal_SCH_decode returns.  _dev:
+ * device pointers, only enqueues on the context's stream; the lanes and every answer about the calibrate / scan call before stay
+ * untouched. */
+int gsmcal_sch_decode_batch(gsmcal_ctx* ctx, const double* r, long stride, const long* r_len, const double* pos_info, int d,
+                            int oversampling_ratio, const double* sch_training_sequence, int len_ts, double* out, double* soft,
+                            unsigned char* u);
+int gsmcal_sch_decode_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
+                                int d, int oversampling_ratio, const double* sch_training_sequence, int len_ts, double* d_out,
+                                double* d_soft, unsigned char* d_u);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,

@@ -7,7 +7,7 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod BCCH_demod CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
+ *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
  *            gsmcal_band_power gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
@@ -296,6 +296,36 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nlhs > 3) plhs[3] = rc == GSMCAL_S_POST_NO_POS || rc == GSMCAL_S_POST_FEW_BCCH ? mxCreateDoubleMatrix(0, 0, mxREAL) : m;
     }
     if (r) mxFree(r);
+
+#elif defined(GSMCAL_FN_SCH_decode)
+    /* [bsic, fn_anchor, pos_anchor, fn, ok] = SCH_decode(s, pos_info, sch_training_sequence, ov): the project's own function
+     * (include/gsmcal.h), not SCH_demod.m.  The cell's BSIC, the GSM frame number of the anchor burst and its start sample (-1
+     * when fewer than two SCH bursts decode consistently or pos_info == -1), then per SCH burst the frame number and the ok flag
+     * (rows of num_sch entries, NaN where a burst was not decoded).  Prints the call's report lines. */
+    mwSize n = 0, nt = 0, k;
+    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    const double* ts;
+    int rows = (int)mxGetM(prhs[1]), bsic = -1, nb, rc;
+    long fn = -1, pos = -1;
+    double row[GSMCAL_SCH_COLS];
+    if (nrhs < 4) mexErrMsgIdAndTxt("gsmcal:args", "usage: [bsic, fn_anchor, pos_anchor, fn, ok] = SCH_decode(s, pos_info, sch_training_sequence, ov)");
+    ts = cplx_in(prhs[2], &nt);
+    rc = gsmcal_SCH_decode(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, ts, (int)nt, (int)mxGetScalar(prhs[3]), &bsic, &fn, &pos,
+                           row, NULL, NULL);
+    chk(rc, "SCH_decode");
+    say();
+    nb = (int)row[GSMCAL_C_NUM_SCH] < GSMCAL_MAX_HITS ? (int)row[GSMCAL_C_NUM_SCH] : GSMCAL_MAX_HITS;
+    plhs[0] = scalar((double)bsic);
+    if (nlhs > 1) plhs[1] = scalar((double)fn);
+    if (nlhs > 2) plhs[2] = scalar((double)pos);
+    if (nlhs > 3) {
+        plhs[3] = mxCreateDoubleMatrix(1, (mwSize)nb, mxREAL);
+        for (k = 0; k < (mwSize)nb; ++k) REAL_PTR(plhs[3])[k] = row[GSMCAL_C_FN + k];
+    }
+    if (nlhs > 4) {
+        plhs[4] = mxCreateDoubleMatrix(1, (mwSize)nb, mxREAL);
+        for (k = 0; k < (mwSize)nb; ++k) REAL_PTR(plhs[4])[k] = row[GSMCAL_C_OK + k];
+    }
 
 #elif defined(GSMCAL_FN_CW_check)
     /* r = CW_check(s)     CW_check.m:6-8: s a complex vector of N >= 2 samples (raw2iq's output, check_CW_samples_loss_tcp.m:70,

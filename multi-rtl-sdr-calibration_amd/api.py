@@ -17,6 +17,7 @@ sentinel returns (scalar -1.0 / inf, pos_info = [[-1, -1]]) so that tests read l
     FCCH_demod(s,pos_info,ov,carrier_freq)                           FCCH_demod.m:5 (what it prints, returned as a dict)
     [idx,r,carrier_ppm] = BCCH_demod(s,pos_info,normal_training_sequence,ov,carrier_freq)     BCCH_demod.m:5 (a dict)
     ppm_out = total_ppm_calculation(ppm_in)
+and, without a counterpart in the reference (its SCH_demod.m returns nothing): SCH_decode(s,pos_info,sch_training_sequence,ov).
 
 Everything computes on the GPU through the C ABI; there is no CPU fallback.
 """
@@ -29,7 +30,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BCCH_COLS, CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, SCH_COLS, CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -464,6 +465,46 @@ def BCCH_demod(s, pos_info, normal_training_sequence, oversampling_ratio, carrie
     return out
 
 
+def _sch_template_in(sch_training_sequence):
+    t = np.ascontiguousarray(np.asarray(sch_training_sequence, dtype=np.complex128).ravel())
+    return t, len(t)
+
+
+def SCH_decode(s, pos_info, sch_training_sequence, oversampling_ratio, ctx=None, want_soft=False):
+    """SCH_decode(s, pos_info, sch_training_sequence, ov) -- the project's own function (include/gsmcal.h; not a
+    port of SCH_demod.m): the BSIC and the GSM frame number the SCH bursts of pos_info carry.  ov 2, 4 or 8.  Returns None when
+    pos_info is all -1, otherwise a dict: `status` (0, or 14 = fewer than two bursts decode consistently), `bsic`, `fn_anchor`,
+    `pos_anchor` (-1 at status 14), `num_sch`, `num_ok`, `num_consistent`, `mean_slope`, per SCH burst `ok`, `bsic_b`, `fn`,
+    `ts_err`, `corrected`, `slope`, `amp` (NaN for a burst that was not evaluated), `u` (num_sch, 39) uint8 -- the decoded words
+    -- and with want_soft `soft` (num_sch, 148); `row` is the (SCH_COLS,) table row sch_decode_batch holds for this stream."""
+    ctx = ctx or default_context()
+    buf, n = _r_in(s)
+    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
+    rows = pi.shape[0]
+    pic = np.ascontiguousarray(pi.T)
+    ts, len_ts = _sch_template_in(sch_training_sequence)
+    bsic, fn, pos = C.c_int(), C.c_long(), C.c_long()
+    row = np.full(SCH_COLS, np.nan)
+    soft = np.empty((MAX_HITS, 148)) if want_soft else None
+    u = np.empty((MAX_HITS, 39), dtype=np.uint8)
+    rc = ctx.check(ctx.lib.gsmcal_SCH_decode(ctx.h, _dp(buf) if buf is not None else None, n, _dp(pic), rows, rows, _dp(ts), len_ts,
+                                             int(oversampling_ratio), C.byref(bsic), C.byref(fn), C.byref(pos), _dp(row),
+                                             _dp(soft) if want_soft else None, u.ctypes.data_as(_lib.c_u8_p)), "SCH_decode")
+    _say(ctx)
+    if rc == _lib.S_POST_NO_POS:
+        return None
+    t = sch_rows(row)
+    k = min(int(t["num_sch"][0]), MAX_HITS) if rc >= 0 else 0
+    out = {"status": rc, "bsic": bsic.value, "fn_anchor": fn.value, "pos_anchor": pos.value, "num_sch": int(t["num_sch"][0]),
+           "num_ok": int(t["num_ok"][0]), "num_consistent": int(t["num_consistent"][0]), "mean_slope": float(t["mean_slope"][0]),
+           "u": u[:k].copy(), "row": row}
+    for name in ("ok", "bsic_b", "fn", "ts_err", "corrected", "slope", "amp"):
+        out[name] = t[name][0, :k].copy()
+    if want_soft:
+        out["soft"] = soft[:k].copy()
+    return out
+
+
 def total_ppm_calculation(ppm_in):
     lib = _lib.load()
     p = np.ascontiguousarray(np.atleast_1d(np.asarray(ppm_in, dtype=np.float64)))
@@ -697,6 +738,72 @@ def bcch_demod_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio
     ctx.check(ctx.lib.gsmcal_bcch_demod_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
                                                   int(d), int(oversampling_ratio), _dp(ts), len_ts, _dp(cf), C.c_void_p(d_out),
                                                   opt(d_corr), opt(d_r_out), opt(d_r_len_out)), "bcch_demod_batch_dev")
+
+
+SCH_FIELDS = ("num_sch", "num_ok", "num_consistent", "bsic", "fn_anchor", "pos_anchor", "status", "mean_slope")   # columns 0..7
+
+
+def sch_rows(table):
+    """(D, SCH_COLS) table of sch_decode_batch[_dev] -> dict of its columns (ok, bsic_b, fn, ts_err, corrected, slope, amp:
+    (D, MAX_HITS), NaN for unused entries and for bursts that were not evaluated)."""
+    t = np.asarray(table).reshape(-1, SCH_COLS)
+    out = {k: t[:, i] for i, k in enumerate(SCH_FIELDS)}
+    for j, name in enumerate(("ok", "bsic_b", "fn", "ts_err", "corrected", "slope", "amp")):
+        out[name] = t[:, 8 + j * MAX_HITS: 8 + (j + 1) * MAX_HITS]
+    return out
+
+
+def sch_alignment(rows, oversampling_ratio, ref=0):
+    """Per stream of an SCH_decode table (or of sch_rows' dict), the sample offset of its frame clock against stream `ref` at a
+    common frame number: pos_anchor[d] - pos_anchor[ref] - wrap(fn_anchor[d] - fn_anchor[ref]) * 1250 * ov, the frame difference
+    wrapped into +-half a hyperframe.  NaN for a stream whose status is not 0 (for all of them when `ref`'s is not)."""
+    t = rows if isinstance(rows, dict) else sch_rows(rows)
+    good = t["status"] == 0
+    out = np.full(len(good), np.nan)
+    if not good[ref]:
+        return out
+    half = _lib.HYPERFRAME // 2
+    dfn = (t["fn_anchor"][good] - t["fn_anchor"][ref] + half) % _lib.HYPERFRAME - half
+    out[good] = t["pos_anchor"][good] - t["pos_anchor"][ref] - dfn * 1250.0 * oversampling_ratio
+    return out
+
+
+def sch_decode_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, sch_training_sequence, ctx=None, want_soft=False,
+                     want_u=False):
+    """SCH_decode for D streams, on what calibrate_batch(..., want_r=True) returns (as bcch_demod_batch) plus the SCH template
+    (64*ov samples; only its length is looked at).  Returns the (D, SCH_COLS) table (sch_rows names its columns; per-row outcomes
+    are in its status column) -- or, with want_soft / want_u, a dict: "table", "soft" (D, MAX_HITS, 148), "u" (D, MAX_HITS, 39)
+    uint8 (255 where no burst was evaluated)."""
+    ctx = ctx or default_context()
+    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
+    d, stride = r.shape
+    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
+    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
+    if len(rl) != d:
+        raise ValueError("r_len must have one entry per stream")
+    ts, len_ts = _sch_template_in(sch_training_sequence)
+    out = np.empty((d, SCH_COLS))
+    soft = np.empty((d, MAX_HITS, 148)) if want_soft else None
+    u = np.empty((d, MAX_HITS, 39), dtype=np.uint8) if want_u else None
+    ctx.check(ctx.lib.gsmcal_sch_decode_batch(ctx.h, _dp(r), stride, rl.ctypes.data_as(_lib.c_long_p), _dp(pi), d,
+                                              int(oversampling_ratio), _dp(ts), len_ts, _dp(out), _dp(soft) if want_soft else None,
+                                              u.ctypes.data_as(_lib.c_u8_p) if want_u else None), "sch_decode_batch")
+    if not (want_soft or want_u):
+        return out
+    return {"table": out, "soft": soft, "u": u}
+
+
+def sch_decode_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio, sch_training_sequence, d_out, d_soft=None,
+                         d_u=None, ctx=None):
+    """Device-pointer form of sch_decode_batch: only enqueues on the context's stream, e.g. directly behind calibrate_batch_dev on
+    its d_r_correct / d_r_len / d_pos_info (ctx.sync() before reading).  d_out: [d][SCH_COLS] doubles; optional d_soft:
+    [d][MAX_HITS][148] doubles, d_u: [d][MAX_HITS][39] bytes.  Device or pinned host memory."""
+    ctx = ctx or default_context()
+    ts, len_ts = _sch_template_in(sch_training_sequence)
+    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    ctx.check(ctx.lib.gsmcal_sch_decode_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
+                                                  int(d), int(oversampling_ratio), _dp(ts), len_ts, C.c_void_p(d_out), opt(d_soft),
+                                                  opt(d_u)), "sch_decode_batch_dev")
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

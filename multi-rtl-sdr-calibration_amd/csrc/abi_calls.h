@@ -890,6 +890,90 @@ int gsmcal_BCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* po
     return status;
 }
 
+// ---- SCH_decode: the BSIC and the frame number in the SCH bursts -----------------------------------------
+// k_sch_decode (one wave per burst slot and stream) + k_sch_finish (one wave per stream) on the context's stream, in sd_part;
+// nothing of the lanes or of the chain's state is touched.
+static int sch_decode_args(gsmcal_ctx* c, int ov, const double* ts, int len_ts) {
+    if (ov != 2 && ov != 4 && ov != 8) { c->err = "SCH_decode: oversampling ratios 2, 4 and 8 only"; return GSMCAL_E_UNSUPPORTED; }
+    if (!ts || len_ts != 64 * ov) { c->err = "SCH_decode: the template must be 64*oversampling_ratio samples long"; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+int gsmcal_sch_decode_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
+                                int ov, const double* sch_ts, int len_ts, double* d_out, double* d_soft, unsigned char* d_u) {
+    if (!c || !d_r || !d_r_len || !d_pos_info || !d_out || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    RET_IF(sch_decode_args(c, ov, sch_ts, len_ts));
+    ENTER(c);
+    c->cur = &c->lanes[0];                                      // the context's stream; the lane's buffers are not touched
+    RET_IF(ensure(c, c->sd_part, (size_t)d * MAXH * SD_PART * sizeof(double)));
+    double* part = (double*)c->sd_part.p;
+    for_capture_chunks(d, [&](long lo, int S) {
+        LAUNCH(c, k_sch_decode, dim3(MAXH, S), dim3(64), 0, (const cplx*)d_r + (size_t)lo * stride, stride, d_r_len + lo,
+               d_pos_info + (size_t)lo * 2 * MAXROWS, ov, part + (size_t)lo * MAXH * SD_PART,
+               d_soft ? d_soft + (size_t)lo * MAXH * 148 : nullptr, d_u ? d_u + (size_t)lo * MAXH * 39 : nullptr);
+    });
+    LAUNCH(c, k_sch_finish, dim3(d), dim3(64), 0, d_r_len, stride, d_pos_info, ov, (const double*)part, d_out);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_sch_decode_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
+                            const double* sch_ts, int len_ts, double* out, double* soft, unsigned char* u) {
+    if (!c || !r || !r_len || !pos_info || !out || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    RET_IF(sch_decode_args(c, ov, sch_ts, len_ts));
+    ENTER(c);
+    const Stage io[] = {STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),
+                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
+                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
+                        STAGE(sd_out, (size_t)d * GSMCAL_SCH_COLS * sizeof(double), nullptr, out, 0),
+                        STAGE(sd_soft, soft ? (size_t)d * MAXH * 148 * sizeof(double) : 0, nullptr, soft, 0),
+                        STAGE(sd_u, u ? (size_t)d * MAXH * 39 : 0, nullptr, u, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_sch_decode_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d, ov,
+                                       sch_ts, len_ts, (double*)c->sd_out.p, soft ? (double*)c->sd_soft.p : nullptr,
+                                       u ? (unsigned char*)c->sd_u.p : nullptr));
+    return stage_down(c, io);
+}
+
+int gsmcal_SCH_decode(gsmcal_ctx* c, const double* s, long len, const double* pos_info, int rows, int ld, const double* sch_ts,
+                      int len_ts, int ov, int* bsic, long* fn_anchor, long* pos_anchor, double* table_row, double* soft,
+                      unsigned char* u) {
+    if (!c || !pos_info || rows < 1 || ld < rows) return GSMCAL_E_ARG;
+    RET_IF(sch_decode_args(c, ov, sch_ts, len_ts));
+    ENTER(c);
+    if (bsic) *bsic = -1;
+    if (fn_anchor) *fn_anchor = -1;
+    if (pos_anchor) *pos_anchor = -1;
+    c->report.clear();
+    std::vector<double> row(GSMCAL_SCH_COLS, NAN);
+    bool all_m1 = true;
+    for (int i = 0; i < rows; ++i) all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
+    if (all_m1) {                                               // nothing to read: the batch form's row for such a stream
+        row[GSMCAL_C_NUM_SCH] = row[GSMCAL_C_NUM_OK] = row[GSMCAL_C_NUM_CONSISTENT] = 0.0;
+        row[GSMCAL_C_BSIC] = row[GSMCAL_C_FN_ANCHOR] = row[GSMCAL_C_POS_ANCHOR] = -1.0;
+        row[GSMCAL_C_STATUS] = GSMCAL_S_POST_NO_POS;
+        if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
+        if (soft) std::fill(soft, soft + (size_t)MAXH * 148, NAN);
+        if (u) memset(u, 255, (size_t)MAXH * 39);
+        return GSMCAL_S_POST_NO_POS;
+    }
+    if (!s || len < 1) return GSMCAL_E_ARG;
+    if (rows > MAXROWS) return GSMCAL_E_CAPACITY;
+    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
+    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
+    RET_IF(gsmcal_sch_decode_batch(c, s, len, &len, pi.data(), 1, ov, sch_ts, len_ts, row.data(), soft, u));
+    if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
+    const int status = (int)row[GSMCAL_C_STATUS];
+    if (status < 0) return status;
+    if (status == 0) {
+        if (bsic) *bsic = (int)row[GSMCAL_C_BSIC];
+        if (fn_anchor) *fn_anchor = (long)row[GSMCAL_C_FN_ANCHOR];
+        if (pos_anchor) *pos_anchor = (long)row[GSMCAL_C_POS_ANCHOR];
+    }
+    c->report = report_sch_decode(row.data());
+    return status;
+}
+
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out) {
     if (!ppm_in || !ppm_out || n < 1) return GSMCAL_E_ARG;

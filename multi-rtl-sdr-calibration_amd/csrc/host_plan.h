@@ -58,6 +58,9 @@ struct CtxBufs {
     // BCCH_demod (gsmcal_BCCH_demod, gsmcal_bcch_demod_batch*), on top of FCCH_demod's buffers: the templates, the correlations and
     // window flags per (stream, burst slot), and the host wrapper's staging of the table, the correlations, r and its lengths
     DevBuf bc_ts, bc_corr, bc_flag, bc_out, bc_corr_out, bc_r, bc_rlen;
+    // SCH_decode (gsmcal_SCH_decode, gsmcal_sch_decode_batch*): the per-burst records, and the host wrapper's staging of the table,
+    // the soft values and the decoded words (its inputs go through fd_in / fd_len / fd_pos)
+    DevBuf sd_part, sd_out, sd_soft, sd_u;
     // sub-band power (gsmcal_subband_power_batch*).  sb_taps: one modulated tap row per distinct phase_rotate value, built on the
     // host; sb_idx: the [capture][slot] table into them
     DevBuf sb_taps, sb_idx, sb_state, sb_part;
@@ -66,7 +69,7 @@ struct CtxBufs {
     DevBuf cw_state, cw_part, cw_rec, cw_mean, cw_in, cw_r;
     ALL_BUFS(CtxBufs, &coef, &ts, &cf, &table, &snrhit, &arr_in, &arr_out, &posinfo, &rlen, &misc, &tw, &csum_head, &tw_sch, &stage_raw,
              &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &bc_ts, &bc_corr, &bc_flag, &bc_out,
-             &bc_corr_out, &bc_r, &bc_rlen, &sb_taps, &sb_idx,
+             &bc_corr_out, &bc_r, &bc_rlen, &sd_part, &sd_out, &sd_soft, &sd_u, &sb_taps, &sb_idx,
              &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r)
 };
 

@@ -538,3 +538,243 @@ __global__ void __launch_bounds__(256) k_bcch_rotate(const cplx* __restrict__ r,
         y[n] = cmul(x[n], make_double2(cs, sn));
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// SCH_decode -- the payload of the SCH bursts: BSIC and GSM frame number.  The project's own function: SCH_demod.m
+// has no outputs and demodulates with Communications Toolbox code, so there is nothing to be in parity with; the definition is
+// DESIGN 16's and tests/sch_decode_ref.py restates it line by line.
+//
+// k_sch_decode: grid (MAXH, D), block 64 -- one wave per SCH burst slot.  The wave ranks the type-1 rows of its stream's pos_info
+// from ballots and takes the blockIdx.x-th (1-based start p).  delta = (5 ov - 1) div 2.
+//   1  y_k = s(p + k ov + delta) (-j)^k, k = 3..144: 142 strided reads, rotated by a swap and a negation, kept in LDS.  A burst
+//      whose reads leave the stream, or whose p is NaN or < 1, is not evaluated (decided before a sample is read).
+//   2  lane i holds y_{42+i} a_i, a_i = 1 - 2 SCH_TRAINING_BITS[i]; five xor-shuffle steps inside each half of the wave leave h1
+//      in lanes 0..31 and h2 in lanes 32..63: one fixed order.  h = h1 + h2, slope = angle(h2 conj(h1)) / 32, amp = |h| / 64.
+//   3  soft_k = Re(y_k conj(h)/|h| exp(-j slope (k - 73.5))) for k = 3..144, in LDS.
+//   4  the 16-state Viterbi decoder over soft[3..41], soft[106..144]: lane (state) = u(k-1)<<3 | u(k-2)<<2 | u(k-3)<<1 | u(k-4)
+//      (every group of 16 lanes runs the same trellis); per step two additions per candidate -- (+-soft[2k]) + (+-soft[2k+1]),
+//      then path metric + that: no product, nothing contracts -- a strict > that keeps the candidate whose older bit is 0, and
+//      the survivor's 39-bit history in one 64-bit register, taken from the predecessor lane by __shfl (register exchange: no
+//      traceback memory, no atomics).  Start in state 0 (the others at -inf), the answer is state 0's history.
+//   5  ts_err and corrected from two ballots; CRC, tail bits and the fields on lane 0 (SD_INFO_MAP is the bit map, the one
+//      table to pin against a capture).
+// part[s][slot][SD_PART] = {evaluated, ok, bsic, fn, ts_err, corrected, slope, amp}; every block writes its record.  Optional:
+// soft_out[s][slot][148] (NaN outside 3..144 and for a slot that was not evaluated), u_out[s][slot][39] bytes (255 likewise).
+// ------------------------------------------------------------------------------------------------
+#define SD_PART 8
+#define SD_TRAINING_MASK 0xd86ea2b4f020469dull   /* bit i = SCH_TRAINING_BITS[i] (gsm_SCH_training_sequence_gen.m:17-19) */
+#define SD_HYPERFRAME 2715648L
+#define SD_CRC_POLY 0x575u                       /* g(D) = D^10 + D^8 + D^6 + D^5 + D^4 + D^2 + 1 */
+
+enum { SD_BSIC = 0, SD_T1 = 1, SD_T2 = 2, SD_T3P = 3 };
+// information bit d(i) = bit SD_INFO_MAP[i][1] of field SD_INFO_MAP[i][0] (GSM 04.08 9.1.30, 05.03 4.7; synth.SCH_INFO_MAP)
+__device__ const unsigned char SD_INFO_MAP[25][2] = {
+    {SD_T1, 9}, {SD_T1, 10}, {SD_BSIC, 0}, {SD_BSIC, 1}, {SD_BSIC, 2}, {SD_BSIC, 3}, {SD_BSIC, 4}, {SD_BSIC, 5},
+    {SD_T1, 1}, {SD_T1, 2}, {SD_T1, 3}, {SD_T1, 4}, {SD_T1, 5}, {SD_T1, 6}, {SD_T1, 7}, {SD_T1, 8},
+    {SD_T3P, 1}, {SD_T3P, 2}, {SD_T2, 0}, {SD_T2, 1}, {SD_T2, 2}, {SD_T2, 3}, {SD_T2, 4}, {SD_T1, 0}, {SD_T3P, 0}};
+
+__device__ __forceinline__ unsigned long long sd_shfl_u64(unsigned long long v, int src) {
+    const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src, 64), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ int sd_soft_index(int j) { return j < 39 ? 3 + j : 67 + j; }      // coded bit c(j) -> burst symbol
+__device__ __forceinline__ unsigned sd_u(unsigned long long u, int k) { return k < 0 ? 0u : (unsigned)(u >> k) & 1u; }
+
+__global__ void __launch_bounds__(64) k_sch_decode(const cplx* __restrict__ r, long stride, const long* __restrict__ r_len,
+                                                   const double* __restrict__ pos_info, int ov, double* __restrict__ part,
+                                                   double* __restrict__ soft_out, unsigned char* __restrict__ u_out) {
+    __shared__ cplx ys[148];
+    __shared__ double soft[148];
+    const int s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double* out = part + ((size_t)s * MAXH + b) * SD_PART;
+    const long len = r_len[s] < stride ? r_len[s] : stride;
+    const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
+    // ---- the b-th type-1 row ----
+    constexpr int NCH = (MAXROWS + 63) / 64;
+    int n1 = 0, row = -1;
+    for (int c = 0; c < NCH; ++c) {
+        const int i = c * 64 + lane;
+        const bool is1 = i < MAXROWS && pi[MAXROWS + i] == 1.0;
+        const unsigned long long m = __ballot(is1);
+        const unsigned long long sel = __ballot(is1 && n1 + __popcll(m & ((1ull << lane) - 1ull)) == b);
+        if (sel) row = c * 64 + __ffsll((long long)sel) - 1;
+        n1 += __popcll(m);
+    }
+    const int dl = (5 * ov - 1) / 2;
+    const double spd = row >= 0 ? pi[row] : 0.0;
+    // p NaN or < 1, or symbol 144 behind the last sample: not evaluated (wave-uniform)
+    if (len < 1 || row < 0 || n1 > MAXH || !(spd >= 1.0) || !(spd + (double)(144 * ov + dl) <= (double)len)) {
+        if (lane == 0) out[0] = 0.0;
+        else if (lane < SD_PART) out[lane] = nan;
+        if (soft_out)
+            for (int k = lane; k < 148; k += 64) soft_out[((size_t)s * MAXH + b) * 148 + k] = nan;
+        if (u_out && lane < 39) u_out[((size_t)s * MAXH + b) * 39 + lane] = 255;
+        return;
+    }
+    // ---- 1  the 142 symbols, derotated ----
+    const cplx* x = r + (size_t)s * stride + ((long)spd - 1 + dl);
+    for (int k = 3 + lane; k <= 144; k += 64) {
+        const cplx v = x[(long)k * ov];
+        const int q = k & 3;                                       // (-j)^k: 1, -j, -1, j
+        ys[k] = q == 0 ? v : q == 1 ? make_double2(v.y, -v.x) : q == 2 ? make_double2(-v.x, -v.y) : make_double2(-v.y, v.x);
+    }
+    __syncthreads();
+    // ---- 2  the two half-sums over the training sequence ----
+    const bool tbit = (SD_TRAINING_MASK >> lane) & 1ull;
+    double hr = tbit ? -ys[42 + lane].x : ys[42 + lane].x, hi = tbit ? -ys[42 + lane].y : ys[42 + lane].y;
+    for (int off = 16; off > 0; off >>= 1) {
+        hr += __shfl_xor(hr, off, 64);
+        hi += __shfl_xor(hi, off, 64);
+    }
+    const double h1r = __shfl(hr, 0, 64), h1i = __shfl(hi, 0, 64), h2r = __shfl(hr, 32, 64), h2i = __shfl(hi, 32, 64);
+    const double hx = h1r + h2r, hy = h1i + h2i;
+    const double mag = hypot(hx, hy);
+    const double slope = atan2(h2i * h1r - h2r * h1i, h2r * h1r + h2i * h1i) / 32.0;
+    const double amp = mag / 64.0;
+    const cplx w = make_double2(hx / mag, -hy / mag);               // conj(h)/|h|
+    // ---- 3  the soft values ----
+    for (int k = 3 + lane; k <= 144; k += 64) {
+        double sn, cs;
+        sincos(slope * ((double)k - 73.5), &sn, &cs);
+        const cplx q = cmul(w, make_double2(cs, -sn));
+        soft[k] = ys[k].x * q.x - ys[k].y * q.y;
+    }
+    __syncthreads();
+    // ---- 4  the trellis: this lane's state and its two predecessors (older bit 0, older bit 1) ----
+    const int ns = lane & 15, bit = ns >> 3, p0 = (ns & 7) << 1, p1 = p0 | 1;
+    const bool a0 = (bit ^ (p0 >> 1) ^ p0) & 1, a1 = (a0 ^ (p0 >> 3)) & 1;      // c(2k), c(2k+1) coming from p0
+    const bool b0 = (bit ^ (p1 >> 1) ^ p1) & 1, b1 = (b0 ^ (p1 >> 3)) & 1;      // ... from p1
+    double pm = ns == 0 ? 0.0 : -__builtin_huge_val();
+    unsigned long long hist = 0;
+    for (int k = 0; k < 39; ++k) {
+        const double s0 = soft[sd_soft_index(2 * k)], s1 = soft[sd_soft_index(2 * k + 1)];
+        const double bm0 = (a0 ? -s0 : s0) + (a1 ? -s1 : s1);
+        const double bm1 = (b0 ? -s0 : s0) + (b1 ? -s1 : s1);
+        const double c0 = __shfl(pm, p0, 64) + bm0, c1 = __shfl(pm, p1, 64) + bm1;
+        const unsigned long long g0 = sd_shfl_u64(hist, p0), g1 = sd_shfl_u64(hist, p1);
+        const bool take = c1 > c0;                                 // strict: the first candidate stays
+        pm = take ? c1 : c0;
+        hist = (take ? g1 : g0) | ((unsigned long long)bit << k);
+    }
+    const unsigned long long u = sd_shfl_u64(hist, 0);             // end in state 0: u(k) = bit k
+    // ---- 5  hard errors in the training bits; hard channel bits against the re-encoded word ----
+    const int ts_err = __popcll(__ballot((soft[42 + lane] < 0.0) != tbit));
+    int corrected = 0;
+    for (int j0 = 0; j0 < 78; j0 += 64) {                          // (uniform)
+        const int j = j0 + lane, k = j >> 1;
+        bool differs = false;
+        if (j < 78) {
+            const unsigned c = sd_u(u, k) ^ sd_u(u, k - 3) ^ sd_u(u, k - 4) ^ ((j & 1) ? sd_u(u, k - 1) : 0u);
+            differs = (soft[sd_soft_index(j)] < 0.0) != (c != 0u);
+        }
+        corrected += __popcll(__ballot(differs));
+    }
+    if (soft_out)
+        for (int k = lane; k < 148; k += 64) soft_out[((size_t)s * MAXH + b) * 148 + k] = k >= 3 && k <= 144 ? soft[k] : nan;
+    if (u_out && lane < 39) u_out[((size_t)s * MAXH + b) * 39 + lane] = (unsigned char)sd_u(u, lane);
+    if (lane == 0) {
+        unsigned reg = 0;                                          // u(0..34) divided by g(D): the remainder must be all ones
+        for (int k = 0; k < 35; ++k) {
+            reg = (reg << 1) | sd_u(u, k);
+            if (reg & 0x400u) reg ^= SD_CRC_POLY;
+        }
+        int f[4] = {0, 0, 0, 0};
+        for (int i = 0; i < 25; ++i) f[SD_INFO_MAP[i][0]] |= (int)sd_u(u, i) << SD_INFO_MAP[i][1];
+        const int t3 = 10 * f[SD_T3P] + 1;
+        const long fn = 1326L * f[SD_T1] + 51L * (((t3 - f[SD_T2]) % 26 + 26) % 26) + t3;
+        const bool ok = reg == 0x3ffu && (u >> 35) == 0ull && f[SD_T3P] <= 4 && f[SD_T2] <= 25;
+        out[0] = 1.0;
+        out[1] = ok ? 1.0 : 0.0;
+        out[2] = ok ? (double)f[SD_BSIC] : nan;
+        out[3] = ok ? (double)fn : nan;
+        out[4] = (double)ts_err;
+        out[5] = (double)corrected;
+        out[6] = slope;
+        out[7] = amp;
+    }
+}
+
+// k_sch_finish: one wave per stream, grid D, block 64.  out[s] = one row of GSMCAL_SCH_COLS doubles (GSMCAL_C_*), written here and
+// nowhere else.  Lane i holds the i-th type-1 row.  The consistency rule: among the ok bursts c_i counts the ok bursts j (i
+// included) with bsic_j == bsic_i and (fn_j - fn_i - round((p_j - p_i) / (1250 ov))) mod 2 715 648 == 0 (round: half away from
+// zero, MATLAB's); the anchor is the smallest i with the largest c_i; status 0 iff c_anchor >= 2 -- one pass of a 10-bit CRC is
+// not evidence -- otherwise GSMCAL_S_SCH_NO_DECODE with bsic, fn_anchor, pos_anchor = -1.
+//   r_len < 1 or every element of pos_info -1        status GSMCAL_S_POST_NO_POS, num_sch 0
+//   more than MAXH type-1 rows                       status GSMCAL_E_CAPACITY, nothing evaluated
+// mean_slope: the mean of slope[] over the ok bursts, summed left to right; NaN without one.
+__global__ void __launch_bounds__(64) k_sch_finish(const long* __restrict__ r_len, long stride, const double* __restrict__ pos_info,
+                                                   int ov, const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double pos[MAXH];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
+    const double* ps = part + (size_t)s * MAXH * SD_PART;
+    double* o = out + (size_t)s * GSMCAL_SCH_COLS;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    constexpr int NCH = (MAXROWS + 63) / 64;
+    int n1 = 0;
+    unsigned not_m1 = 0;
+    for (int c = 0; c < NCH; ++c) {
+        const int i = c * 64 + lane;
+        const double p = i < MAXROWS ? pi[i] : -1.0, t = i < MAXROWS ? pi[MAXROWS + i] : -1.0;
+        not_m1 += (p != -1.0) || (t != -1.0);
+        const unsigned long long m = __ballot(t == 1.0);
+        const int rank = n1 + __popcll(m & ((1ull << lane) - 1ull));
+        if (t == 1.0 && rank < MAXH) pos[rank] = p;
+        n1 += __popcll(m);
+    }
+    not_m1 = wave_sum_u32(not_m1);
+    __syncthreads();
+    const long len = r_len[s] < stride ? r_len[s] : stride;
+    int status = 0, nb = n1;
+    if (len < 1 || not_m1 == 0) { status = GSMCAL_S_POST_NO_POS; nb = 0; }
+    else if (nb > MAXH) status = GSMCAL_E_CAPACITY;
+    const bool mine = status == 0 && lane < nb;
+    const bool ev = mine && ps[lane * SD_PART] == 1.0;
+    const bool ok = ev && ps[lane * SD_PART + 1] == 1.0;
+    const double bsic = ok ? ps[lane * SD_PART + 2] : nan, fnd = ok ? ps[lane * SD_PART + 3] : nan;
+    const long fn = ok ? (long)fnd : 0;
+    const double p = mine ? pos[lane] : 0.0, slope = ev ? ps[lane * SD_PART + 6] : nan;
+    const double frame = 1250.0 * (double)ov;
+    int cnt = 0, num_ok = 0;
+    double acc = 0.0;
+    for (int j = 0; j < MAXH; ++j) {                               // (uniform)
+        const bool okj = __shfl((int)ok, j, 64) != 0;
+        const double bj = __shfl(bsic, j, 64), pj = __shfl(p, j, 64), sj = __shfl(slope, j, 64);
+        const long fj = (long)sd_shfl_u64((unsigned long long)fn, j);
+        if (okj) { ++num_ok; acc += sj; }
+        if (ok && okj && bj == bsic) {
+            const long dfr = (long)round((pj - p) / frame);
+            const long dd = (fj - fn - dfr) % SD_HYPERFRAME;
+            cnt += dd == 0;
+        }
+    }
+    int best = 0, anchor = -1;
+    for (int i = 0; i < MAXH; ++i) {                               // the smallest i with the largest c_i
+        const int ci = __shfl(cnt, i, 64);
+        if (ci > best) { best = ci; anchor = i; }
+    }
+    if (status == 0 && best < 2) status = GSMCAL_S_SCH_NO_DECODE;
+    if (lane < MAXH) {
+        o[GSMCAL_C_OK + lane] = ev ? (ok ? 1.0 : 0.0) : nan;
+        o[GSMCAL_C_BSIC_B + lane] = bsic;
+        o[GSMCAL_C_FN + lane] = fnd;
+        o[GSMCAL_C_TS_ERR + lane] = ev ? ps[lane * SD_PART + 4] : nan;
+        o[GSMCAL_C_CORRECTED + lane] = ev ? ps[lane * SD_PART + 5] : nan;
+        o[GSMCAL_C_SLOPE + lane] = slope;
+        o[GSMCAL_C_AMP + lane] = ev ? ps[lane * SD_PART + 7] : nan;
+    }
+    const int an = anchor < 0 ? 0 : anchor;
+    const double a_bsic = __shfl(bsic, an, 64), a_fn = __shfl(fnd, an, 64), a_pos = __shfl(p, an, 64);
+    if (lane == 0) {
+        const bool good = status == 0;
+        o[GSMCAL_C_NUM_SCH] = (double)nb;
+        o[GSMCAL_C_NUM_OK] = (double)num_ok;
+        o[GSMCAL_C_NUM_CONSISTENT] = (double)best;
+        o[GSMCAL_C_BSIC] = good ? a_bsic : -1.0;
+        o[GSMCAL_C_FN_ANCHOR] = good ? a_fn : -1.0;
+        o[GSMCAL_C_POS_ANCHOR] = good ? a_pos : -1.0;
+        o[GSMCAL_C_STATUS] = (double)status;
+        o[GSMCAL_C_MEAN_SLOPE] = num_ok > 0 ? acc / (double)num_ok : nan;
+    }
+}

@@ -49,6 +49,74 @@ TSC = np.array([
 
 DEFAULT_SEED = 20260101
 
+# ---- the SCH payload (GSM 05.03 section 4.7, 04.08 section 9.1.30): BSIC and reduced frame number ---------------------------
+HYPERFRAME = 2048 * 26 * 51                      # 2 715 648 TDMA frames
+# the bit map, one row per information bit d(0..24): (field, bit of that field).  T1 = FN div 1326 (11 bits), T2 = FN mod 26,
+# T3P = (FN mod 51 - 1) / 10.  Unpinned against a real capture: this table is the one place to pin it.
+SCH_INFO_MAP = (
+    ("T1", 9), ("T1", 10), ("BSIC", 0), ("BSIC", 1), ("BSIC", 2), ("BSIC", 3), ("BSIC", 4), ("BSIC", 5),
+    ("T1", 1), ("T1", 2), ("T1", 3), ("T1", 4), ("T1", 5), ("T1", 6), ("T1", 7), ("T1", 8),
+    ("T3P", 1), ("T3P", 2), ("T2", 0), ("T2", 1), ("T2", 2), ("T2", 3), ("T2", 4), ("T1", 0), ("T3P", 0))
+SCH_CRC_POLY = 0b10101110101                     # g(D) = D^10 + D^8 + D^6 + D^5 + D^4 + D^2 + 1
+SCH_CODED_FIRST, SCH_CODED_SECOND = 3, 106       # burst bits 3..41 carry c(0..38), 106..144 carry c(39..77)
+
+
+def sch_info_bits(bsic, fn):
+    """The 25 information bits d(0..24) of the SCH burst of TDMA frame fn (fn mod 51 in 1, 11, 21, 31, 41)."""
+    bsic, fn = int(bsic), int(fn)
+    t3 = fn % 51
+    if not (0 <= bsic < 64 and 0 <= fn < HYPERFRAME and t3 % 10 == 1 and t3 < 50):
+        raise ValueError("sch_info_bits: bsic 0..63, fn an SCH frame of the hyperframe")
+    val = {"BSIC": bsic, "T1": fn // 1326, "T2": fn % 26, "T3P": (t3 - 1) // 10}
+    return np.array([(val[f] >> b) & 1 for f, b in SCH_INFO_MAP], dtype=np.int8)
+
+
+def sch_fields(d):
+    """d(0..24) -> dict(bsic, t1, t2, t3p, fn); fn = 1326 T1 + 51 ((T3 - T2) mod 26) + T3 with T3 = 10 T3' + 1."""
+    val = {"BSIC": 0, "T1": 0, "T2": 0, "T3P": 0}
+    for bit, (f, b) in zip(np.asarray(d).tolist(), SCH_INFO_MAP):
+        val[f] |= int(bit) << b
+    t3 = 10 * val["T3P"] + 1
+    return {"bsic": val["BSIC"], "t1": val["T1"], "t2": val["T2"], "t3p": val["T3P"],
+            "fn": 1326 * val["T1"] + 51 * ((t3 - val["T2"]) % 26) + t3}
+
+
+def sch_crc_remainder(word):
+    """remainder (10 bits, as an integer, D^9 the top bit) of the bit sequence `word` (first bit = highest power) divided by g(D)"""
+    reg = 0
+    for bit in np.asarray(word).tolist():
+        reg = (reg << 1) | int(bit)
+        if reg & 0x400:
+            reg ^= SCH_CRC_POLY
+    return reg
+
+
+def sch_conv_encode(u):
+    """rate 1/2: c(2k) = u(k)+u(k-3)+u(k-4), c(2k+1) = u(k)+u(k-1)+u(k-3)+u(k-4), u(k<0) = 0"""
+    u = np.asarray(u, dtype=np.int8)
+    z = np.concatenate([np.zeros(4, np.int8), u])
+    c = np.empty(2 * len(u), dtype=np.int8)
+    c[0::2] = z[4:] ^ z[1:-3] ^ z[:-4]
+    c[1::2] = z[4:] ^ z[3:-1] ^ z[1:-3] ^ z[:-4]
+    return c
+
+
+def sch_encode(bsic, fn):
+    """The 78 coded bits c(0..77) of the SCH burst of frame fn: 25 information bits, 10 parity bits (the inverted remainder, so
+    that the 35-bit word leaves all ones), 4 zero tail bits, the rate-1/2 code.  No interleaving."""
+    d = sch_info_bits(bsic, fn)
+    rem = sch_crc_remainder(np.concatenate([d, np.zeros(10, np.int8)])) ^ 0x3FF
+    par = np.array([(rem >> (9 - i)) & 1 for i in range(10)], dtype=np.int8)
+    return sch_conv_encode(np.concatenate([d, par, np.zeros(4, np.int8)]))
+
+
+def sch_plant(bits, bsic, fn):
+    """overwrite the 78 payload bits of the 148 SCH burst bits (in place)"""
+    c = sch_encode(bsic, fn)
+    bits[SCH_CODED_FIRST:SCH_CODED_FIRST + 39] = c[:39]
+    bits[SCH_CODED_SECOND:SCH_CODED_SECOND + 39] = c[39:]
+    return bits
+
 
 def _qfunc(x):
     return 0.5 * np.array([math.erfc(v / math.sqrt(2.0)) for v in np.ravel(x)]).reshape(np.shape(x))
@@ -146,10 +214,23 @@ def _ramp(n_total, n_edge=8):
 _RAMP = _ramp(BURST_BITS * OV)
 
 
-def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0):
+def _sch_payload_args(start_frame, bsic, fn0):
+    """(bsic, fn0) to plant, or None: either argument switches the planted payload on, the other then takes its default"""
+    if bsic is None and fn0 is None:
+        return None
+    bsic, fn0 = (0 if bsic is None else int(bsic)), (int(start_frame) if fn0 is None else int(fn0))
+    if not 0 <= bsic < 64 or not 0 <= fn0 < HYPERFRAME or fn0 % 51 != start_frame:
+        raise ValueError("bsic must be 0..63 and fn0 a frame of the hyperframe with fn0 mod 51 == start_frame")
+    return bsic, fn0
+
+
+def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0, bsic=None, fn0=None):
     """Complex baseband at exactly 8 samples/symbol, num_frames TDMA frames starting at frame
     `start_frame` of the 51-multiframe.  bcch=False gives a traffic-only carrier (no FCCH/SCH).
-    tsc: the training sequence code (0..7) every normal burst carries."""
+    tsc: the training sequence code (0..7) every normal burst carries.
+    bsic / fn0: plant sch_encode(bsic, fn0 + frame) in every SCH burst (fn0 mod 51 == start_frame; the frame number wraps at
+    HYPERFRAME).  The random payload is drawn first and then overwritten, so everything else of the waveform is unchanged."""
+    payload = _sch_payload_args(start_frame, bsic, fn0)
     n = num_frames * FRAME_OV
     x = np.zeros(n, dtype=np.complex128)
     # all bursts of the stream are modulated in one vectorised pass: bits -> (nb, 148)
@@ -168,6 +249,8 @@ def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0):
     bits = np.zeros((nb, nbits), dtype=np.int8)
     for i, k in enumerate(kinds):
         bits[i, PRE:PRE + BURST_BITS] = _burst_bits("N" if k == "I" else k, rng, tsc)
+        if k == "S" and payload is not None:
+            sch_plant(bits[i, PRE:PRE + BURST_BITS], payload[0], (payload[1] + i // 8) % HYPERFRAME)
     prev = np.concatenate([np.zeros((nb, 1), np.int8), bits[:, :-1]], axis=1)
     pre = 1 - np.abs(bits - prev)                       # diff_precode per burst
     a = 2.0 * pre.astype(np.float64) - 1.0
@@ -190,11 +273,14 @@ def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0):
 
 def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
                 sampling_ppm=None, carrier_ppm=None, snr_db=None, carrier_freq=957.4e6,
-                start_frame=None, frac_start=None, tx_key=None, tsc=0):
+                start_frame=None, frac_start=None, tx_key=None, tsc=0, bsic=None, fn0=None):
     """One capture: returns (raw uint8 interleaved I,Q of length 2*num_frames*10000, truth dict).
     tx_key: dongles given the same key receive the SAME transmission (payload, multiframe phase, start instant) through
     their own clocks, carrier offsets and noise -- what gsm_sync_demod.m's inter-dongle phase plot (:151-158) looks at.
-    tsc: the cell's training sequence code (0..7), planted in every normal burst."""
+    tsc: the cell's training sequence code (0..7), planted in every normal burst.
+    bsic / fn0: the SCH payload (ideal_waveform): the cell's BSIC and the GSM frame number of the waveform's first frame, which
+    needs start_frame given with fn0 mod 51 == start_frame.  Left at None the SCH payload stays random and the capture is
+    byte-identical to what it always was."""
     rng = np.random.Generator(np.random.Philox(key=[int(seed), (int(dongle) << 20) ^ int(arfcn)]))
     eps_s = rng.uniform(-80.0, 80.0) if sampling_ppm is None else float(sampling_ppm)
     eps_c = rng.uniform(-40.0, 40.0) if carrier_ppm is None else float(carrier_ppm)
@@ -203,14 +289,14 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     fs0 = rng.uniform(0.0, FRAME_OV) if frac_start is None else float(frac_start)
     n = num_frames * FRAME_OV
     if tx_key is None:
-        ideal = ideal_waveform(num_frames + 2, sf, rng, bcch=bcch, tsc=tsc)
+        ideal = ideal_waveform(num_frames + 2, sf, rng, bcch=bcch, tsc=tsc, bsic=bsic, fn0=fn0)
     else:
         txr = np.random.Generator(np.random.Philox(key=[int(seed) ^ 0x5A5A5A5A, int(tx_key)]))
         if start_frame is None:
             sf = int(txr.integers(0, 51))
         if frac_start is None:
             fs0 = txr.uniform(0.0, FRAME_OV)
-        ideal = ideal_waveform(num_frames + 2, sf, txr, bcch=bcch, tsc=tsc)
+        ideal = ideal_waveform(num_frames + 2, sf, txr, bcch=bcch, tsc=tsc, bsic=bsic, fn0=fn0)
     # the dongle's clock runs (1+eps_s) fast => sample k is taken at ideal time k/(1+eps_s)... the
     # estimator's sign convention (FCCH_fine_correction.m:111-115): observed spacing = ideal*(1+e)
     # means the dongle takes MORE samples per GSM frame, i.e. query ideal time t_k = k/(1+e).
@@ -233,6 +319,8 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     raw = np.clip(np.floor(raw + 0.5), 0, 255).astype(np.uint8)
     truth = {"sampling_ppm": eps_s, "carrier_ppm": eps_c, "snr_db": snr, "start_frame": sf,
              "frac_start": fs0, "carrier_freq": carrier_freq, "bcch": bcch}
+    payload = _sch_payload_args(sf, bsic, fn0) if bcch else None
+    truth["bsic"], truth["fn0"] = payload if payload is not None else (None, None)
     return raw, truth
 
 
