@@ -160,6 +160,18 @@ int gsmcal_devtiming_report(gsmcal_ctx* c) {
             if (n) fprintf(stderr, " %d:%.1f", i, a / n);
         }
         fprintf(stderr, "\n");
+        if (k == KID_COARSE_SCAN) {                        // k_coarse_scan<INL>: SNR rounds computed per workgroup (word 15)
+            int hist[17] = {0}, any = 0;
+            for (int b = 0; b < DEV_STAMP_BLOCKS; ++b) {
+                const unsigned long long* r = &h[((size_t)k * DEV_STAMP_BLOCKS + b) * 16];
+                if (r[0] && r[15] >= 1 && r[15] <= 16) { ++hist[r[15]]; ++any; }
+            }
+            if (any) {
+                fprintf(stderr, "    SNR rounds computed (rounds:workgroups):");
+                for (int i = 1; i <= 16; ++i) if (hist[i]) fprintf(stderr, " %d:%d", i, hist[i]);
+                fprintf(stderr, "\n");
+            }
+        }
     }
     // what the certificate of the last batch left open, and what the chunk sweep handed on
     Lane& L = c->lanes[0];

@@ -987,8 +987,8 @@ int hits_capacity(long len_dec, int dec_ratio) {
     return h;
 }
 
-size_t coarse_scan_lds(long nwin, int mv_len) {
-    return coarse_scan_lds_fixed() + (size_t)(nwin + mv_len + 128) * sizeof(double);
+size_t coarse_scan_lds(long nwin, int mv_len, bool inl = false) {
+    return coarse_scan_lds_fixed(inl) + (size_t)(nwin + mv_len + 128) * sizeof(double);
 }
 
 // Partial tap sums of the head rows (see coarse()): uploaded on the context's stream BEFORE fork_lanes(), so the fork
@@ -1073,7 +1073,7 @@ int coarse(gsmcal_ctx* c, int S, const cplx* d_dec, long stride, long len, int d
             a.snr_g = (double*)c->cur->snrbuf.p;
             c->cur->snr_stride = ntab;
         }
-        LAUNCH(c, k_coarse_scan_inl, dim3(S), dim3(256), lds, (StreamState*)c->cur->state.p, a);
+        LAUNCH(c, k_coarse_scan_inl, dim3(S), dim3(256), coarse_scan_lds(n_first, 10 * fft_len, true), (StreamState*)c->cur->state.p, a);   // 47 584 bytes: three per CU
         CHECK_LAUNCH(c);
         return 0;
     }

@@ -443,7 +443,8 @@ __device__ void d_scan_accept(const StreamState* st, int s, double* snr_numhit, 
                               double* pos_snr, int* counts, const DevParams& P, int lane);   // kernels_estim.h
 
 // ---- k_coarse_scan: first hit + hop walk of FCCH_coarse_position, one workgroup per stream ----
-// grid S, block 256.  LDS: state copy | 64 twiddles | 4 x 36 hop samples | 2 x 11 x 17 hop powers | snr[mv_len + nwin + 64].
+// grid S, block 256.  LDS: state copy | 64 twiddles | 4 x 36 hop samples | 2 x 11 x 17 hop powers | (INL: prefix ring, CS_RING) |
+// snr[mv_len + nwin + 64]: coarse_scan_lds_fixed(INL) + the snr part.
 //
 // (1) First hit, move_fft_snr_runtime_avg.m:30-42.  The loop is serial only through the ROUNDING of sum_snr (two
 // dependent fp64 adds per window); its decisions (snr - sum_snr/mv_len > th) almost never depend on that rounding.
@@ -451,7 +452,9 @@ __device__ void d_scan_accept(const StreamState* st, int s, double* snr_numhit, 
 // These sums differ from the reference's serially rounded ones by at most
 //     (2 nwin + mv_len + 2 per) * 2^-53 * mv_len * V     (every fp64 add errs by <= 2^-53 |result|, |result| <= mv_len V,
 //                                                         V = 1000 >= |snr| checked per window, the seed is 999)
-// i.e. <= 1e-9 on the average for the reference geometry.  A window whose margin to the threshold exceeds `delta`
+// i.e. <= 1e-9 on the average for the reference geometry (the INL form adds in another order: (2 nwin + mv_len) * 2^-53 *
+// mv_len * V for the reference's own rounding as here, and the term derived with that form below for its prefixes: 1.2e-9
+// in all).  A window whose margin to the threshold exceeds `delta`
 // (1e-6 + 4x that bound) is decided for good, and the first decided hit stands if no undecided window precedes it.
 // Otherwise (a margin inside delta, a non-finite SNR) wave 0 replays the reference's running-sum updates in the
 // reference's order, 64 windows at a time: every lane advances the same wave-uniform sum from broadcast LDS reads,
@@ -468,13 +471,31 @@ __device__ void d_scan_accept(const StreamState* st, int s, double* snr_numhit, 
 // (1) the hop decisions carry the same delta check; a decision inside delta repeats the stream with the exact replay.
 // WAVES: minimum waves per SIMD the register allocator must leave room for (2: small batches, 4: four workgroups per CU).
 #define CS_ROW 36
-__host__ __device__ inline size_t coarse_scan_lds_fixed() {
-    return ((sizeof(StreamState) + 15) & ~(size_t)15) + 64 * sizeof(cplx) + 4 * CS_ROW * sizeof(cplx) + (2 * 11 * 17 + 2 * MAXH) * sizeof(double);
+#define CS_RING (2 * 256 + 2 * 4)    // INL: prefixes of the last two rounds (one per window) + their four wave totals
+// inl: the INL form's prefix ring on top (12 368 -> 16 528 bytes; 47 584 with the reference geometry's S, three workgroups per CU)
+__host__ __device__ inline size_t coarse_scan_lds_fixed(bool inl = false) {
+    return ((sizeof(StreamState) + 15) & ~(size_t)15) + 64 * sizeof(cplx) + 4 * CS_ROW * sizeof(cplx) + (2 * 11 * 17 + 2 * MAXH) * sizeof(double) +
+           (inl ? CS_RING * sizeof(double) : 0);
 }
 
 // INL (throughput batches, 16-point windows): the moving search's window SNRs are computed HERE, straight into the LDS copy the
 // scan reads -- k_coarse_snr<true,false>'s arithmetic, value for value -- so the table never makes the trip through HBM and the
 // k_coarse_snr launch in front of this kernel is gone (a.snr_g non-null: it is still written out, for gsmcal_last_batch_snr).
+// The certificate of (1) is applied in the round that computes a window, and the rounds stop behind the first decided hit
+// (the reference stops there too, move_fft_snr_runtime_avg.m:30-42): with C[p] = sum_{i<p} S[i] window j sees
+// C[mv_len + j] - C[j].  A round forms C[mv_len + j] for its 256 windows as (base + totals of the waves in front) + the
+// wave's exclusive scan -- base carried from round to round, exclusive scans and wave totals of the last two rounds kept in
+// an LDS ring, from which C[j] (window j - mv_len: this round or the one before, 999 j inside the seed) is formed by the very
+// same operations.  A C value of round r carries <= 4 r + 11 fp64 adds of magnitude <= sc_total V (4 per earlier round: three
+// for its total, one onto the base; 7 for the exclusive scan, 2 for the waves in front, 2 to put them together), so the
+// average differs from the exactly summed one by <= (8 rounds + 23) 2^-53 V sc_total / mv_len: the second term of cert_delta
+// in this form.  The verdict on rounds <= r is read after round r + 1 has staged its samples, under that round's barrier:
+// hit decided and no undecided window in front of it -- leave (the samples of round r + 1 were requested a round ago and
+// are dropped, round r + 2's are never requested); an undecided window first -- the exact replay decides and may hit later:
+// all remaining rounds, without the test; the kept table (a.snr_g) -- all rounds.  Nothing behind the last computed round is
+// read: the decided hit's average takes S[pred .. pred + mv_len); the replay runs with every round computed or, after a hop
+// decision inside delta, ends at the decided hit, in a 64-window group that lies inside the hit's round; the head windows are
+// redone inside round 0; the hop walk has its own spectra.
 template <int WAVES, bool FFT16, bool REFG = false, bool INL = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) k_coarse_scan(StreamState* __restrict__ sts, CoarseArgs a_in) {
     CoarseArgs a = a_in;
@@ -491,7 +512,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
     cplx* rows = tw + 64;                                 // 4 x CS_ROW samples of the current hop
     double* Pb = (double*)(rows + 4 * CS_ROW);            // [group][window][17]: powers of the hop's 22 windows
     double* hop_sig_base = Pb + 2 * 11 * 17;             // (signal, noise) of the hit each hop settled on
-    double* snr_s = hop_sig_base + 2 * MAXH;
+    double* cs_ring = hop_sig_base + 2 * MAXH;            // (INL) [2][256] exclusive wave scans | [2][4] wave totals
+    double* snr_s = cs_ring + (INL ? CS_RING : 0);
     StreamState* st_g = sts + blockIdx.x;
     const long len = a.len;
     const CoarseGeom g = REFG ? CoarseGeom{16, 160, a.th0, 3594L, 3594L - 15L} : coarse_geom<false>(a);   // (derived here, under the latency of the loads below: with the host's values this kernel ran 1.2 us SLOWER)
@@ -583,36 +605,116 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
             }
     };
     if (!tw_lazy) make_tw();
-    if (INL && FFT16 && !bad && a.mode != 2) {
+    const double cert_V = 1000.0;
+    const int sc_total = mv_len + (int)g.nwin;            // entries of S that windows can see
+    const int sc_per = (sc_total + 255) / 256;            // entries (and windows) per thread
+    // adds behind a prefix value: a thread's chunk + the block scan, or (INL && FFT16, above) the chain through the rounds
+    const double cert_adds = (INL && FFT16) ? 4.0 * (double)((g.nwin + 255) / 256) + 16.0 : (double)sc_per + 32.0;
+    const double cert_delta = 1e-6 + 4.0 * 1.1102230246251565e-16 * cert_V *
+                              ((2.0 * (double)g.nwin + (double)mv_len + 64.0) +
+                               2.0 * cert_adds * (double)sc_total / (double)mv_len);
+    const bool inl_run = INL && FFT16 && !bad && a.mode != 2;
+    if (inl_run) {
         // k_coarse_snr<true, false>: 256 windows per round from the 271 raw samples they cover (the DC term is removed in the
-        // spectrum), the next round's samples requested before this round's spectra; then the head windows again with per-sample
-        // DC removal.  S = [999 x mv_len | snr | 0 x 64] as above.
+        // spectrum), the next round's samples requested before this round's spectra; in round 0 the head windows again with
+        // per-sample DC removal; every round tests its windows (see INL above).  S = [999 x mv_len | snr | 0 x 64] as above.
         const long nwin = g.nwin;
         for (int i = tid; i < mv_len; i += 256) snr_s[i] = 999.0;
         for (int i = tid; i < 64; i += 256) snr_s[mv_len + nwin + i] = 0.0;
+        // the certificate needs window j - mv_len in this round or the one before; otherwise (and in mode 1) the exact replay
+        if (tid == 0) { sh_pred = 0x7fffffff; sh_unc = (a.mode == 0 && mv_len <= 256) ? 0x7fffffff : 0; }
         cplx* xw = rows;                                  // 271 samples: the hop buffers (rows | Pb, 5.3 KB) are not in use yet
         const cplx* sp = s.s;
         const cplx z = make_double2(0.0, 0.0);
         cplx c0 = tid < len ? sp[tid] : z, c1 = (tid < 15 && 256 + tid < len) ? sp[256 + tid] : z;
+        const int lane = tid & 63, wave = tid >> 6;
+        const bool all_rounds = a.snr_g != nullptr;
+        const double inv = 1.0 / (double)mv_len;
+        // totals of the waves in front of wave w, always added in this order: both ends of a window's sum come out of the same operations
+        auto waves_before = [](const double* ws, int w) {
+            double o = 0.0;
+            if (w > 0) o = ws[0];
+            if (w > 1) o += ws[1];
+            if (w > 2) o += ws[2];
+            return o;
+        };
+        bool testing = true;                               // block-uniform: every window so far is a decided miss
+        double cbase = 999.0 * (double)mv_len, cbase_prev = cbase;   // C[mv_len + b0] of this round and of the one before (:11-12; exact)
+#ifdef GSMCAL_DEVTIMING
+        int rounds_done = 0;
+#endif
         for (long b0 = 0; b0 < nwin; b0 += 256) {
             xw[tid] = c0;
             if (tid < 15) xw[256 + tid] = c1;
             __syncthreads();
+            if (testing) {                                 // the verdict on the rounds before this one
+                const int pred = sh_pred;
+                if (sh_unc < pred) testing = false;
+                else if (pred != 0x7fffffff) {
+                    if (!all_rounds) break;
+                    testing = false;
+                }
+            }
             const long nb = b0 + 256;
             if (nb < nwin) {
                 c0 = nb + tid < len ? sp[nb + tid] : z;
                 if (tid < 15) c1 = nb + 256 + tid < len ? sp[nb + 256 + tid] : z;
             }
-            if (b0 + tid < nwin) snr_s[mv_len + b0 + tid] = window_snr16_from(s, xw + tid);
+            const bool inw = b0 + tid < nwin;
+            double v = 0.0;
+            if (inw) {
+                v = window_snr16_from(s, xw + tid);
+                snr_s[mv_len + b0 + tid] = v;
+            }
+            if (b0 == 0 && s.n_head > 0) {                 // (block-uniform) the head windows again, before they are tested
+                __syncthreads();                           // (xw is read no more)
+                cplx* hx = rows;
+                const int nh = s.n_head < 8 ? s.n_head : 8;
+                if (tid < nh + fft_len - 1 && tid < g.n_first) hx[tid] = dv_load(s, tid);
+                __syncthreads();
+                if (tid < nh && tid < nwin) {
+                    v = window_snr16_head(hx + tid, s.floor2);
+                    snr_s[mv_len + tid] = v;
+                }
+            }
+            const int par = (int)(b0 >> 8) & 1;
+            double* ex = cs_ring + par * 256;
+            double* ws = cs_ring + 512 + par * 4;
+            double excl = 0.0;
+            if (testing) {
+                const double inc = wave_scan_incl(v);
+                excl = inc - v;
+                ex[tid] = excl;
+                if (lane == 63) ws[wave] = inc;
+            }
             __syncthreads();
+            if (testing) {
+                const int j = (int)b0 + tid;               // this thread's window
+                const double chi = (cbase + waves_before(ws, wave)) + excl;        // C[mv_len + j]
+                double clo;                                                        // C[j]
+                if (j < mv_len) clo = 999.0 * (double)j;                           // (exact)
+                else {
+                    const int q = j - mv_len, t = q & 255;                         // window q: this round (q >= b0) or the one before
+                    const bool same = q >= (int)b0;
+                    const int p = same ? par : par ^ 1;
+                    clo = ((same ? cbase : cbase_prev) + waves_before(cs_ring + 512 + p * 4, t >> 6)) + cs_ring[p * 256 + t];
+                }
+                const double mg = (v - (chi - clo) * inv) - th;
+                if (inw) {
+                    if (!(fabs(v) <= cert_V) || !(fabs(mg) > cert_delta)) atomicMin(&sh_unc, j);   // (NaN lands here)
+                    else if (mg > 0.0) atomicMin(&sh_pred, j);
+                }
+                cbase_prev = cbase;
+                cbase += ((ws[0] + ws[1]) + ws[2]) + ws[3];
+            }
+#ifdef GSMCAL_DEVTIMING
+            ++rounds_done;
+#endif
         }
-        if (s.n_head > 0) {                               // (block-uniform)
-            cplx* hx = rows;
-            const int nh = s.n_head < 8 ? s.n_head : 8;
-            if (tid < nh + fft_len - 1 && tid < g.n_first) hx[tid] = dv_load(s, tid);
-            __syncthreads();
-            if (tid < nh && tid < nwin) snr_s[mv_len + tid] = window_snr16_head(hx + tid, s.floor2);
-        }
+#ifdef GSMCAL_DEVTIMING
+        if (g_stamps && tid == 0 && blockIdx.x < DEV_STAMP_BLOCKS)       // rounds computed (word 15: below any time stamp, no phase)
+            g_stamps[((size_t)KID_COARSE_SCAN * DEV_STAMP_BLOCKS + blockIdx.x) * 16 + 15] = (unsigned long long)rounds_done;
+#endif
         if (a.snr_g) {
             __syncthreads();
             double* tab = a.snr_g + (size_t)blockIdx.x * a.snr_stride;
@@ -628,8 +730,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
         st->mv_hit_idx = -1.0;
         st->mv_hit_snr = INFINITY;
         sh_hit = 0x7fffffff;
-        sh_pred = 0x7fffffff;
-        sh_unc = 0x7fffffff;
+        if (!inl_run) {                                    // (the rounds above have posted their verdicts)
+            sh_pred = 0x7fffffff;
+            sh_unc = 0x7fffffff;
+        }
         sh_exact = want_cert ? 0 : 1;
         sh_redo = 0;
         if (bad) set_status(st, 3, GSMCAL_E_INDEX);
@@ -637,13 +741,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
     __syncthreads();
     int n = 0;
     CS_STAMP(1);
-    const double cert_V = 1000.0;
-    const int sc_total = mv_len + (int)g.nwin;            // entries of S that windows can see
-    const int sc_per = (sc_total + 255) / 256;            // entries (and windows) per thread
-    const double cert_delta = 1e-6 + 4.0 * 1.1102230246251565e-16 * cert_V *
-                              ((2.0 * (double)g.nwin + (double)mv_len + 64.0) +
-                               2.0 * ((double)sc_per + 32.0) * (double)sc_total / (double)mv_len);
     if (want_cert) {
+      if (!(INL && FFT16)) {
         // window sums from a block-wide prefix scan of S: C[p] = sum_{i<p} S[i] at every thread's chunk start (Cb) plus
         // a partial chunk sum; window j sees C[j+mv_len] - C[j].  (<= sc_per + 32 fp64 adds of magnitude <= sc_total V per
         // C value: the second term of cert_delta.)
@@ -677,6 +776,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
             }
         }
         __syncthreads();
+      }
         if (tid < 64) {
             // the average the decided hit sees (64 lanes + a reduction tree: within the same bound)
             const int pred = sh_pred;
