@@ -26,6 +26,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gsmcal_si.h"   /* gsmcal_si_info, gsmcal_si_fields: the parser of a decoded BCCH block (plain C, header only) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -50,6 +52,7 @@ enum {
     GSMCAL_S_ALL_INF = 12,        /* total_ppm_calculation.m:7-11                                 */
     GSMCAL_S_BCCH_TSC_MIXED = 13, /* BCCH_demod.m:103-105: the first four BCCH bursts disagree     */
     GSMCAL_S_SCH_NO_DECODE = 14,  /* gsmcal_SCH_decode: fewer than two SCH bursts decode consistently */
+    GSMCAL_S_BCCH_NO_DECODE = 15, /* gsmcal_BCCH_decode: no BCCH block passes the Fire code's check   */
     /* < 0: failures */
     GSMCAL_E_ARG = -1,
     GSMCAL_E_HIP = -2,
@@ -66,6 +69,9 @@ enum {
 #define GSMCAL_MAX_BCCH (4 * GSMCAL_MAX_HITS)         /* BCCH bursts (type-2 rows of pos_info) gsmcal_bcch_demod_batch evaluates */
 #define GSMCAL_BCCH_COLS (6 + 4 * GSMCAL_MAX_BCCH)    /* one row of gsmcal_bcch_demod_batch[_dev]: 390 doubles */
 #define GSMCAL_SCH_COLS (8 + 7 * GSMCAL_MAX_HITS)      /* one row of gsmcal_sch_decode_batch[_dev]: 176 doubles */
+#define GSMCAL_SI_COLS (4 + 7 * GSMCAL_MAX_HITS)       /* one row of gsmcal_bcch_decode_batch[_dev]: 172 doubles */
+#define GSMCAL_BLOCK_OCTETS 23                         /* octets of one BCCH block (GSMCAL_SI_OCTETS of gsmcal_si.h) */
+#define GSMCAL_BLOCK_CODED 456                         /* coded bits of one BCCH block */
 
 /* columns of one row of the calibration table (doubles; this row is what ranks all-gather) */
 enum {
@@ -125,6 +131,21 @@ enum {
     GSMCAL_C_AMP = 8 + 6 * GSMCAL_MAX_HITS          /* [GSMCAL_MAX_HITS] |h| / 64                                              */
 };
 
+/* columns of one row of the BCCH_decode table (doubles) */
+enum {
+    GSMCAL_I_NUM_BLOCKS = 0,                        /* type-1 rows of pos_info that four type-2 rows follow (0 at GSMCAL_S_POST_NO_POS) */
+    GSMCAL_I_NUM_OK = 1,                            /* blocks whose decoded word passes the Fire code and the tail check       */
+    GSMCAL_I_STATUS = 2,                            /* 0, GSMCAL_S_POST_NO_POS, GSMCAL_S_BCCH_NO_DECODE, GSMCAL_E_CAPACITY     */
+    GSMCAL_I_FIRST_OK = 3,                          /* 1-based index of the first ok block, -1 without one                     */
+    GSMCAL_I_OK = 4,                                /* [GSMCAL_MAX_HITS] 1 / 0; NaN: the block was not evaluated               */
+    GSMCAL_I_POS = 4 + GSMCAL_MAX_HITS,             /* [GSMCAL_MAX_HITS] 1-based start sample of the block's first burst       */
+    GSMCAL_I_CORRECTED = 4 + 2 * GSMCAL_MAX_HITS,   /* [GSMCAL_MAX_HITS] hard channel bits (of 456) that differ from the re-encoded word */
+    GSMCAL_I_TS_ERR = 4 + 3 * GSMCAL_MAX_HITS,      /* [GSMCAL_MAX_HITS] hard errors in the 4 x 26 mid-amble bits              */
+    GSMCAL_I_STEAL = 4 + 4 * GSMCAL_MAX_HITS,       /* [GSMCAL_MAX_HITS] stealing flags read as one, 0..8 (a BCCH block: 8)    */
+    GSMCAL_I_MEAN_SLOPE = 4 + 5 * GSMCAL_MAX_HITS,  /* [GSMCAL_MAX_HITS] mean phase slope of the four bursts, rad/symbol       */
+    GSMCAL_I_AMP = 4 + 6 * GSMCAL_MAX_HITS          /* [GSMCAL_MAX_HITS] mean of the four bursts' |h| / 26                     */
+};
+
 /* ---- algorithm thresholds (the constants the reference hard-codes inside its functions) ---------- */
 /* Defaults = the reference's literals.  gsmcal_set_params() takes effect from the next call on (calls in flight finish with the
  * values they were made under; a captured graph is never replayed across a change); the fields marked "geometry" size windows
@@ -182,7 +203,7 @@ const char* gsmcal_last_error(gsmcal_ctx* ctx);
  * SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79) -- and a MEX file that shadows one
  * would otherwise run silent.  After gsmcal_FCCH_coarse_position / _FCCH_fine_correction / _SCH_corr_rate_correction /
  * _carrier_correct_post_SCH this returns the lines that call's .m file would have printed, '\n'-separated, numbers formatted as
- * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  gsmcal_FCCH_demod, gsmcal_BCCH_demod and gsmcal_SCH_decode leave their lines too.  buf may be NULL; the return value is the
+ * MATLAB's num2str formats them (gsmcal_num2str: the same formatter, for row vectors).  gsmcal_FCCH_demod, gsmcal_BCCH_demod, gsmcal_SCH_decode and gsmcal_BCCH_decode leave their lines too.  buf may be NULL; the return value is the
  * text's length without the terminator.  The gateway mexPrintf()s it; the Python mirror prints it when GSMCAL_VERBOSE=1. */
 long gsmcal_last_call_report(gsmcal_ctx* ctx, char* buf, size_t cap);
 long gsmcal_num2str(const double* x, int n, char* buf, size_t cap);
@@ -404,6 +425,31 @@ int gsmcal_SCH_decode(gsmcal_ctx* ctx, const double* s, long len, const double* 
                       const double* sch_training_sequence, int len_ts, int oversampling_ratio, int* bsic, long* fn_anchor,
                       long* pos_anchor, double* table_row, double* soft, unsigned char* u);
 
+/* BCCH_decode(s, pos_info, tsc, ov): the system information in the BCCH blocks that pos_info marks -- which cell this is.  The
+ * project's own function, NOT a port: BCCH_demod.m stops at the training sequence index.  A block is four
+ * type-2 rows of pos_info directly behind a type-1 row (rows i+1..i+4; a shorter run is no block).  Per burst with 1-based start
+ * p, tsc in 0..7 (anything else: GSMCAL_E_ARG), ov in {2, 4, 8} (anything else: GSMCAL_E_UNSUPPORTED), delta = (5*ov - 1) div 2:
+ *   y_k = s(p + k*ov + delta) * (-j)^k for k = 3..144; if any of the block's four bursts would read outside the stream, or has p
+ *   NaN or < 1, the block is not evaluated (NaN columns, zero octets, no error);  pass 0: h = the correlation of y_61..86 with the
+ *   26 training bits of code tsc (1 - 2 bit), amp = |h| / 26, soft_k = Re(y_k conj(h)/|h|);  two decision-directed refinements:
+ *   b_k = sign(soft_k) (+1 at zero; the training bits inside the mid-amble), g1, g2 = the sums of y_k b_k over k = 3..73 and
+ *   74..144, g = g1 + g2, slope = angle(g2 conj(g1)) / 71, soft_k = Re(y_k conj(g)/|g| exp(-j slope (k - 73.5))), positive = bit 0;
+ *   the 4 x 114 data values are de-interleaved to c(0..455) (GSM 05.03 4.1.4: c(k) in burst k mod 4 at position 2 ((49 k) mod 57) +
+ *   ((k mod 8) div 4)); the stealing flags are counted, not used;  the 16-state soft-decision Viterbi decoder of gsmcal_SCH_decode
+ *   (the same generators) over 228 steps from state 0 to state 0;  ok = the remainder of u(0..223) by the Fire code's g(D) =
+ *   D^40 + D^26 + D^23 + D^17 + D^3 + 1 is all ones and u(224..227) = 0 -- detection only, no burst-error correction.
+ * Octet n of the block has d(8n + k) as its bit k (LSB first); unpinned against a real capture.
+ * Per stream: status 0 iff at least one block is ok (a 40-bit code is evidence on its own), otherwise GSMCAL_S_BCCH_NO_DECODE.
+ * pos_info all -1: GSMCAL_S_POST_NO_POS.  More than GSMCAL_MAX_HITS blocks: GSMCAL_E_CAPACITY.
+ * octets (required): [GSMCAL_MAX_HITS][23] bytes, the decoded blocks, zeros unless ok.  table_row (may be NULL): GSMCAL_SI_COLS
+ * doubles (GSMCAL_I_*), the row gsmcal_bcch_decode_batch writes for this stream.  soft (may be NULL): [GSMCAL_MAX_HITS][456]
+ * doubles, the de-interleaved soft values, NaN for blocks not evaluated.  first (may be NULL): what gsmcal_si_fields (gsmcal_si.h)
+ * reads in the first ok block (valid = 0 without one).  gsmcal_last_call_report then returns "BCCH blocks N decoded N" and
+ * "System information type T cell identity c LAI mcc-mnc-lac" or "Fail to decode the BCCH blocks." (nothing at
+ * GSMCAL_S_POST_NO_POS).  Returns the status. */
+int gsmcal_BCCH_decode(gsmcal_ctx* ctx, const double* s, long len, const double* pos_info, int rows, int ld, int tsc,
+                       int oversampling_ratio, unsigned char* octets, double* table_row, double* soft, gsmcal_si_info* first);
+
 /* ppm_out = total_ppm_calculation(ppm_in)                           total_ppm_calculation.m:5-21
  * (pure host arithmetic; no context needed) */
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out);
@@ -566,6 +612,21 @@ int gsmcal_sch_decode_batch(gsmcal_ctx* ctx, const double* r, long stride, const
 int gsmcal_sch_decode_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
                                 int d, int oversampling_ratio, const double* sch_training_sequence, int len_ts, double* d_out,
                                 double* d_soft, unsigned char* d_u);
+
+/* BCCH_decode for D streams, on the same inputs as gsmcal_sch_decode_batch[_dev] with one training sequence code per stream (host,
+ * tsc[D], each 0..7: anything else GSMCAL_E_ARG) in place of the SCH template.  out: [D][GSMCAL_SI_COLS], row = {num_blocks, num_ok,
+ * status, first_ok, ok[], pos[], corrected[], ts_err[], steal[], mean_slope[], amp[]} (GSMCAL_I_*); unused entries and blocks that
+ * were not evaluated NaN.  Per-row outcomes go in the status column: 0, GSMCAL_S_POST_NO_POS (r_len = -1 or an all -1 pos_info;
+ * num_blocks 0), GSMCAL_S_BCCH_NO_DECODE, GSMCAL_E_CAPACITY (more than GSMCAL_MAX_HITS blocks; nothing evaluated).  octets
+ * (required): [D][GSMCAL_MAX_HITS][23] bytes, zeros unless the block is ok.  soft (NULL to skip): [D][GSMCAL_MAX_HITS][456] doubles,
+ * NaN where the block was not evaluated.  ov other than 2, 4, 8: GSMCAL_E_UNSUPPORTED.  A row is bit-identical alone, at any
+ * position of a batch, and equal to what gsmcal_BCCH_decode returns.  _dev: device pointers (tsc stays a host array), only enqueues
+ * on the context's stream; the lanes and every answer about the calibrate / scan call before stay untouched. */
+int gsmcal_bcch_decode_batch(gsmcal_ctx* ctx, const double* r, long stride, const long* r_len, const double* pos_info, int d,
+                             int oversampling_ratio, const int* tsc, double* out, unsigned char* octets, double* soft);
+int gsmcal_bcch_decode_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
+                                 int d, int oversampling_ratio, const int* tsc, double* d_out, unsigned char* d_octets,
+                                 double* d_soft);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,

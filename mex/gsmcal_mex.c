@@ -7,7 +7,7 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
+ *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode BCCH_decode CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
  *            gsmcal_band_power gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
@@ -325,6 +325,42 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nlhs > 4) {
         plhs[4] = mxCreateDoubleMatrix(1, (mwSize)nb, mxREAL);
         for (k = 0; k < (mwSize)nb; ++k) REAL_PTR(plhs[4])[k] = row[GSMCAL_C_OK + k];
+    }
+
+#elif defined(GSMCAL_FN_BCCH_decode)
+    /* [cell_id, lai, si_type, octets, ok] = BCCH_decode(s, pos_info, tsc, ov): the project's own function (include/gsmcal.h), not
+     * BCCH_demod.m.  tsc: the training sequence code 0..7 (BCCH_demod's idx - 1).  From the first block that passes the Fire code:
+     * the cell identity (-1 unless it is a SYSTEM INFORMATION TYPE 3), lai = [mcc mnc lac] (-1 where the message has none) and the
+     * type 1..4 (0: not recognised, -1: no block decoded or pos_info == -1); then the blocks as a num_blocks x 23 matrix of octets
+     * (zero rows where a block failed) and the ok flag per block (NaN where it was not evaluated).  Prints the report lines. */
+    mwSize n = 0, k, j;
+    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    int rows = (int)mxGetM(prhs[1]), nb, rc;
+    double row[GSMCAL_SI_COLS];
+    unsigned char oct[GSMCAL_MAX_HITS * GSMCAL_BLOCK_OCTETS];
+    gsmcal_si_info si;
+    if (nrhs < 4) mexErrMsgIdAndTxt("gsmcal:args", "usage: [cell_id, lai, si_type, octets, ok] = BCCH_decode(s, pos_info, tsc, ov)");
+    rc = gsmcal_BCCH_decode(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, (int)mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]), oct,
+                            row, NULL, &si);
+    chk(rc, "BCCH_decode");
+    say();
+    nb = (int)row[GSMCAL_I_NUM_BLOCKS] < GSMCAL_MAX_HITS ? (int)row[GSMCAL_I_NUM_BLOCKS] : GSMCAL_MAX_HITS;
+    plhs[0] = scalar((double)si.cell_id);
+    if (nlhs > 1) {
+        plhs[1] = mxCreateDoubleMatrix(1, 3, mxREAL);
+        REAL_PTR(plhs[1])[0] = (double)si.mcc;
+        REAL_PTR(plhs[1])[1] = (double)si.mnc;
+        REAL_PTR(plhs[1])[2] = (double)si.lac;
+    }
+    if (nlhs > 2) plhs[2] = scalar(rc == 0 ? (double)si.si_type : -1.0);
+    if (nlhs > 3) {
+        plhs[3] = mxCreateDoubleMatrix((mwSize)nb, GSMCAL_BLOCK_OCTETS, mxREAL);
+        for (k = 0; k < (mwSize)nb; ++k)
+            for (j = 0; j < GSMCAL_BLOCK_OCTETS; ++j) REAL_PTR(plhs[3])[j * (mwSize)nb + k] = (double)oct[k * GSMCAL_BLOCK_OCTETS + j];
+    }
+    if (nlhs > 4) {
+        plhs[4] = mxCreateDoubleMatrix(1, (mwSize)nb, mxREAL);
+        for (k = 0; k < (mwSize)nb; ++k) REAL_PTR(plhs[4])[k] = row[GSMCAL_I_OK + k];
     }
 
 #elif defined(GSMCAL_FN_CW_check)

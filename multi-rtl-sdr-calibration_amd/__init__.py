@@ -9,7 +9,7 @@ valid Python identifier).  Sub-modules:
     build  -- hipcc build of csrc/ -> lib/libgsmcal.so
 """
 from . import build, ingest, synth  # noqa: F401
-from ._lib import GsmcalError, MAX_HITS, MAX_POS_ROWS, MAX_SUBBANDS, TABLE_COLS, DEMOD_COLS, MAX_BCCH, BCCH_COLS, SCH_COLS, HYPERFRAME, CW_MAX_EVENTS, CW_COLS, CW_TILE, CW_OK, CW_SHORT, CW_ZERO, SIGNATURES, lib_path, load  # noqa: F401
+from ._lib import GsmcalError, MAX_HITS, MAX_POS_ROWS, MAX_SUBBANDS, TABLE_COLS, DEMOD_COLS, MAX_BCCH, BCCH_COLS, SCH_COLS, SI_COLS, BLOCK_OCTETS, BLOCK_CODED, HYPERFRAME, CW_MAX_EVENTS, CW_COLS, CW_TILE, CW_OK, CW_SHORT, CW_ZERO, SIGNATURES, lib_path, load  # noqa: F401
 from .api import (  # noqa: F401
     Context, default_context, raw2iq, filter, chn_filter_8x_4x, chn_filter_4x, move_fft_snr_runtime_avg,
     specific_fft_snr_fix_avg, FCCH_coarse_position, FCCH_fine_correction, SCH_corr_rate_correction,
@@ -20,4 +20,5 @@ from .api import (  # noqa: F401
     subband_power_batch, subband_power_batch_dev, multichannel_spectrum_scan, CW_check, cw_check_batch, cw_check_batch_dev,
     cw_rows, CW_FIELDS, BCCH_demod, bcch_demod_batch, bcch_demod_batch_dev, bcch_rows, BCCH_FIELDS,
     SCH_decode, sch_decode_batch, sch_decode_batch_dev, sch_rows, SCH_FIELDS, sch_alignment,
+    BCCH_decode, bcch_decode_batch, bcch_decode_batch_dev, si_rows, SI_FIELDS, SI_BLOCK_FIELDS, si_fields,
 )

@@ -27,6 +27,9 @@ BCCH_COLS = 6 + 4 * MAX_BCCH       # one row of bcch_demod_batch: six scalars (a
 S_POST_NO_POS, S_POST_FEW_BCCH, S_BCCH_TSC_MIXED = 10, 11, 13
 SCH_COLS = 8 + 7 * MAX_HITS        # one row of sch_decode_batch: eight scalars (api.SCH_FIELDS), then ok[], bsic[], fn[], ts_err[], corrected[], slope[], amp[]
 S_SCH_NO_DECODE = 14
+SI_COLS = 4 + 7 * MAX_HITS         # one row of bcch_decode_batch: four scalars (api.SI_FIELDS), then ok[], pos[], corrected[], ts_err[], steal[], mean_slope[], amp[]
+S_BCCH_NO_DECODE = 15
+BLOCK_OCTETS, BLOCK_CODED = 23, 456  # octets and coded bits of one BCCH block
 HYPERFRAME = 2715648               # TDMA frames per GSM hyperframe: frame numbers wrap here
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
@@ -87,6 +90,12 @@ SIGNATURES = {
                                           C.c_int, c_double_p, c_double_p, c_u8_p]),
     "gsmcal_sch_decode_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_double_p,
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsmcal_BCCH_decode": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_double_p, C.c_int, C.c_int, C.c_int, C.c_int, c_u8_p,
+                                     c_double_p, c_double_p, C.c_void_p]),
+    "gsmcal_bcch_decode_batch": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_long_p, c_double_p, C.c_int, C.c_int, c_int_p,
+                                           c_double_p, c_u8_p, c_double_p]),
+    "gsmcal_bcch_decode_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsmcal_total_ppm_calculation": (C.c_int, [c_double_p, C.c_int, c_double_p]),
     "gsmcal_frontend_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                         c_double_p]),

@@ -17,7 +17,8 @@ sentinel returns (scalar -1.0 / inf, pos_info = [[-1, -1]]) so that tests read l
     FCCH_demod(s,pos_info,ov,carrier_freq)                           FCCH_demod.m:5 (what it prints, returned as a dict)
     [idx,r,carrier_ppm] = BCCH_demod(s,pos_info,normal_training_sequence,ov,carrier_freq)     BCCH_demod.m:5 (a dict)
     ppm_out = total_ppm_calculation(ppm_in)
-and, without a counterpart in the reference (its SCH_demod.m returns nothing): SCH_decode(s,pos_info,sch_training_sequence,ov).
+and, without a counterpart in the reference (its SCH_demod.m returns nothing, its BCCH_demod.m stops at the training sequence index):
+SCH_decode(s,pos_info,sch_training_sequence,ov) and BCCH_decode(s,pos_info,tsc,ov).
 
 Everything computes on the GPU through the C ABI; there is no CPU fallback.
 """
@@ -30,7 +31,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BCCH_COLS, SCH_COLS, CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -505,6 +506,63 @@ def SCH_decode(s, pos_info, sch_training_sequence, oversampling_ratio, ctx=None,
     return out
 
 
+class _SiInfo(C.Structure):
+    _fields_ = [(name, C.c_int) for name in ("valid", "msg_type", "si_type", "cell_id", "mcc", "mnc", "mnc_digits", "lac")]
+
+
+def _si_dict(info):
+    return {name: int(getattr(info, name)) for name, _ in _SiInfo._fields_}
+
+
+def si_fields(octets):
+    """What a decoded BCCH block says about the cell: gsmcal_si_fields (include/gsmcal_si.h, plain C, the definition libgsmcal.so
+    exports) on 23 octets -> dict(valid, msg_type, si_type, cell_id, mcc, mnc, mnc_digits, lac); fields a message does not carry
+    are -1, valid is 0 for anything the parser does not recognise.  Needs no context and no GPU."""
+    o = np.ascontiguousarray(np.asarray(octets, dtype=np.uint8).ravel())
+    if o.shape != (BLOCK_OCTETS,):
+        raise ValueError("si_fields: 23 octets")
+    fn = _lib.load().gsmcal_si_fields
+    fn.restype, fn.argtypes = C.c_int, [_lib.c_u8_p, C.POINTER(_SiInfo)]
+    info = _SiInfo()
+    fn(o.ctypes.data_as(_lib.c_u8_p), C.byref(info))
+    return _si_dict(info)
+
+
+def BCCH_decode(s, pos_info, tsc, oversampling_ratio, ctx=None, want_soft=False):
+    """BCCH_decode(s, pos_info, tsc, ov) -- the project's own function (include/gsmcal.h; BCCH_demod.m stops at
+    the training sequence index): the system information the BCCH blocks of pos_info carry.  A block is four type-2 rows directly
+    behind a type-1 row; tsc 0..7 is the cell's training sequence code (what BCCH_demod finds, minus one); ov 2, 4 or 8.  Returns
+    None when pos_info is all -1, otherwise a dict: `status` (0, or 15 = no block passes the Fire code), `num_blocks`, `num_ok`,
+    `first_ok` (1-based, -1 without one), per block `ok`, `pos`, `corrected`, `ts_err`, `steal`, `mean_slope`, `amp` (NaN for a
+    block that was not evaluated), `octets` (num_blocks, 23) uint8 -- zeros unless ok --, `si`: si_fields of the first ok block
+    (valid 0 without one), and with want_soft `soft` (num_blocks, 456); `row` is the (SI_COLS,) table row bcch_decode_batch holds
+    for this stream."""
+    ctx = ctx or default_context()
+    buf, n = _r_in(s)
+    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
+    rows = pi.shape[0]
+    pic = np.ascontiguousarray(pi.T)
+    row = np.full(SI_COLS, np.nan)
+    octets = np.zeros((MAX_HITS, BLOCK_OCTETS), dtype=np.uint8)
+    soft = np.empty((MAX_HITS, BLOCK_CODED)) if want_soft else None
+    info = _SiInfo()
+    rc = ctx.check(ctx.lib.gsmcal_BCCH_decode(ctx.h, _dp(buf) if buf is not None else None, n, _dp(pic), rows, rows, int(tsc),
+                                              int(oversampling_ratio), octets.ctypes.data_as(_lib.c_u8_p), _dp(row),
+                                              _dp(soft) if want_soft else None, C.c_void_p(C.addressof(info))), "BCCH_decode")
+    _say(ctx)
+    if rc == _lib.S_POST_NO_POS:
+        return None
+    t = si_rows(row)
+    k = min(int(t["num_blocks"][0]), MAX_HITS) if rc >= 0 else 0
+    out = {"status": rc, "num_blocks": int(t["num_blocks"][0]), "num_ok": int(t["num_ok"][0]), "first_ok": int(t["first_ok"][0]),
+           "octets": octets[:k].copy(), "si": _si_dict(info), "row": row}
+    for name in SI_BLOCK_FIELDS:
+        out[name] = t[name][0, :k].copy()
+    if want_soft:
+        out["soft"] = soft[:k].copy()
+    return out
+
+
 def total_ppm_calculation(ppm_in):
     lib = _lib.load()
     p = np.ascontiguousarray(np.atleast_1d(np.asarray(ppm_in, dtype=np.float64)))
@@ -804,6 +862,67 @@ def sch_decode_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio
     ctx.check(ctx.lib.gsmcal_sch_decode_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
                                                   int(d), int(oversampling_ratio), _dp(ts), len_ts, C.c_void_p(d_out), opt(d_soft),
                                                   opt(d_u)), "sch_decode_batch_dev")
+
+
+SI_FIELDS = ("num_blocks", "num_ok", "status", "first_ok")          # columns 0..3
+SI_BLOCK_FIELDS = ("ok", "pos", "corrected", "ts_err", "steal", "mean_slope", "amp")
+
+
+def si_rows(table):
+    """(D, SI_COLS) table of bcch_decode_batch[_dev] -> dict of its columns (ok, pos, corrected, ts_err, steal, mean_slope, amp:
+    (D, MAX_HITS), NaN for unused entries and for blocks that were not evaluated)."""
+    t = np.asarray(table).reshape(-1, SI_COLS)
+    out = {k: t[:, i] for i, k in enumerate(SI_FIELDS)}
+    for j, name in enumerate(SI_BLOCK_FIELDS):
+        out[name] = t[:, 4 + j * MAX_HITS: 4 + (j + 1) * MAX_HITS]
+    return out
+
+
+def _tsc_in(tsc, d):
+    t = np.asarray(tsc, dtype=np.int32).ravel()
+    t = np.ascontiguousarray(np.broadcast_to(t, (d,)) if t.size == 1 else t)
+    if len(t) != d:
+        raise ValueError("tsc must be one code or one per stream")
+    return t
+
+
+def bcch_decode_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, tsc, ctx=None, want_soft=False):
+    """BCCH_decode for D streams, on what calibrate_batch(..., want_r=True) returns (as sch_decode_batch) plus the training
+    sequence code: one int for all streams or one per stream.  Returns a dict: "table" (D, SI_COLS) (si_rows names its columns;
+    per-row outcomes are in its status column), "octets" (D, MAX_HITS, 23) uint8, zeros unless the block is ok, and with want_soft
+    "soft" (D, MAX_HITS, 456)."""
+    ctx = ctx or default_context()
+    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
+    d, stride = r.shape
+    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
+    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
+    if len(rl) != d:
+        raise ValueError("r_len must have one entry per stream")
+    codes = _tsc_in(tsc, d)
+    out = np.empty((d, SI_COLS))
+    octets = np.empty((d, MAX_HITS, BLOCK_OCTETS), dtype=np.uint8)
+    soft = np.empty((d, MAX_HITS, BLOCK_CODED)) if want_soft else None
+    ctx.check(ctx.lib.gsmcal_bcch_decode_batch(ctx.h, _dp(r), stride, rl.ctypes.data_as(_lib.c_long_p), _dp(pi), d,
+                                               int(oversampling_ratio), codes.ctypes.data_as(_lib.c_int_p), _dp(out),
+                                               octets.ctypes.data_as(_lib.c_u8_p), _dp(soft) if want_soft else None),
+              "bcch_decode_batch")
+    res = {"table": out, "octets": octets}
+    if want_soft:
+        res["soft"] = soft
+    return res
+
+
+def bcch_decode_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio, tsc, d_out, d_octets, d_soft=None, ctx=None):
+    """Device-pointer form of bcch_decode_batch: only enqueues on the context's stream, e.g. directly behind calibrate_batch_dev on
+    its d_r_correct / d_r_len / d_pos_info (ctx.sync() before reading).  tsc: one int or one per stream (host).  d_out:
+    [d][SI_COLS] doubles; d_octets: [d][MAX_HITS][23] bytes; optional d_soft: [d][MAX_HITS][456] doubles.  Device or pinned host
+    memory."""
+    ctx = ctx or default_context()
+    codes = _tsc_in(tsc, int(d))
+    ctx.check(ctx.lib.gsmcal_bcch_decode_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
+                                                   int(d), int(oversampling_ratio), codes.ctypes.data_as(_lib.c_int_p),
+                                                   C.c_void_p(d_out), C.c_void_p(d_octets), C.c_void_p(d_soft) if d_soft else None),
+              "bcch_decode_batch_dev")
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

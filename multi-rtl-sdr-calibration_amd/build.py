@@ -14,6 +14,7 @@ LIB = os.environ.get("GSMCAL_LIB") or os.path.join(LIB_DIR, "libgsmcal.so")   # 
 def _deps():
     d = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))]
     d.append(os.path.join(HERE, "..", "include", "gsmcal.h"))
+    d.append(os.path.join(HERE, "..", "include", "gsmcal_si.h"))
     return d
 
 

@@ -974,6 +974,91 @@ int gsmcal_SCH_decode(gsmcal_ctx* c, const double* s, long len, const double* po
     return status;
 }
 
+// ---- BCCH_decode: the system information in the BCCH blocks ----------------------------------------------
+// k_bcch_decode (one workgroup per block slot and stream, one wave per burst) + k_bcch_decode_finish (one wave per stream) on the
+// context's stream, in bd_part; nothing of the lanes or of the chain's state is touched.
+static int bcch_decode_args(gsmcal_ctx* c, int ov, const int* tsc, int d) {
+    if (ov != 2 && ov != 4 && ov != 8) { c->err = "BCCH_decode: oversampling ratios 2, 4 and 8 only"; return GSMCAL_E_UNSUPPORTED; }
+    for (int i = 0; i < d; ++i)
+        if (tsc[i] < 0 || tsc[i] > 7) { c->err = "BCCH_decode: the training sequence code must be 0..7"; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+int gsmcal_bcch_decode_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
+                                 int ov, const int* tsc, double* d_out, unsigned char* d_octets, double* d_soft) {
+    if (!c || !d_r || !d_r_len || !d_pos_info || !tsc || !d_out || !d_octets || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    RET_IF(bcch_decode_args(c, ov, tsc, d));
+    ENTER(c);
+    c->cur = &c->lanes[0];                                      // the context's stream; the lane's buffers are not touched
+    RET_IF(ensure(c, c->bd_part, (size_t)d * MAXH * BD_PART * sizeof(double)));
+    RET_IF(upload_if_changed(c, c->bd_tsc, c->h_bd_tsc, tsc, (size_t)d, "BCCH_decode training sequence codes"));
+    double* part = (double*)c->bd_part.p;
+    const int* d_tsc = (const int*)c->bd_tsc.p;
+    for_capture_chunks(d, [&](long lo, int S) {
+        LAUNCH(c, k_bcch_decode, dim3(MAXH, S), dim3(256), 0, (const cplx*)d_r + (size_t)lo * stride, stride, d_r_len + lo,
+               d_pos_info + (size_t)lo * 2 * MAXROWS, ov, d_tsc + lo, part + (size_t)lo * MAXH * BD_PART,
+               d_octets + (size_t)lo * MAXH * GSMCAL_BLOCK_OCTETS, d_soft ? d_soft + (size_t)lo * MAXH * GSMCAL_BLOCK_CODED : nullptr);
+    });
+    LAUNCH(c, k_bcch_decode_finish, dim3(d), dim3(64), 0, d_r_len, stride, d_pos_info, (const double*)part, d_out);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_bcch_decode_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
+                             const int* tsc, double* out, unsigned char* octets, double* soft) {
+    if (!c || !r || !r_len || !pos_info || !tsc || !out || !octets || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    RET_IF(bcch_decode_args(c, ov, tsc, d));
+    ENTER(c);
+    const Stage io[] = {STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),
+                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
+                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
+                        STAGE(bd_out, (size_t)d * GSMCAL_SI_COLS * sizeof(double), nullptr, out, 0),
+                        STAGE(bd_oct, (size_t)d * MAXH * GSMCAL_BLOCK_OCTETS, nullptr, octets, 0),
+                        STAGE(bd_soft, soft ? (size_t)d * MAXH * GSMCAL_BLOCK_CODED * sizeof(double) : 0, nullptr, soft, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_bcch_decode_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d,
+                                        ov, tsc, (double*)c->bd_out.p, (unsigned char*)c->bd_oct.p,
+                                        soft ? (double*)c->bd_soft.p : nullptr));
+    return stage_down(c, io);
+}
+
+int gsmcal_BCCH_decode(gsmcal_ctx* c, const double* s, long len, const double* pos_info, int rows, int ld, int tsc, int ov,
+                       unsigned char* octets, double* table_row, double* soft, gsmcal_si_info* first) {
+    if (!c || !pos_info || !octets || rows < 1 || ld < rows) return GSMCAL_E_ARG;
+    RET_IF(bcch_decode_args(c, ov, &tsc, 1));
+    ENTER(c);
+    gsmcal_si_info si;
+    gsmcal_si_fields(nullptr, &si);                             // valid = 0, every field -1
+    if (first) *first = si;
+    c->report.clear();
+    std::vector<double> row(GSMCAL_SI_COLS, NAN);
+    bool all_m1 = true;
+    for (int i = 0; i < rows; ++i) all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
+    if (all_m1) {                                               // nothing to read: the batch form's row for such a stream
+        row[GSMCAL_I_NUM_BLOCKS] = row[GSMCAL_I_NUM_OK] = 0.0;
+        row[GSMCAL_I_FIRST_OK] = -1.0;
+        row[GSMCAL_I_STATUS] = GSMCAL_S_POST_NO_POS;
+        if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
+        memset(octets, 0, (size_t)MAXH * GSMCAL_BLOCK_OCTETS);
+        if (soft) std::fill(soft, soft + (size_t)MAXH * GSMCAL_BLOCK_CODED, NAN);
+        return GSMCAL_S_POST_NO_POS;
+    }
+    if (!s || len < 1) return GSMCAL_E_ARG;
+    if (rows > MAXROWS) return GSMCAL_E_CAPACITY;
+    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
+    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
+    RET_IF(gsmcal_bcch_decode_batch(c, s, len, &len, pi.data(), 1, ov, &tsc, row.data(), octets, soft));
+    if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
+    const int status = (int)row[GSMCAL_I_STATUS];
+    if (status < 0) return status;
+    if (status == 0) {
+        gsmcal_si_fields(octets + (size_t)((int)row[GSMCAL_I_FIRST_OK] - 1) * GSMCAL_BLOCK_OCTETS, &si);
+        if (first) *first = si;
+    }
+    c->report = report_bcch_decode(row.data(), si);
+    return status;
+}
+
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out) {
     if (!ppm_in || !ppm_out || n < 1) return GSMCAL_E_ARG;

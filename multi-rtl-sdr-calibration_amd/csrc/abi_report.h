@@ -1,6 +1,6 @@
 // abi_report.h -- the reference's console diagnostics (FCCH_coarse_position.m:6,28,92-94, FCCH_fine_correction.m:6,13,66,
 // 96-99,116,156-161,190-193, SCH_corr_rate_correction.m:6,12,60,80,107-110,118, carrier_correct_post_SCH.m:6,11,17,73-79, FCCH_demod.m:6,9,43-49,65-66,
-// BCCH_demod.m:15,69,72,101,104; gsmcal_SCH_decode's own three lines) as TEXT:
+// BCCH_demod.m:15,69,72,101,104; gsmcal_SCH_decode's and gsmcal_BCCH_decode's own three lines each) as TEXT:
 // the per-function entry points of abi_calls.h have the stream's state on the host anyway and leave the lines the .m file would
 // have disp()ed in the context; gsmcal_last_call_report() hands them to the MEX gateway (mexPrintf) or the Python mirror.
 // Included by gsmcal.hip ahead of abi_calls.h (host code only).
@@ -163,6 +163,17 @@ std::string report_sch_decode(const double* row) {
     if ((int)row[GSMCAL_C_STATUS] != 0) return r + "Fail to decode the SCH bursts.\n";
     snprintf(buf, sizeof buf, "BSIC %d frame number %ld at sample %ld\n", (int)row[GSMCAL_C_BSIC], (long)row[GSMCAL_C_FN_ANCHOR],
              (long)row[GSMCAL_C_POS_ANCHOR]);
+    return r + buf;
+}
+
+// gsmcal_BCCH_decode (the project's own lines).  row: one row of the BCCH_decode table (GSMCAL_I_*), status 0 or
+// GSMCAL_S_BCCH_NO_DECODE; si: what gsmcal_si_fields reads in the first ok block.
+std::string report_bcch_decode(const double* row, const gsmcal_si_info& si) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "BCCH blocks %d decoded %d\n", (int)row[GSMCAL_I_NUM_BLOCKS], (int)row[GSMCAL_I_NUM_OK]);
+    std::string r = buf;
+    if ((int)row[GSMCAL_I_STATUS] != 0) return r + "Fail to decode the BCCH blocks.\n";
+    snprintf(buf, sizeof buf, "System information type %d cell identity %d LAI %d-%d-%d\n", si.si_type, si.cell_id, si.mcc, si.mnc, si.lac);
     return r + buf;
 }
 

@@ -23,6 +23,7 @@
 #include <rccl/rccl.h>
 #include <unistd.h>
 
+#define GSMCAL_SI_LINKAGE   // gsmcal_si.h (through gsmcal.h): the library holds the exported definition of gsmcal_si_fields
 #include "../../include/gsmcal.h"
 #include "builtin_taps.h"
 #include "kernels_detect.h"

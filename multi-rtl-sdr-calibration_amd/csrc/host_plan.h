@@ -61,6 +61,9 @@ struct CtxBufs {
     // SCH_decode (gsmcal_SCH_decode, gsmcal_sch_decode_batch*): the per-burst records, and the host wrapper's staging of the table,
     // the soft values and the decoded words (its inputs go through fd_in / fd_len / fd_pos)
     DevBuf sd_part, sd_out, sd_soft, sd_u;
+    // BCCH_decode (gsmcal_BCCH_decode, gsmcal_bcch_decode_batch*): the per-block records, the training sequence codes, and the host
+    // wrapper's staging of the table, the octets and the soft values (its inputs go through fd_in / fd_len / fd_pos)
+    DevBuf bd_part, bd_tsc, bd_out, bd_oct, bd_soft;
     // sub-band power (gsmcal_subband_power_batch*).  sb_taps: one modulated tap row per distinct phase_rotate value, built on the
     // host; sb_idx: the [capture][slot] table into them
     DevBuf sb_taps, sb_idx, sb_state, sb_part;
@@ -69,7 +72,7 @@ struct CtxBufs {
     DevBuf cw_state, cw_part, cw_rec, cw_mean, cw_in, cw_r;
     ALL_BUFS(CtxBufs, &coef, &ts, &cf, &table, &snrhit, &arr_in, &arr_out, &posinfo, &rlen, &misc, &tw, &csum_head, &tw_sch, &stage_raw,
              &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &bc_ts, &bc_corr, &bc_flag, &bc_out,
-             &bc_corr_out, &bc_r, &bc_rlen, &sd_part, &sd_out, &sd_soft, &sd_u, &sb_taps, &sb_idx,
+             &bc_corr_out, &bc_r, &bc_rlen, &sd_part, &sd_out, &sd_soft, &sd_u, &bd_part, &bd_tsc, &bd_out, &bd_oct, &bd_soft, &sb_taps, &sb_idx,
              &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r)
 };
 
@@ -182,7 +185,7 @@ struct gsmcal_ctx : CtxBufs {
     std::vector<double> h_coef, h_ts, h_cf;   // host copies: upload only when changed
     // host copies of the add-on caches (upload_if_changed); h_sb_coef / h_sb_w: what the rows in sb_taps were built from
     std::vector<double> h_bp_coef, h_fd_cf, h_bc_ts, h_sb_coef, h_sb_w, h_sb_rows;
-    std::vector<int> h_sb_idx;
+    std::vector<int> h_sb_idx, h_bd_tsc;
     int fd_tw_n = 0;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream

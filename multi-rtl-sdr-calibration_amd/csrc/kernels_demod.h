@@ -778,3 +778,289 @@ __global__ void __launch_bounds__(64) k_sch_finish(const long* __restrict__ r_le
         o[GSMCAL_C_MEAN_SLOPE] = num_ok > 0 ? acc / (double)num_ok : nan;
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// BCCH_decode -- the system information in the BCCH blocks: which cell this is.  The project's own function:
+// BCCH_demod.m stops at the training sequence index; the definition is DESIGN 17's and tests/bcch_decode_ref.py restates it.
+//
+// k_bcch_decode: grid (MAXH, D), block 256 -- one workgroup per block slot, wave w takes burst w of the block.  Every wave ranks
+// the block rows of its stream's pos_info from ballots (a type-1 row that four type-2 rows follow directly) and takes the
+// blockIdx.x-th; its bursts start at rows +1..+4 (1-based starts p).  delta = (5 ov - 1) div 2.  A block that is absent, or of which
+// one burst would read outside the stream or has p NaN or < 1, writes its empty record and returns before the barrier (the
+// decision is the same in all four waves).
+//   1  y_k = s(p + k ov + delta) (-j)^k, k = 3..144: 142 strided reads, rotated by a swap and a negation.  Lane l keeps k = 3 + l,
+//      67 + l and (l < 14) 131 + l in registers: nothing of the detector goes through LDS, so no wave waits for another one's
+//      stores before the one barrier.
+//   2  pass 0: every lane adds its own mid-amble symbols y_{61+i} a_i (a_i = 1 - 2 TSC[tsc][i], bits of BD_TSC_MASK), six
+//      xor-shuffle steps leave h in every lane: one fixed order.  amp = |h| / 26, soft_k = Re(y_k conj(h)/|h|).
+//   3  two refinements: b_k = sign(soft_k) (+1 at zero), a_{k-61} inside the mid-amble; g1 (k <= 73), g2 (k >= 74) by the same
+//      lane-strided partial sums and xor-shuffle tree; slope = angle(g2 conj(g1)) / 71;
+//      soft_k = Re(y_k conj(g)/|g| exp(-j slope (k - 73.5))).
+//   4  each wave stores its 114 data values at their places c(0..455) of the coded word in LDS (bd_coded_index: the inverse of
+//      the interleaver, the one table to pin), counts its mid-amble errors and the two stealing flags from ballots, and leaves
+//      {ts_err, steal, slope, amp} in LDS.  ONE barrier; waves 1..3 are done.
+//   5  wave 0: the 16-state trellis of k_sch_decode over 228 steps (lane mod 16 = state, metrics by __shfl, the same two additions
+//      per candidate and the same strict >).  The survivor no longer fits a register: the low 16 bits of __ballot(take) are the
+//      step's decision word, stored by lane 0 (456 bytes of LDS), and lane 0 traces back from state 0 into four 64-bit registers
+//      that one __shfl hands to the wave.  No atomics, no global traceback memory, no scratch.
+//   6  integer work: corrected from eight ballots against the re-encoded word, the Fire remainder of u(0..223) (a 40-bit shift
+//      register), the tail bits, and lanes 0..22 pack one octet each (bit k of octet n = u(8n + k)).
+// part[s][slot][BD_PART] = {evaluated, ok, corrected, ts_err, steal, mean_slope, amp, pos}; oct_out[s][slot][23]: zeros unless ok;
+// optional soft_out[s][slot][456]: the de-interleaved soft values, NaN for a slot that was not evaluated.  Every workgroup writes
+// all of its slot's outputs.
+// ------------------------------------------------------------------------------------------------
+#define BD_PART 8
+#define BD_FIRE_POLY 0x10004820009ull            /* g(D) = D^40 + D^26 + D^23 + D^17 + D^3 + 1 */
+#define BD_FIRE_ONES 0xffffffffffull
+
+// bit i = TSC[code][i] (GSM 05.02 table 5.2.3a; synth.TSC)
+__device__ const unsigned BD_TSC_MASK[8] = {0x3a443a4u, 0x3b47bb4u, 0x1c25dc2u, 0x1e22de2u, 0x3582758u, 0x1720d72u, 0x3e51be5u, 0x0f748f7u};
+
+// data bit i(B, j), j = 0..113 -> the coded bit c(k) it carries: k mod 4 = B, j = 2 ((49 k) mod 57) + ((k mod 8) div 4)
+// (GSM 05.03 4.1.4; synth.bcch_interleave_map).  49 * 7 = 1 (mod 57), so k mod 57 = 7 (j div 2) mod 57, and k mod 8 = B + 4 (j mod 2).
+__device__ __forceinline__ int bd_coded_index(int B, int j) {
+    const int r57 = (7 * (j >> 1)) % 57;
+    return r57 + 57 * ((B + 4 * (j & 1) - r57) & 7);
+}
+__device__ __forceinline__ unsigned bd_u(unsigned long long u0, unsigned long long u1, unsigned long long u2, unsigned long long u3, int k) {
+    const unsigned long long w = k < 64 ? u0 : k < 128 ? u1 : k < 192 ? u2 : u3;
+    return k < 0 ? 0u : (unsigned)(w >> (k & 63)) & 1u;
+}
+
+__global__ void __launch_bounds__(256) k_bcch_decode(const cplx* __restrict__ r, long stride, const long* __restrict__ r_len,
+                                                     const double* __restrict__ pos_info, int ov, const int* __restrict__ tsc,
+                                                     double* __restrict__ part, unsigned char* __restrict__ oct_out,
+                                                     double* __restrict__ soft_out) {
+    __shared__ double cs[456];
+    __shared__ double bstat[4][4];
+    __shared__ unsigned short dec[228];
+    const int s = blockIdx.y, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const size_t slot = (size_t)s * MAXH + b;
+    double* out = part + slot * BD_PART;
+    const long len = r_len[s] < stride ? r_len[s] : stride;
+    const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
+    // ---- the b-th block row: type 1, and type 2 in the four rows behind it ----
+    constexpr int NCH = (MAXROWS + 63) / 64;
+    int nb = 0, row = -1;
+    for (int c = 0; c < NCH; ++c) {
+        const int i = c * 64 + lane;
+        bool isb = i + 4 < MAXROWS && pi[MAXROWS + i] == 1.0;
+        for (int q = 1; q <= 4; ++q) isb = isb && pi[MAXROWS + i + q] == 2.0;
+        const unsigned long long m = __ballot(isb);
+        const unsigned long long sel = __ballot(isb && nb + __popcll(m & ((1ull << lane) - 1ull)) == b);
+        if (sel) row = c * 64 + __ffsll((long long)sel) - 1;
+        nb += __popcll(m);
+    }
+    const int dl = (5 * ov - 1) / 2;
+    // any of the four p NaN or < 1, or its symbol 144 behind the last sample: the block is not evaluated (uniform in the workgroup)
+    bool evaluated = len >= 1 && row >= 0 && nb <= MAXH;
+    if (evaluated)
+        for (int q = 1; q <= 4; ++q) {
+            const double pq = pi[row + q];
+            evaluated = evaluated && pq >= 1.0 && pq + (double)(144 * ov + dl) <= (double)len;
+        }
+    if (!evaluated) {
+        if (tid == 0) out[0] = 0.0;
+        else if (tid < BD_PART) out[tid] = nan;
+        if (tid < 23) oct_out[slot * 23 + tid] = 0;
+        if (soft_out)
+            for (int k = tid; k < 456; k += 256) soft_out[slot * 456 + k] = nan;
+        return;
+    }
+    // ---- 1  this wave's burst: 142 symbols, derotated, three per lane ----
+    const double spd = pi[row + 1 + w];
+    const cplx* x = r + (size_t)s * stride + ((long)spd - 1 + dl);
+    const unsigned mask = BD_TSC_MASK[tsc[s] & 7];
+    cplx y[3];
+    double a[3], soft[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int k = 3 + lane + 64 * m;
+        y[m] = make_double2(0.0, 0.0);
+        a[m] = 0.0;
+        if (k <= 144) {
+            const cplx v = x[(long)k * ov];
+            const int q = k & 3;                                       // (-j)^k: 1, -j, -1, j
+            y[m] = q == 0 ? v : q == 1 ? make_double2(v.y, -v.x) : q == 2 ? make_double2(-v.x, -v.y) : make_double2(-v.y, v.x);
+            if (k >= 61 && k <= 86) a[m] = (mask >> (k - 61)) & 1u ? -1.0 : 1.0;
+        }
+    }
+    // ---- 2  pass 0: constant phase from the mid-amble ----
+    double hx = 0.0, hy = 0.0;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        hx += y[m].x * a[m];
+        hy += y[m].y * a[m];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        hx += __shfl_xor(hx, off, 64);
+        hy += __shfl_xor(hy, off, 64);
+    }
+    const double mag = hypot(hx, hy), amp = mag / 26.0;
+    {
+        const cplx q = make_double2(hx / mag, -hy / mag);              // conj(h)/|h|
+#pragma unroll
+        for (int m = 0; m < 3; ++m) soft[m] = y[m].x * q.x - y[m].y * q.y;
+    }
+    // ---- 3  two decision-directed refinements over the whole burst ----
+    double slope = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+        double g1x = 0.0, g1y = 0.0, g2x = 0.0, g2y = 0.0;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            const int k = 3 + lane + 64 * m;
+            if (k <= 144) {
+                const double bk = a[m] != 0.0 ? a[m] : soft[m] >= 0.0 ? 1.0 : -1.0;
+                if (k <= 73) { g1x += y[m].x * bk; g1y += y[m].y * bk; }
+                else { g2x += y[m].x * bk; g2y += y[m].y * bk; }
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            g1x += __shfl_xor(g1x, off, 64);
+            g1y += __shfl_xor(g1y, off, 64);
+            g2x += __shfl_xor(g2x, off, 64);
+            g2y += __shfl_xor(g2y, off, 64);
+        }
+        const double gx = g1x + g2x, gy = g1y + g2y, gm = hypot(gx, gy);
+        slope = atan2(g2y * g1x - g2x * g1y, g2x * g1x + g2y * g1y) / 71.0;
+        const cplx wq = make_double2(gx / gm, -gy / gm);               // conj(g)/|g|
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            double sn, cn;
+            sincos(slope * ((double)(3 + lane + 64 * m) - 73.5), &sn, &cn);
+            const cplx q = cmul(wq, make_double2(cn, -sn));
+            soft[m] = y[m].x * q.x - y[m].y * q.y;
+        }
+    }
+    // ---- 4  de-interleave into the coded word; mid-amble errors and stealing flags ----
+    int ts_err = 0, steal = 0;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int k = 3 + lane + 64 * m;
+        const bool data0 = k <= 59, data1 = k >= 88 && k <= 144;
+        if (data0 || data1) cs[bd_coded_index(w, data0 ? k - 3 : k - 31)] = soft[m];
+        ts_err += __popcll(__ballot(a[m] != 0.0 && (soft[m] < 0.0) != (a[m] < 0.0)));
+        steal += __popcll(__ballot((k == 60 || k == 87) && soft[m] < 0.0));
+    }
+    if (lane == 0) {
+        bstat[w][0] = (double)ts_err;
+        bstat[w][1] = (double)steal;
+        bstat[w][2] = slope;
+        bstat[w][3] = amp;
+    }
+    __syncthreads();
+    if (w != 0) return;
+    // ---- 5  the trellis: this lane's state and its two predecessors (older bit 0, older bit 1) ----
+    const int ns = lane & 15, bit = ns >> 3, p0 = (ns & 7) << 1, p1 = p0 | 1;
+    const bool a0 = (bit ^ (p0 >> 1) ^ p0) & 1, a1 = (a0 ^ (p0 >> 3)) & 1;      // c(2k), c(2k+1) coming from p0
+    const bool b0 = (bit ^ (p1 >> 1) ^ p1) & 1, b1 = (b0 ^ (p1 >> 3)) & 1;      // ... from p1
+    double pm = ns == 0 ? 0.0 : -__builtin_huge_val();
+    for (int k = 0; k < 228; ++k) {
+        const double s0 = cs[2 * k], s1 = cs[2 * k + 1];
+        const double bm0 = (a0 ? -s0 : s0) + (a1 ? -s1 : s1);
+        const double bm1 = (b0 ? -s0 : s0) + (b1 ? -s1 : s1);
+        const double c0 = __shfl(pm, p0, 64) + bm0, c1 = __shfl(pm, p1, 64) + bm1;
+        const bool take = c1 > c0;                                     // strict: the first candidate stays
+        pm = take ? c1 : c0;
+        const unsigned long long word = __ballot(take);
+        if (lane == 0) dec[k] = (unsigned short)word;                  // bit ns: state ns came from its predecessor p1
+    }
+    unsigned long long u0 = 0, u1 = 0, u2 = 0, u3 = 0;                // u(k) = bit k & 63 of word k >> 6
+    if (lane == 0) {                                                   // trace back from state 0 (the writer reads its own stores)
+        int st = 0;
+        for (int k = 227; k >= 192; --k) { u3 |= (unsigned long long)(st >> 3) << (k - 192); st = ((st & 7) << 1) | ((dec[k] >> st) & 1); }
+        for (int k = 191; k >= 128; --k) { u2 |= (unsigned long long)(st >> 3) << (k - 128); st = ((st & 7) << 1) | ((dec[k] >> st) & 1); }
+        for (int k = 127; k >= 64; --k) { u1 |= (unsigned long long)(st >> 3) << (k - 64); st = ((st & 7) << 1) | ((dec[k] >> st) & 1); }
+        for (int k = 63; k >= 0; --k) { u0 |= (unsigned long long)(st >> 3) << k; st = ((st & 7) << 1) | ((dec[k] >> st) & 1); }
+    }
+    u0 = sd_shfl_u64(u0, 0);
+    u1 = sd_shfl_u64(u1, 0);
+    u2 = sd_shfl_u64(u2, 0);
+    u3 = sd_shfl_u64(u3, 0);
+    // ---- 6  hard channel bits against the re-encoded word; the Fire code; the octets ----
+    int corrected = 0;
+    for (int j0 = 0; j0 < 456; j0 += 64) {                             // (uniform)
+        const int j = j0 + lane, k = j >> 1;
+        bool differs = false;
+        if (j < 456) {
+            const unsigned c = bd_u(u0, u1, u2, u3, k) ^ bd_u(u0, u1, u2, u3, k - 3) ^ bd_u(u0, u1, u2, u3, k - 4) ^
+                               ((j & 1) ? bd_u(u0, u1, u2, u3, k - 1) : 0u);
+            differs = (cs[j] < 0.0) != (c != 0u);
+        }
+        corrected += __popcll(__ballot(differs));
+    }
+    unsigned long long reg = 0;                                        // u(0..223) divided by g(D): the remainder must be all ones
+    for (int k = 0; k < 224; ++k) {
+        reg = (reg << 1) | bd_u(u0, u1, u2, u3, k);
+        if (reg >> 40) reg ^= BD_FIRE_POLY;
+    }
+    const bool ok = reg == BD_FIRE_ONES && (u3 >> 32) == 0ull;         // ... and u(224..227) = 0
+    if (lane < 23) {
+        const unsigned long long wd = lane < 8 ? u0 : lane < 16 ? u1 : u2;
+        oct_out[slot * 23 + lane] = ok ? (unsigned char)(wd >> ((lane & 7) * 8)) : (unsigned char)0;
+    }
+    if (soft_out)
+        for (int k = lane; k < 456; k += 64) soft_out[slot * 456 + k] = cs[k];
+    if (lane == 0) {
+        out[0] = 1.0;
+        out[1] = ok ? 1.0 : 0.0;
+        out[2] = (double)corrected;
+        out[3] = ((bstat[0][0] + bstat[1][0]) + bstat[2][0]) + bstat[3][0];
+        out[4] = ((bstat[0][1] + bstat[1][1]) + bstat[2][1]) + bstat[3][1];
+        out[5] = (((bstat[0][2] + bstat[1][2]) + bstat[2][2]) + bstat[3][2]) / 4.0;
+        out[6] = (((bstat[0][3] + bstat[1][3]) + bstat[2][3]) + bstat[3][3]) / 4.0;
+        out[7] = pi[row + 1];
+    }
+}
+
+// k_bcch_decode_finish: one wave per stream, grid D, block 64.  out[s] = one row of GSMCAL_SI_COLS doubles (GSMCAL_I_*), written
+// here and nowhere else.  Lane i holds the i-th block.  status 0 iff at least one block is ok -- a 40-bit code is evidence on its
+// own -- otherwise GSMCAL_S_BCCH_NO_DECODE; first_ok: the 1-based index of the first ok block, -1 without one.
+//   r_len < 1 or every element of pos_info -1        status GSMCAL_S_POST_NO_POS, num_blocks 0
+//   more than MAXH blocks                            status GSMCAL_E_CAPACITY, nothing evaluated
+__global__ void __launch_bounds__(64) k_bcch_decode_finish(const long* __restrict__ r_len, long stride,
+                                                           const double* __restrict__ pos_info, const double* __restrict__ part,
+                                                           double* __restrict__ out) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
+    const double* ps = part + (size_t)s * MAXH * BD_PART;
+    double* o = out + (size_t)s * GSMCAL_SI_COLS;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    constexpr int NCH = (MAXROWS + 63) / 64;
+    int nb = 0;
+    unsigned not_m1 = 0;
+    for (int c = 0; c < NCH; ++c) {
+        const int i = c * 64 + lane;
+        const double p = i < MAXROWS ? pi[i] : -1.0, t = i < MAXROWS ? pi[MAXROWS + i] : -1.0;
+        not_m1 += (p != -1.0) || (t != -1.0);
+        bool isb = i + 4 < MAXROWS && t == 1.0;
+        for (int q = 1; q <= 4; ++q) isb = isb && pi[MAXROWS + i + q] == 2.0;
+        nb += __popcll(__ballot(isb));
+    }
+    not_m1 = wave_sum_u32(not_m1);
+    const long len = r_len[s] < stride ? r_len[s] : stride;
+    int status = 0;
+    if (len < 1 || not_m1 == 0) { status = GSMCAL_S_POST_NO_POS; nb = 0; }
+    else if (nb > MAXH) status = GSMCAL_E_CAPACITY;
+    const bool mine = status == 0 && lane < nb;
+    const bool ev = mine && ps[lane * BD_PART] == 1.0;
+    const bool ok = ev && ps[lane * BD_PART + 1] == 1.0;
+    const unsigned long long okm = __ballot(ok);
+    if (status == 0 && okm == 0ull) status = GSMCAL_S_BCCH_NO_DECODE;
+    if (lane < MAXH) {
+        o[GSMCAL_I_OK + lane] = ev ? (ok ? 1.0 : 0.0) : nan;
+        o[GSMCAL_I_POS + lane] = ev ? ps[lane * BD_PART + 7] : nan;
+        o[GSMCAL_I_CORRECTED + lane] = ev ? ps[lane * BD_PART + 2] : nan;
+        o[GSMCAL_I_TS_ERR + lane] = ev ? ps[lane * BD_PART + 3] : nan;
+        o[GSMCAL_I_STEAL + lane] = ev ? ps[lane * BD_PART + 4] : nan;
+        o[GSMCAL_I_MEAN_SLOPE + lane] = ev ? ps[lane * BD_PART + 5] : nan;
+        o[GSMCAL_I_AMP + lane] = ev ? ps[lane * BD_PART + 6] : nan;
+    }
+    if (lane == 0) {
+        o[GSMCAL_I_NUM_BLOCKS] = (double)nb;
+        o[GSMCAL_I_NUM_OK] = (double)__popcll(okm);
+        o[GSMCAL_I_STATUS] = (double)status;
+        o[GSMCAL_I_FIRST_OK] = okm ? (double)__ffsll((long long)okm) : -1.0;
+    }
+}

@@ -118,6 +118,160 @@ def sch_plant(bits, bsic, fn):
     return bits
 
 
+# ---- the BCCH block (GSM 05.03 section 4.1: SACCH / BCCH coding): 23 octets of system information over four normal bursts ----
+FIRE_POLY = sum(1 << k for k in (40, 26, 23, 17, 3, 0))    # g(D) = (D^23 + 1)(D^17 + D^3 + 1)
+FIRE_ONES = (1 << 40) - 1
+BCCH_FRAMES = (2, 3, 4, 5)                       # frames of the 51-multiframe whose slot 0 carries the BCCH block
+SI_MESSAGE_TYPE = {1: 0x19, 2: 0x1A, 3: 0x1B, 4: 0x1C}     # 04.08 section 10.4
+SI_FILL = 0x2B
+
+
+def bcch_bit_order(octets):
+    """23 octets -> d(0..183), d(8n + k) = bit k of octet n (LSB first).  Unpinned against a real capture: this
+    function and bcch_octets below are the one place to pin the order."""
+    o = np.asarray(octets, dtype=np.int64).ravel()
+    if o.shape != (23,) or np.any(o < 0) or np.any(o > 255):
+        raise ValueError("a BCCH block is 23 octets")
+    return ((o[:, None] >> np.arange(8)[None, :]) & 1).astype(np.int8).ravel()
+
+
+def bcch_octets(d):
+    """the inverse of bcch_bit_order: d(0..183) -> (23,) uint8"""
+    d = np.asarray(d, dtype=np.int64).reshape(23, 8)
+    return np.sum(d << np.arange(8)[None, :], axis=1).astype(np.uint8)
+
+
+def fire_remainder(word):
+    """remainder (40 bits, as an integer, D^39 the top bit) of the bit sequence `word` (first bit = highest power) divided by the
+    Fire code's g(D) = D^40 + D^26 + D^23 + D^17 + D^3 + 1"""
+    reg = 0
+    for bit in np.asarray(word).tolist():
+        reg = (reg << 1) | int(bit)
+        if reg >> 40:
+            reg ^= FIRE_POLY
+    return reg
+
+
+def bcch_interleave_map():
+    """(456, 2): coded bit c(k) goes to burst B = k mod 4 of the block, position j = 2 ((49 k) mod 57) + ((k mod 8) div 4) of that
+    burst's 114 data bits"""
+    k = np.arange(456)
+    return np.stack([k % 4, 2 * ((49 * k) % 57) + (k % 8) // 4], axis=1)
+
+
+def bcch_data_symbol(j):
+    """data bit i(B, j), j = 0..113 -> its bit of the 148-bit normal burst: e(j) for j < 57, e(j + 2) behind the two stealing
+    flags e(57), e(58); e(0..57) are burst bits 3..60 and e(58..115) burst bits 87..144"""
+    j = np.asarray(j)
+    return np.where(j < 57, 3 + j, 31 + j)
+
+
+BCCH_STEAL_SYMBOLS = (60, 87)                    # e(57), e(58)
+
+
+def bcch_block_encode(octets):
+    """23 octets -> (4, 116) int8, the e(B, 0..115) of the block's four bursts: 184 information bits, 40 parity bits (the inverted
+    Fire remainder, so that the 224-bit word leaves all ones), 4 zero tail bits, the rate-1/2 code of the SCH (the same generators),
+    the interleaver of 05.03 section 4.1.4, and the two stealing flags set."""
+    d = bcch_bit_order(octets)
+    rem = fire_remainder(np.concatenate([d, np.zeros(40, np.int8)])) ^ FIRE_ONES
+    par = np.array([(rem >> (39 - i)) & 1 for i in range(40)], dtype=np.int8)
+    c = sch_conv_encode(np.concatenate([d, par, np.zeros(4, np.int8)]))
+    m = bcch_interleave_map()
+    i = np.zeros((4, 114), dtype=np.int8)
+    i[m[:, 0], m[:, 1]] = c
+    e = np.ones((4, 116), dtype=np.int8)
+    e[:, :57] = i[:, :57]
+    e[:, 59:] = i[:, 57:]
+    return e
+
+
+def bcch_plant(bits, e):
+    """overwrite the 116 payload bits (stealing flags included) of the 148 normal-burst bits (in place)"""
+    bits[3:61] = e[:58]
+    bits[87:145] = e[58:]
+    return bits
+
+
+def _bcd_digits(value, what, allowed):
+    s = value if isinstance(value, str) else ("%d" % int(value)).rjust(min(allowed), "0")
+    if not s.isdigit() or len(s) not in allowed:
+        raise ValueError("%s: %s decimal digits" % (what, " or ".join(str(a) for a in allowed)))
+    return [int(ch) for ch in s]
+
+
+def lai_octets(mcc, mnc, lac):
+    """The five octets of the location area identification (04.08 section 10.5.1.3): MCC digit 2 | digit 1, MNC digit 3 | MCC
+    digit 3, MNC digit 2 | digit 1, then the LAC big-endian.  mnc: an int below 100 is a 2-digit MNC (its third digit is the
+    filler 0xF), 100..999 a 3-digit one; a string gives the digits as written ("012")."""
+    m, n = _bcd_digits(mcc, "mcc", (3,)), _bcd_digits(mnc, "mnc", (2, 3))
+    lac = int(lac)
+    if not 0 <= lac <= 0xFFFF:
+        raise ValueError("lac: 0..65535")
+    n3 = n[2] if len(n) == 3 else 0xF
+    return [m[1] << 4 | m[0], n3 << 4 | m[2], n[1] << 4 | n[0], lac >> 8, lac & 0xFF]
+
+
+def _si_octets(si_type, length, body):
+    o = [(length << 2) | 1, 0x06, SI_MESSAGE_TYPE[si_type]] + body
+    return np.array(o + [SI_FILL] * (23 - len(o)), dtype=np.uint8)
+
+
+def si3_octets(cell_id, mcc, mnc, lac):
+    """A SYSTEM INFORMATION TYPE 3 block: L2 pseudo-length, protocol discriminator 0x06, message type 0x1B, the cell identity
+    in octets 3-4 (big-endian), the LAI in octets 5-9, the rest 0x2B"""
+    cell_id = int(cell_id)
+    if not 0 <= cell_id <= 0xFFFF:
+        raise ValueError("cell_id: 0..65535")
+    return _si_octets(3, 18, [cell_id >> 8, cell_id & 0xFF] + lai_octets(mcc, mnc, lac))
+
+
+def si4_octets(mcc, mnc, lac):
+    """A SYSTEM INFORMATION TYPE 4 block: the LAI in octets 3-7"""
+    return _si_octets(4, 12, lai_octets(mcc, mnc, lac))
+
+
+def si_fields(octets):
+    """The Python statement of gsmcal_si_fields (include/gsmcal_si.h): 23 octets -> dict(valid, msg_type, si_type, cell_id, mcc,
+    mnc, mnc_digits, lac); the fields are -1 where the message does not carry them, valid is 0 for anything not recognised
+    (another pseudo-length form or protocol discriminator, another message type, BCD digits above 9 other than the MNC filler)."""
+    o = [int(v) for v in np.asarray(octets).ravel()]
+    out = {"valid": 0, "msg_type": o[2], "si_type": 0, "cell_id": -1, "mcc": -1, "mnc": -1, "mnc_digits": -1, "lac": -1}
+    if len(o) != 23 or (o[0] & 3) != 1 or o[1] != 0x06:
+        return out
+    types = {v: k for k, v in SI_MESSAGE_TYPE.items()}
+    if o[2] not in types:
+        return out
+    out["si_type"] = types[o[2]]
+    if out["si_type"] < 3:
+        out["valid"] = 1
+        return out
+    at = 5 if out["si_type"] == 3 else 3
+    m = [o[at] & 15, o[at] >> 4, o[at + 1] & 15]
+    n = [o[at + 2] & 15, o[at + 2] >> 4, o[at + 1] >> 4]
+    if max(m) > 9 or max(n[:2]) > 9 or (n[2] > 9 and n[2] != 0xF):
+        return out
+    if out["si_type"] == 3:
+        out["cell_id"] = o[3] << 8 | o[4]
+    out["mcc"] = 100 * m[0] + 10 * m[1] + m[2]
+    out["mnc_digits"] = 2 if n[2] == 0xF else 3
+    out["mnc"] = 10 * n[0] + n[1] if n[2] == 0xF else 100 * n[0] + 10 * n[1] + n[2]
+    out["lac"] = o[at + 3] << 8 | o[at + 4]
+    out["valid"] = 1
+    return out
+
+
+def _si_args(si):
+    """si= of ideal_waveform / make_stream -> a (count, 23) uint8 array, or None"""
+    if si is None:
+        return None
+    a = np.asarray(si)
+    a = a.reshape(1, 23) if a.ndim == 1 else a
+    if a.ndim != 2 or a.shape[1] != 23 or a.shape[0] < 1 or np.any(a < 0) or np.any(a > 255):
+        raise ValueError("si: 23 octets, or a sequence of such blocks")
+    return a.astype(np.uint8)
+
+
 def _qfunc(x):
     return 0.5 * np.array([math.erfc(v / math.sqrt(2.0)) for v in np.ravel(x)]).reshape(np.shape(x))
 
@@ -224,13 +378,18 @@ def _sch_payload_args(start_frame, bsic, fn0):
     return bsic, fn0
 
 
-def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0, bsic=None, fn0=None):
+def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0, bsic=None, fn0=None, si=None):
     """Complex baseband at exactly 8 samples/symbol, num_frames TDMA frames starting at frame
     `start_frame` of the 51-multiframe.  bcch=False gives a traffic-only carrier (no FCCH/SCH).
     tsc: the training sequence code (0..7) every normal burst carries.
     bsic / fn0: plant sch_encode(bsic, fn0 + frame) in every SCH burst (fn0 mod 51 == start_frame; the frame number wraps at
-    HYPERFRAME).  The random payload is drawn first and then overwritten, so everything else of the waveform is unchanged."""
+    HYPERFRAME).  The random payload is drawn first and then overwritten, so everything else of the waveform is unchanged.
+    si: 23 octets, or a sequence of such blocks: bcch_block_encode(si[(frame number div 51) mod len(si)]) is planted in the slot-0
+    bursts of frames 2..5 of every multiframe (the frame number counts from fn0, or from start_frame without one), again over
+    the random payload that was drawn first."""
     payload = _sch_payload_args(start_frame, bsic, fn0)
+    blocks = _si_args(si) if bcch else None
+    coded = {}
     n = num_frames * FRAME_OV
     x = np.zeros(n, dtype=np.complex128)
     # all bursts of the stream are modulated in one vectorised pass: bits -> (nb, 148)
@@ -251,6 +410,12 @@ def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0, bsic=None, fn
         bits[i, PRE:PRE + BURST_BITS] = _burst_bits("N" if k == "I" else k, rng, tsc)
         if k == "S" and payload is not None:
             sch_plant(bits[i, PRE:PRE + BURST_BITS], payload[0], (payload[1] + i // 8) % HYPERFRAME)
+        if blocks is not None and i % 8 == 0 and (start_frame + i // 8) % 51 in BCCH_FRAMES:
+            fn = ((start_frame if payload is None else payload[1]) + i // 8) % HYPERFRAME
+            which = (fn // 51) % len(blocks)
+            if which not in coded:
+                coded[which] = bcch_block_encode(blocks[which])
+            bcch_plant(bits[i, PRE:PRE + BURST_BITS], coded[which][(start_frame + i // 8) % 51 - BCCH_FRAMES[0]])
     prev = np.concatenate([np.zeros((nb, 1), np.int8), bits[:, :-1]], axis=1)
     pre = 1 - np.abs(bits - prev)                       # diff_precode per burst
     a = 2.0 * pre.astype(np.float64) - 1.0
@@ -273,14 +438,16 @@ def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0, bsic=None, fn
 
 def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
                 sampling_ppm=None, carrier_ppm=None, snr_db=None, carrier_freq=957.4e6,
-                start_frame=None, frac_start=None, tx_key=None, tsc=0, bsic=None, fn0=None):
+                start_frame=None, frac_start=None, tx_key=None, tsc=0, bsic=None, fn0=None, si=None):
     """One capture: returns (raw uint8 interleaved I,Q of length 2*num_frames*10000, truth dict).
     tx_key: dongles given the same key receive the SAME transmission (payload, multiframe phase, start instant) through
     their own clocks, carrier offsets and noise -- what gsm_sync_demod.m's inter-dongle phase plot (:151-158) looks at.
     tsc: the cell's training sequence code (0..7), planted in every normal burst.
     bsic / fn0: the SCH payload (ideal_waveform): the cell's BSIC and the GSM frame number of the waveform's first frame, which
     needs start_frame given with fn0 mod 51 == start_frame.  Left at None the SCH payload stays random and the capture is
-    byte-identical to what it always was."""
+    byte-identical to what it always was.
+    si: the system information the BCCH blocks carry (ideal_waveform; si3_octets / si4_octets build one); None leaves their
+    payload random and the capture byte-identical likewise."""
     rng = np.random.Generator(np.random.Philox(key=[int(seed), (int(dongle) << 20) ^ int(arfcn)]))
     eps_s = rng.uniform(-80.0, 80.0) if sampling_ppm is None else float(sampling_ppm)
     eps_c = rng.uniform(-40.0, 40.0) if carrier_ppm is None else float(carrier_ppm)
@@ -289,14 +456,14 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     fs0 = rng.uniform(0.0, FRAME_OV) if frac_start is None else float(frac_start)
     n = num_frames * FRAME_OV
     if tx_key is None:
-        ideal = ideal_waveform(num_frames + 2, sf, rng, bcch=bcch, tsc=tsc, bsic=bsic, fn0=fn0)
+        ideal = ideal_waveform(num_frames + 2, sf, rng, bcch=bcch, tsc=tsc, bsic=bsic, fn0=fn0, si=si)
     else:
         txr = np.random.Generator(np.random.Philox(key=[int(seed) ^ 0x5A5A5A5A, int(tx_key)]))
         if start_frame is None:
             sf = int(txr.integers(0, 51))
         if frac_start is None:
             fs0 = txr.uniform(0.0, FRAME_OV)
-        ideal = ideal_waveform(num_frames + 2, sf, txr, bcch=bcch, tsc=tsc, bsic=bsic, fn0=fn0)
+        ideal = ideal_waveform(num_frames + 2, sf, txr, bcch=bcch, tsc=tsc, bsic=bsic, fn0=fn0, si=si)
     # the dongle's clock runs (1+eps_s) fast => sample k is taken at ideal time k/(1+eps_s)... the
     # estimator's sign convention (FCCH_fine_correction.m:111-115): observed spacing = ideal*(1+e)
     # means the dongle takes MORE samples per GSM frame, i.e. query ideal time t_k = k/(1+e).
@@ -321,6 +488,7 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
              "frac_start": fs0, "carrier_freq": carrier_freq, "bcch": bcch}
     payload = _sch_payload_args(sf, bsic, fn0) if bcch else None
     truth["bsic"], truth["fn0"] = payload if payload is not None else (None, None)
+    truth["si"] = _si_args(si) if bcch else None
     return raw, truth
 
 
