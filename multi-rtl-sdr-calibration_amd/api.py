@@ -360,13 +360,17 @@ def SCH_corr_rate_correction(s, FCCH_pos, sch_training_sequence, oversampling_ra
     return pos_info, rr, sp.value
 
 
+def _pos_info_in(pos_info):
+    """pos_info as a MATLAB-signature wrapper takes it -> (the (rows, 2) table, rows, its column-major copy with ld = rows)"""
+    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
+    return pi, pi.shape[0], np.ascontiguousarray(pi.T)
+
+
 def carrier_correct_post_SCH(s, pos_info, oversampling_ratio, carrier_freq, ctx=None, want_r=True):
     """[r, carrier_ppm] = carrier_correct_post_SCH(...) -- carrier_correct_post_SCH.m:5."""
     ctx = ctx or default_context()
     buf, n = _r_in(s)
-    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
-    rows = pi.shape[0]
-    pic = np.ascontiguousarray(pi.T)  # column-major, ld = rows
+    pi, rows, pic = _pos_info_in(pos_info)
     r = np.empty(n if want_r else 0, dtype=np.complex128)
     lr = C.c_long()
     cp = C.c_double()
@@ -384,9 +388,7 @@ def SCH_equalise(s, pos_info, training_sequence, oversampling_ratio, ctx=None):
     every SCH row of pos_info, shape (num_sch, 194*ov).  pos_info all -1 (:8-11) -> None."""
     ctx = ctx or default_context()
     buf, n = _r_in(s)
-    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
-    rows = pi.shape[0]
-    pic = np.ascontiguousarray(pi.T)
+    pi, rows, pic = _pos_info_in(pos_info)
     ts = np.ascontiguousarray(np.asarray(training_sequence, dtype=np.complex128).ravel())
     L = 194 * int(oversampling_ratio)
     cap = int(np.sum(pi[:, 1] == 1)) if pi.shape[1] > 1 else 0
@@ -407,9 +409,7 @@ def FCCH_demod(s, pos_info, oversampling_ratio, carrier_freq, ctx=None):
     `carrier_ppm`.  Returns a dict of these, or None at the :8 exit (pos_info all -1)."""
     ctx = ctx or default_context()
     buf, n = _r_in(s)
-    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
-    rows = pi.shape[0]
-    pic = np.ascontiguousarray(pi.T)
+    pi, rows, pic = _pos_info_in(pos_info)
     cap = int(np.sum(pi[:, 1] == 0)) if pi.shape[1] > 1 else 0
     freq, snr, idx = (np.full(max(cap, 1), np.nan) for _ in range(3))
     nb = C.c_int()
@@ -442,9 +442,7 @@ def BCCH_demod(s, pos_info, normal_training_sequence, oversampling_ratio, carrie
     `row` is the (BCCH_COLS,) table row bcch_demod_batch holds for this stream."""
     ctx = ctx or default_context()
     buf, n = _r_in(s)
-    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
-    rows = pi.shape[0]
-    pic = np.ascontiguousarray(pi.T)
+    pi, rows, pic = _pos_info_in(pos_info)
     ts, len_ts = _templates_in(normal_training_sequence, oversampling_ratio)
     r = np.empty(n, dtype=np.complex128) if want_r and n > 0 else None
     idx, lr, cp = C.c_int(), C.c_long(), C.c_double()
@@ -480,9 +478,7 @@ def SCH_decode(s, pos_info, sch_training_sequence, oversampling_ratio, ctx=None,
     -- and with want_soft `soft` (num_sch, 148); `row` is the (SCH_COLS,) table row sch_decode_batch holds for this stream."""
     ctx = ctx or default_context()
     buf, n = _r_in(s)
-    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
-    rows = pi.shape[0]
-    pic = np.ascontiguousarray(pi.T)
+    pi, rows, pic = _pos_info_in(pos_info)
     ts, len_ts = _sch_template_in(sch_training_sequence)
     bsic, fn, pos = C.c_int(), C.c_long(), C.c_long()
     row = np.full(SCH_COLS, np.nan)
@@ -539,9 +535,7 @@ def BCCH_decode(s, pos_info, tsc, oversampling_ratio, ctx=None, want_soft=False)
     for this stream."""
     ctx = ctx or default_context()
     buf, n = _r_in(s)
-    pi = np.atleast_2d(np.asarray(pos_info, dtype=np.float64))
-    rows = pi.shape[0]
-    pic = np.ascontiguousarray(pi.T)
+    pi, rows, pic = _pos_info_in(pos_info)
     row = np.full(SI_COLS, np.nan)
     octets = np.zeros((MAX_HITS, BLOCK_OCTETS), dtype=np.uint8)
     soft = np.empty((MAX_HITS, BLOCK_CODED)) if want_soft else None
@@ -704,15 +698,39 @@ def cw_check_batch_dev(d_raw, d, n, thr, d_summary, d_r=None, r_stride=0, ctx=No
                                                 C.c_void_p(d_r) if d_r else None, int(r_stride)), "cw_check_batch_dev")
 
 
+def _opt(p):
+    """an optional device pointer"""
+    return C.c_void_p(p) if p else None
+
+
+def _post_batch_in(r_correct, r_len, pos_info_raw):
+    """What calibrate_batch(..., want_r=True) returns, as the *_batch wrappers of the demod family pass it on -> r (D, N), D, N,
+    r_len (D,) int64, pos_info (D, 2, MAX_POS_ROWS)"""
+    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
+    d, stride = r.shape
+    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
+    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
+    if len(rl) != d:
+        raise ValueError("r_len must have one entry per stream")
+    return r, d, stride, rl, pi
+
+
+def _table_rows(table, cols, head_fields, block_fields, width):
+    """(D, cols) table -> dict of its columns: the head fields one column each, then `width` columns per block field"""
+    t = np.asarray(table).reshape(-1, cols)
+    out = {k: t[:, i] for i, k in enumerate(head_fields)}
+    n = len(head_fields)
+    for j, name in enumerate(block_fields):
+        out[name] = t[:, n + j * width: n + (j + 1) * width]
+    return out
+
+
 DEMOD_FIELDS = ("num_fcch", "mean_freq", "carrier_ppm", "status")      # columns 0..3 of a demod row; then freq | snr | max_idx
 
 
 def demod_rows(table):
     """(D, DEMOD_COLS) table of fcch_demod_batch[_dev] -> dict of its columns (freq, snr, max_idx: (D, MAX_HITS), NaN unused)."""
-    t = np.asarray(table).reshape(-1, DEMOD_COLS)
-    out = {k: t[:, i] for i, k in enumerate(DEMOD_FIELDS)}
-    out["freq"], out["snr"], out["max_idx"] = (t[:, 4 + j * MAX_HITS: 4 + (j + 1) * MAX_HITS] for j in range(3))
-    return out
+    return _table_rows(table, DEMOD_COLS, DEMOD_FIELDS, ("freq", "snr", "max_idx"), MAX_HITS)
 
 
 def fcch_demod_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, carrier_freq, ctx=None):
@@ -720,12 +738,7 @@ def fcch_demod_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, carrier
     (-1 where the reference returns r = -1), pos_info_raw (D, 2, MAX_POS_ROWS).  Returns the (D, DEMOD_COLS) table (demod_rows
     names its columns); per-row outcomes are in its status column."""
     ctx = ctx or default_context()
-    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
-    d, stride = r.shape
-    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
-    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
-    if len(rl) != d:
-        raise ValueError("r_len must have one entry per stream")
+    r, d, stride, rl, pi = _post_batch_in(r_correct, r_len, pos_info_raw)
     cf = np.ascontiguousarray(np.broadcast_to(np.asarray(carrier_freq, dtype=np.float64), (d,)))
     out = np.empty((d, DEMOD_COLS))
     ctx.check(ctx.lib.gsmcal_fcch_demod_batch(ctx.h, _dp(r), stride, rl.ctypes.data_as(_lib.c_long_p), _dp(pi), d,
@@ -749,10 +762,7 @@ BCCH_FIELDS = ("num_bcch", "tsc_idx", "mean_fo", "carrier_ppm", "status", "num_a
 def bcch_rows(table):
     """(D, BCCH_COLS) table of bcch_demod_batch[_dev] -> dict of its columns (max_idx, peak, runner_up, phase: (D, MAX_BCCH), NaN
     unused; max_idx is the 1-based winning template per burst)."""
-    t = np.asarray(table).reshape(-1, BCCH_COLS)
-    out = {k: t[:, i] for i, k in enumerate(BCCH_FIELDS)}
-    out["max_idx"], out["peak"], out["runner_up"], out["phase"] = (t[:, 6 + j * MAX_BCCH: 6 + (j + 1) * MAX_BCCH] for j in range(4))
-    return out
+    return _table_rows(table, BCCH_COLS, BCCH_FIELDS, ("max_idx", "peak", "runner_up", "phase"), MAX_BCCH)
 
 
 def bcch_demod_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, normal_training_sequence, carrier_freq, ctx=None,
@@ -762,12 +772,7 @@ def bcch_demod_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, normal_
     with want_corr / want_r, a dict: "table", "corr" (D, MAX_BCCH, 8) complex, "r" (D, N) complex and "r_len" (D,), -1 where the
     reference leaves r = -1 (those rows of "r" are zeros)."""
     ctx = ctx or default_context()
-    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
-    d, stride = r.shape
-    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
-    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
-    if len(rl) != d:
-        raise ValueError("r_len must have one entry per stream")
+    r, d, stride, rl, pi = _post_batch_in(r_correct, r_len, pos_info_raw)
     ts, len_ts = _templates_in(normal_training_sequence, oversampling_ratio)
     cf = np.ascontiguousarray(np.broadcast_to(np.asarray(carrier_freq, dtype=np.float64), (d,)))
     out = np.empty((d, BCCH_COLS))
@@ -792,10 +797,9 @@ def bcch_demod_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio
     ctx = ctx or default_context()
     ts, len_ts = _templates_in(normal_training_sequence, oversampling_ratio)
     cf = np.ascontiguousarray(np.broadcast_to(np.asarray(carrier_freq, dtype=np.float64), (int(d),)))
-    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
     ctx.check(ctx.lib.gsmcal_bcch_demod_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
                                                   int(d), int(oversampling_ratio), _dp(ts), len_ts, _dp(cf), C.c_void_p(d_out),
-                                                  opt(d_corr), opt(d_r_out), opt(d_r_len_out)), "bcch_demod_batch_dev")
+                                                  _opt(d_corr), _opt(d_r_out), _opt(d_r_len_out)), "bcch_demod_batch_dev")
 
 
 SCH_FIELDS = ("num_sch", "num_ok", "num_consistent", "bsic", "fn_anchor", "pos_anchor", "status", "mean_slope")   # columns 0..7
@@ -804,11 +808,7 @@ SCH_FIELDS = ("num_sch", "num_ok", "num_consistent", "bsic", "fn_anchor", "pos_a
 def sch_rows(table):
     """(D, SCH_COLS) table of sch_decode_batch[_dev] -> dict of its columns (ok, bsic_b, fn, ts_err, corrected, slope, amp:
     (D, MAX_HITS), NaN for unused entries and for bursts that were not evaluated)."""
-    t = np.asarray(table).reshape(-1, SCH_COLS)
-    out = {k: t[:, i] for i, k in enumerate(SCH_FIELDS)}
-    for j, name in enumerate(("ok", "bsic_b", "fn", "ts_err", "corrected", "slope", "amp")):
-        out[name] = t[:, 8 + j * MAX_HITS: 8 + (j + 1) * MAX_HITS]
-    return out
+    return _table_rows(table, SCH_COLS, SCH_FIELDS, ("ok", "bsic_b", "fn", "ts_err", "corrected", "slope", "amp"), MAX_HITS)
 
 
 def sch_alignment(rows, oversampling_ratio, ref=0):
@@ -833,12 +833,7 @@ def sch_decode_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, sch_tra
     are in its status column) -- or, with want_soft / want_u, a dict: "table", "soft" (D, MAX_HITS, 148), "u" (D, MAX_HITS, 39)
     uint8 (255 where no burst was evaluated)."""
     ctx = ctx or default_context()
-    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
-    d, stride = r.shape
-    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
-    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
-    if len(rl) != d:
-        raise ValueError("r_len must have one entry per stream")
+    r, d, stride, rl, pi = _post_batch_in(r_correct, r_len, pos_info_raw)
     ts, len_ts = _sch_template_in(sch_training_sequence)
     out = np.empty((d, SCH_COLS))
     soft = np.empty((d, MAX_HITS, 148)) if want_soft else None
@@ -858,10 +853,9 @@ def sch_decode_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio
     [d][MAX_HITS][148] doubles, d_u: [d][MAX_HITS][39] bytes.  Device or pinned host memory."""
     ctx = ctx or default_context()
     ts, len_ts = _sch_template_in(sch_training_sequence)
-    opt = lambda p: C.c_void_p(p) if p else None  # noqa: E731
     ctx.check(ctx.lib.gsmcal_sch_decode_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
-                                                  int(d), int(oversampling_ratio), _dp(ts), len_ts, C.c_void_p(d_out), opt(d_soft),
-                                                  opt(d_u)), "sch_decode_batch_dev")
+                                                  int(d), int(oversampling_ratio), _dp(ts), len_ts, C.c_void_p(d_out), _opt(d_soft),
+                                                  _opt(d_u)), "sch_decode_batch_dev")
 
 
 SI_FIELDS = ("num_blocks", "num_ok", "status", "first_ok")          # columns 0..3
@@ -871,11 +865,7 @@ SI_BLOCK_FIELDS = ("ok", "pos", "corrected", "ts_err", "steal", "mean_slope", "a
 def si_rows(table):
     """(D, SI_COLS) table of bcch_decode_batch[_dev] -> dict of its columns (ok, pos, corrected, ts_err, steal, mean_slope, amp:
     (D, MAX_HITS), NaN for unused entries and for blocks that were not evaluated)."""
-    t = np.asarray(table).reshape(-1, SI_COLS)
-    out = {k: t[:, i] for i, k in enumerate(SI_FIELDS)}
-    for j, name in enumerate(SI_BLOCK_FIELDS):
-        out[name] = t[:, 4 + j * MAX_HITS: 4 + (j + 1) * MAX_HITS]
-    return out
+    return _table_rows(table, SI_COLS, SI_FIELDS, SI_BLOCK_FIELDS, MAX_HITS)
 
 
 def _tsc_in(tsc, d):
@@ -892,12 +882,7 @@ def bcch_decode_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, tsc, c
     per-row outcomes are in its status column), "octets" (D, MAX_HITS, 23) uint8, zeros unless the block is ok, and with want_soft
     "soft" (D, MAX_HITS, 456)."""
     ctx = ctx or default_context()
-    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
-    d, stride = r.shape
-    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
-    pi = np.ascontiguousarray(np.asarray(pos_info_raw, dtype=np.float64).reshape(d, 2, MAX_POS_ROWS))
-    if len(rl) != d:
-        raise ValueError("r_len must have one entry per stream")
+    r, d, stride, rl, pi = _post_batch_in(r_correct, r_len, pos_info_raw)
     codes = _tsc_in(tsc, d)
     out = np.empty((d, SI_COLS))
     octets = np.empty((d, MAX_HITS, BLOCK_OCTETS), dtype=np.uint8)
@@ -921,7 +906,7 @@ def bcch_decode_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_rati
     codes = _tsc_in(tsc, int(d))
     ctx.check(ctx.lib.gsmcal_bcch_decode_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
                                                    int(d), int(oversampling_ratio), codes.ctypes.data_as(_lib.c_int_p),
-                                                   C.c_void_p(d_out), C.c_void_p(d_octets), C.c_void_p(d_soft) if d_soft else None),
+                                                   C.c_void_p(d_out), C.c_void_p(d_octets), _opt(d_soft)),
               "bcch_decode_batch_dev")
 
 

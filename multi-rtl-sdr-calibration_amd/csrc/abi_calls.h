@@ -589,6 +589,25 @@ int gsmcal_SCH_corr_rate_correction(gsmcal_ctx* c, const double* s, long len, co
     return positive_status(st, 1);
 }
 
+// ---- pos_info as the MATLAB-signature entry points get it: rows x 2, column-major, leading dimension ld --------------
+// `if pos_info == -1` is true only if every element is -1
+static bool pos_info_all_m1(const double* pos_info, int rows, int ld) {
+    for (int i = 0; i < rows; ++i)
+        if (pos_info[i] != -1.0 || pos_info[ld + i] != -1.0) return false;
+    return true;
+}
+static int pos_info_count(const double* pos_info, int rows, int ld, double type) {
+    int n = 0;
+    for (int i = 0; i < rows; ++i) n += pos_info[ld + i] == type;
+    return n;
+}
+// the table as gsmcal_calibrate_batch hands it on: [2][MAXROWS] with -1 padding (rows <= MAXROWS is the caller's check)
+static std::vector<double> pos_info_padded(const double* pos_info, int rows, int ld) {
+    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);
+    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
+    return pi;
+}
+
 // ---- a8 carrier_correct_post_SCH -------------------------------------------------------------------------
 int gsmcal_carrier_correct_post_SCH(gsmcal_ctx* c, const double* s, long len, const double* pos_info, int rows, int ld,
                                     int ov, double carrier_freq, double* r, long cap_r, long* len_r, double* carrier_ppm) {
@@ -596,8 +615,7 @@ int gsmcal_carrier_correct_post_SCH(gsmcal_ctx* c, const double* s, long len, co
     RET_IF(api_chain_check(ov, 0));
     ENTER(c);
     const Geom g(ov);
-    bool all_m1 = true;                       // `if pos_info == -1` is true only if every element is -1
-    for (int i = 0; i < rows; ++i) all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
+    const bool all_m1 = pos_info_all_m1(pos_info, rows, ld);
     if (!all_m1 && rows > MAXROWS) return GSMCAL_E_CAPACITY;
     const bool have_s = s != nullptr && len >= 1;
     if (have_s) RET_IF(upload_array(c, s, (size_t)len));
@@ -643,9 +661,7 @@ int gsmcal_SCH_equalise(gsmcal_ctx* c, const double* s, long len, const double* 
     const int sp_t0 = (8 + 42) * ov;                            // :56 sp_of_training (0-based)
     *num_bursts = 0;
     if (len_fde_ov) *len_fde_ov = L;
-    bool all_m1 = true;                                         // :8 `if pos_info == -1`: every element
-    for (int i = 0; i < rows; ++i) all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
-    if (all_m1) return GSMCAL_S_POST_NO_POS;
+    if (pos_info_all_m1(pos_info, rows, ld)) return GSMCAL_S_POST_NO_POS;      // :8
     if (!s || len < 1 || !x_eq) return GSMCAL_E_ARG;
     if (sp_t0 + len_ts > L) return GSMCAL_E_ARG;                // the training sequence must fit the window (:58)
     std::vector<long> starts;
@@ -684,9 +700,21 @@ int gsmcal_SCH_equalise(gsmcal_ctx* c, const double* s, long len, const double* 
     return 0;
 }
 
+// ---- the demod family: FCCH_demod, BCCH_demod, SCH_decode, BCCH_decode ------------------------------------------------
+// Each takes (r, r_len, pos_info) of d streams -- r[d][stride] complex, pos_info[d][2][MAXROWS] -- and runs on the context's
+// stream (ENTER_ON_CTX_STREAM).  What the entry points have in common: the argument check, the three input stages of the host
+// forms and their device pointers.  (The macros read the host forms' parameter names.)
+static bool post_args_ok(const gsmcal_ctx* c, const void* r, const void* r_len, const void* pos_info, const void* out, int d, long stride) {
+    return c && r && r_len && pos_info && out && d >= 1 && stride >= 1;
+}
+#define POST_STAGES_IN                                                          \
+    STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),             \
+    STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),                 \
+    STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0)
+#define POST_STAGED_IN (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p
+
 // ---- FCCH_demod.m:5-66: the check behind the calibration ------------------------------------------------------
-// k_fcch_demod (one workgroup per burst slot and stream) + k_fcch_demod_finish (one wave per stream) on the context's stream;
-// nothing of the lanes, the shared taps or the state of the calibrate / scan call before is touched.
+// k_fcch_demod (one workgroup per burst slot and stream) + k_fcch_demod_finish (one wave per stream).
 // The per-burst half, which gsmcal_bcch_demod_batch_dev runs too (BCCH_demod.m:49-68 is the same block): fd_part[d][MAXH][FD_PART]
 // and the carrier frequencies in fd_cf.  The caller has checked its arguments and the oversampling ratio (fcch_demod_ov_ok).
 static bool fcch_demod_ov_ok(int ov) { return ov <= 256 && fd_lds_bytes(148 * ov) <= 159 * 1024; }
@@ -694,7 +722,6 @@ static int fcch_demod_parts(gsmcal_ctx* c, const double* d_r, long stride, const
                      const double* carrier_freq) {
     const int nfft = 148 * ov;                                  // FCCH_demod.m:13-16
     const size_t lds = fd_lds_bytes(nfft);
-    c->cur = &c->lanes[0];                                      // the context's stream; the lane's buffers are not touched
     const double fs = GSM_SYMBOL_RATE * (double)ov;             // :30-31
     const int hnl = (int)ceil(((double)nfft * 200e3 / fs) / 2.0);   // :53 half_noise_len (55 for every ov)
     if (c->fd_tw_n != nfft) {
@@ -714,26 +741,22 @@ static int fcch_demod_parts(gsmcal_ctx* c, const double* d_r, long stride, const
 
 int gsmcal_fcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
                                 int ov, const double* carrier_freq, double* d_out) {
-    if (!c || !d_r || !d_r_len || !d_pos_info || !carrier_freq || !d_out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    if (!post_args_ok(c, d_r, d_r_len, d_pos_info, d_out, d, stride) || !carrier_freq || ov < 1) return GSMCAL_E_ARG;
     if (!fcch_demod_ov_ok(ov)) return GSMCAL_E_UNSUPPORTED;
-    ENTER(c);
+    ENTER_ON_CTX_STREAM(c);
     RET_IF(fcch_demod_parts(c, d_r, stride, d_r_len, d_pos_info, d, ov, carrier_freq));
-    LAUNCH(c, k_fcch_demod_finish, dim3(d), dim3(64), 0, d_r_len, d_pos_info, (const double*)c->fd_cf.p, (const double*)c->fd_part.p, d_out);
+    LAUNCH(c, k_fcch_demod_finish, dim3(d), dim3(64), 0, d_r_len, stride, d_pos_info, (const double*)c->fd_cf.p, (const double*)c->fd_part.p, d_out);
     CHECK_LAUNCH(c);
     return 0;
 }
 
 int gsmcal_fcch_demod_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
                             const double* carrier_freq, double* out) {
-    if (!c || !r || !r_len || !pos_info || !carrier_freq || !out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    if (!post_args_ok(c, r, r_len, pos_info, out, d, stride) || !carrier_freq || ov < 1) return GSMCAL_E_ARG;
     ENTER(c);
-    const Stage io[] = {STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),
-                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
-                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
-                        STAGE(fd_out, (size_t)d * GSMCAL_DEMOD_COLS * sizeof(double), nullptr, out, 0)};
+    const Stage io[] = {POST_STAGES_IN, STAGE(fd_out, (size_t)d * GSMCAL_DEMOD_COLS * sizeof(double), nullptr, out, 0)};
     RET_IF(stage_up(c, io));
-    RET_IF(gsmcal_fcch_demod_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d, ov,
-                                       carrier_freq, (double*)c->fd_out.p));
+    RET_IF(gsmcal_fcch_demod_batch_dev(c, POST_STAGED_IN, d, ov, carrier_freq, (double*)c->fd_out.p));
     return stage_down(c, io);
 }
 
@@ -745,23 +768,16 @@ int gsmcal_FCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* po
     if (mean_freq) *mean_freq = NAN;
     if (carrier_ppm) *carrier_ppm = NAN;
     std::vector<double> row(GSMCAL_DEMOD_COLS, NAN);
-    bool all_m1 = true;                                         // :8 `if pos_info == -1`: every element
-    int nb = 0;
-    for (int i = 0; i < rows; ++i) {
-        all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
-        nb += pos_info[ld + i] == 0.0;
-    }
-    if (all_m1) {
+    if (pos_info_all_m1(pos_info, rows, ld)) {                  // :8
         row[GSMCAL_D_STATUS] = GSMCAL_S_POST_NO_POS;
         c->report = report_fcch_demod(row.data());
         return GSMCAL_S_POST_NO_POS;
     }
+    const int nb = pos_info_count(pos_info, rows, ld, 0.0);
     if (!s || len < 1) return GSMCAL_E_ARG;
     if (rows > MAXROWS || nb > MAXH || nb > cap) return GSMCAL_E_CAPACITY;
     if (nb > 0 && (!freq || !snr || !max_idx)) return GSMCAL_E_ARG;
-    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
-    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
-    RET_IF(gsmcal_fcch_demod_batch(c, s, len, &len, pi.data(), 1, ov, &carrier_freq, row.data()));
+    RET_IF(gsmcal_fcch_demod_batch(c, s, len, &len, pos_info_padded(pos_info, rows, ld).data(), 1, ov, &carrier_freq, row.data()));
     const int status = (int)row[GSMCAL_D_STATUS];
     if (status < 0) return status;                              // MATLAB: index exceeds matrix dimensions at s(sp:ep), :26
     for (int i = 0; i < nb; ++i) { freq[i] = row[GSMCAL_D_FREQ + i]; snr[i] = row[GSMCAL_D_SNR + i]; max_idx[i] = row[GSMCAL_D_MAX_IDX + i]; }
@@ -774,20 +790,24 @@ int gsmcal_FCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* po
 
 // ---- BCCH_demod.m: the training sequence code of the BCCH bursts ---------------------------------------------------
 // k_fcch_demod (the tone estimates of :49-68), k_bcch_corr (BC_GRID_X workgroups per stream, striding over its BCCH rows),
-// k_bcch_finish (one wave per stream) and, when r is asked for, k_bcch_rotate -- on the context's stream, in FCCH_demod's
-// workspace plus bc_*; nothing of the lanes or of the chain's state is touched.
+// k_bcch_finish (one wave per stream) and, when r is asked for, k_bcch_rotate, in FCCH_demod's workspace plus bc_*.
+static int bcch_r_out_check(gsmcal_ctx* c, const double* r, long stride, int d, const double* r_out, const long* r_len_out) {
+    if ((r_out != nullptr) != (r_len_out != nullptr)) { c->err = "BCCH_demod: r_out and r_len_out go together"; return GSMCAL_E_ARG; }
+    if (r_out) {                                                // a stream rotated in place would be read after it was written
+        const uintptr_t a = (uintptr_t)r, b = (uintptr_t)r_out, bytes = (uintptr_t)d * (uintptr_t)stride * sizeof(cplx);
+        if (a < b + bytes && b < a + bytes) { c->err = "BCCH_demod: r_out overlaps r"; return GSMCAL_E_ARG; }
+    }
+    return 0;
+}
+
 int gsmcal_bcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
                                 int ov, const double* nts, int len_ts, const double* carrier_freq, double* d_out, double* d_corr,
                                 double* d_r_out, long* d_r_len_out) {
-    if (!c || !d_r || !d_r_len || !d_pos_info || !nts || !carrier_freq || !d_out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
+    if (!post_args_ok(c, d_r, d_r_len, d_pos_info, d_out, d, stride) || !nts || !carrier_freq || ov < 1) return GSMCAL_E_ARG;
     if (!fcch_demod_ov_ok(ov)) return GSMCAL_E_UNSUPPORTED;
     if (len_ts != 26 * ov) { c->err = "BCCH_demod: the templates must be 26*oversampling_ratio samples long"; return GSMCAL_E_ARG; }
-    if ((d_r_out != nullptr) != (d_r_len_out != nullptr)) { c->err = "BCCH_demod: r_out and r_len_out go together"; return GSMCAL_E_ARG; }
-    if (d_r_out) {                                              // a stream rotated in place would be read after it was written
-        const uintptr_t a = (uintptr_t)d_r, b = (uintptr_t)d_r_out, bytes = (uintptr_t)d * (uintptr_t)stride * sizeof(cplx);
-        if (a < b + bytes && b < a + bytes) { c->err = "BCCH_demod: r_out overlaps r"; return GSMCAL_E_ARG; }
-    }
-    ENTER(c);
+    RET_IF(bcch_r_out_check(c, d_r, stride, d, d_r_out, d_r_len_out));
+    ENTER_ON_CTX_STREAM(c);
     RET_IF(fcch_demod_parts(c, d_r, stride, d_r_len, d_pos_info, d, ov, carrier_freq));
     RET_IF(upload_if_changed(c, c->bc_ts, c->h_bc_ts, nts, (size_t)2 * 8 * len_ts, "BCCH_demod templates"));
     RET_IF(ensure(c, c->bc_corr, (size_t)d * BC_SLOTS * 8 * sizeof(cplx)));
@@ -816,25 +836,19 @@ int gsmcal_bcch_demod_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, c
 int gsmcal_bcch_demod_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
                             const double* nts, int len_ts, const double* carrier_freq, double* out, double* corr, double* r_out,
                             long* r_len_out) {
-    if (!c || !r || !r_len || !pos_info || !nts || !carrier_freq || !out || d < 1 || stride < 1 || ov < 1) return GSMCAL_E_ARG;
-    if ((r_out != nullptr) != (r_len_out != nullptr)) { c->err = "BCCH_demod: r_out and r_len_out go together"; return GSMCAL_E_ARG; }
-    if (r_out) {
-        const uintptr_t a = (uintptr_t)r, b = (uintptr_t)r_out, bytes = (uintptr_t)d * (uintptr_t)stride * sizeof(cplx);
-        if (a < b + bytes && b < a + bytes) { c->err = "BCCH_demod: r_out overlaps r"; return GSMCAL_E_ARG; }
-    }
+    if (!post_args_ok(c, r, r_len, pos_info, out, d, stride) || !nts || !carrier_freq || ov < 1) return GSMCAL_E_ARG;
+    RET_IF(bcch_r_out_check(c, r, stride, d, r_out, r_len_out));
     ENTER(c);
     const size_t nr = (size_t)d * stride * sizeof(cplx);
-    const Stage io[] = {STAGE(fd_in, nr, r, nullptr, 0),
-                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
-                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
+    const Stage io[] = {POST_STAGES_IN,
                         STAGE(bc_out, (size_t)d * GSMCAL_BCCH_COLS * sizeof(double), nullptr, out, 0),
                         STAGE(bc_corr_out, corr ? (size_t)d * BC_SLOTS * 8 * sizeof(cplx) : 0, nullptr, corr, 0),
                         STAGE(bc_r, r_out ? nr : 0, nullptr, r_out, 0),
                         STAGE(bc_rlen, r_out ? (size_t)d * sizeof(long) : 0, nullptr, r_len_out, 0)};
     RET_IF(stage_up(c, io));
     if (r_out) HIPCHK(c, hipMemsetAsync(c->bc_r.p, 0, nr, c->stream));      // rows the reference leaves at r = -1 come back as zeros
-    RET_IF(gsmcal_bcch_demod_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d, ov,
-                                       nts, len_ts, carrier_freq, (double*)c->bc_out.p, corr ? (double*)c->bc_corr_out.p : nullptr,
+    RET_IF(gsmcal_bcch_demod_batch_dev(c, POST_STAGED_IN, d, ov, nts, len_ts, carrier_freq, (double*)c->bc_out.p,
+                                       corr ? (double*)c->bc_corr_out.p : nullptr,
                                        r_out ? (double*)c->bc_r.p : nullptr, r_out ? (long*)c->bc_rlen.p : nullptr));
     return stage_down(c, io);
 }
@@ -848,13 +862,8 @@ int gsmcal_BCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* po
     if (len_r) *len_r = -1;
     if (carrier_ppm) *carrier_ppm = -1.0;
     std::vector<double> row(GSMCAL_BCCH_COLS, NAN);
-    bool all_m1 = true;                                         // :9 `if pos_info == -1`: every element
-    int n0 = 0;
-    for (int i = 0; i < rows; ++i) {
-        all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
-        n0 += pos_info[ld + i] == 0.0;
-    }
-    if (all_m1) {
+    const int n0 = pos_info_count(pos_info, rows, ld, 0.0);
+    if (pos_info_all_m1(pos_info, rows, ld)) {                  // :9
         row[GSMCAL_B_NUM_BCCH] = 0.0; row[GSMCAL_B_TSC_IDX] = -1.0; row[GSMCAL_B_STATUS] = GSMCAL_S_POST_NO_POS;
         if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
         c->report.clear();                                      // the .m file prints nothing at :9
@@ -863,11 +872,9 @@ int gsmcal_BCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* po
     if (!s || len < 1) return GSMCAL_E_ARG;
     if (rows > MAXROWS) return GSMCAL_E_CAPACITY;
     if (r && cap_r < len) return GSMCAL_E_CAPACITY;
-    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
-    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
     std::vector<double> corr((size_t)BC_SLOTS * 8 * 2);
     long lr = -1;
-    RET_IF(gsmcal_bcch_demod_batch(c, s, len, &len, pi.data(), 1, ov, nts, len_ts, &carrier_freq, row.data(), corr.data(), r,
+    RET_IF(gsmcal_bcch_demod_batch(c, s, len, &len, pos_info_padded(pos_info, rows, ld).data(), 1, ov, nts, len_ts, &carrier_freq, row.data(), corr.data(), r,
                                    r ? &lr : nullptr));
     if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
     const int status = (int)row[GSMCAL_B_STATUS];
@@ -891,8 +898,7 @@ int gsmcal_BCCH_demod(gsmcal_ctx* c, const double* s, long len, const double* po
 }
 
 // ---- SCH_decode: the BSIC and the frame number in the SCH bursts -----------------------------------------
-// k_sch_decode (one wave per burst slot and stream) + k_sch_finish (one wave per stream) on the context's stream, in sd_part;
-// nothing of the lanes or of the chain's state is touched.
+// k_sch_decode (one wave per burst slot and stream) + k_sch_finish (one wave per stream), in sd_part.
 static int sch_decode_args(gsmcal_ctx* c, int ov, const double* ts, int len_ts) {
     if (ov != 2 && ov != 4 && ov != 8) { c->err = "SCH_decode: oversampling ratios 2, 4 and 8 only"; return GSMCAL_E_UNSUPPORTED; }
     if (!ts || len_ts != 64 * ov) { c->err = "SCH_decode: the template must be 64*oversampling_ratio samples long"; return GSMCAL_E_ARG; }
@@ -901,10 +907,9 @@ static int sch_decode_args(gsmcal_ctx* c, int ov, const double* ts, int len_ts) 
 
 int gsmcal_sch_decode_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
                                 int ov, const double* sch_ts, int len_ts, double* d_out, double* d_soft, unsigned char* d_u) {
-    if (!c || !d_r || !d_r_len || !d_pos_info || !d_out || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    if (!post_args_ok(c, d_r, d_r_len, d_pos_info, d_out, d, stride)) return GSMCAL_E_ARG;
     RET_IF(sch_decode_args(c, ov, sch_ts, len_ts));
-    ENTER(c);
-    c->cur = &c->lanes[0];                                      // the context's stream; the lane's buffers are not touched
+    ENTER_ON_CTX_STREAM(c);
     RET_IF(ensure(c, c->sd_part, (size_t)d * MAXH * SD_PART * sizeof(double)));
     double* part = (double*)c->sd_part.p;
     for_capture_chunks(d, [&](long lo, int S) {
@@ -919,19 +924,16 @@ int gsmcal_sch_decode_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, c
 
 int gsmcal_sch_decode_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
                             const double* sch_ts, int len_ts, double* out, double* soft, unsigned char* u) {
-    if (!c || !r || !r_len || !pos_info || !out || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    if (!post_args_ok(c, r, r_len, pos_info, out, d, stride)) return GSMCAL_E_ARG;
     RET_IF(sch_decode_args(c, ov, sch_ts, len_ts));
     ENTER(c);
-    const Stage io[] = {STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),
-                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
-                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
+    const Stage io[] = {POST_STAGES_IN,
                         STAGE(sd_out, (size_t)d * GSMCAL_SCH_COLS * sizeof(double), nullptr, out, 0),
                         STAGE(sd_soft, soft ? (size_t)d * MAXH * 148 * sizeof(double) : 0, nullptr, soft, 0),
                         STAGE(sd_u, u ? (size_t)d * MAXH * 39 : 0, nullptr, u, 0)};
     RET_IF(stage_up(c, io));
-    RET_IF(gsmcal_sch_decode_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d, ov,
-                                       sch_ts, len_ts, (double*)c->sd_out.p, soft ? (double*)c->sd_soft.p : nullptr,
-                                       u ? (unsigned char*)c->sd_u.p : nullptr));
+    RET_IF(gsmcal_sch_decode_batch_dev(c, POST_STAGED_IN, d, ov, sch_ts, len_ts, (double*)c->sd_out.p,
+                                       soft ? (double*)c->sd_soft.p : nullptr, u ? (unsigned char*)c->sd_u.p : nullptr));
     return stage_down(c, io);
 }
 
@@ -946,9 +948,7 @@ int gsmcal_SCH_decode(gsmcal_ctx* c, const double* s, long len, const double* po
     if (pos_anchor) *pos_anchor = -1;
     c->report.clear();
     std::vector<double> row(GSMCAL_SCH_COLS, NAN);
-    bool all_m1 = true;
-    for (int i = 0; i < rows; ++i) all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
-    if (all_m1) {                                               // nothing to read: the batch form's row for such a stream
+    if (pos_info_all_m1(pos_info, rows, ld)) {                  // nothing to read: the batch form's row for such a stream
         row[GSMCAL_C_NUM_SCH] = row[GSMCAL_C_NUM_OK] = row[GSMCAL_C_NUM_CONSISTENT] = 0.0;
         row[GSMCAL_C_BSIC] = row[GSMCAL_C_FN_ANCHOR] = row[GSMCAL_C_POS_ANCHOR] = -1.0;
         row[GSMCAL_C_STATUS] = GSMCAL_S_POST_NO_POS;
@@ -959,9 +959,7 @@ int gsmcal_SCH_decode(gsmcal_ctx* c, const double* s, long len, const double* po
     }
     if (!s || len < 1) return GSMCAL_E_ARG;
     if (rows > MAXROWS) return GSMCAL_E_CAPACITY;
-    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
-    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
-    RET_IF(gsmcal_sch_decode_batch(c, s, len, &len, pi.data(), 1, ov, sch_ts, len_ts, row.data(), soft, u));
+    RET_IF(gsmcal_sch_decode_batch(c, s, len, &len, pos_info_padded(pos_info, rows, ld).data(), 1, ov, sch_ts, len_ts, row.data(), soft, u));
     if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
     const int status = (int)row[GSMCAL_C_STATUS];
     if (status < 0) return status;
@@ -975,8 +973,7 @@ int gsmcal_SCH_decode(gsmcal_ctx* c, const double* s, long len, const double* po
 }
 
 // ---- BCCH_decode: the system information in the BCCH blocks ----------------------------------------------
-// k_bcch_decode (one workgroup per block slot and stream, one wave per burst) + k_bcch_decode_finish (one wave per stream) on the
-// context's stream, in bd_part; nothing of the lanes or of the chain's state is touched.
+// k_bcch_decode (one workgroup per block slot and stream, one wave per burst) + k_bcch_decode_finish (one wave per stream), in bd_part.
 static int bcch_decode_args(gsmcal_ctx* c, int ov, const int* tsc, int d) {
     if (ov != 2 && ov != 4 && ov != 8) { c->err = "BCCH_decode: oversampling ratios 2, 4 and 8 only"; return GSMCAL_E_UNSUPPORTED; }
     for (int i = 0; i < d; ++i)
@@ -986,10 +983,9 @@ static int bcch_decode_args(gsmcal_ctx* c, int ov, const int* tsc, int d) {
 
 int gsmcal_bcch_decode_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
                                  int ov, const int* tsc, double* d_out, unsigned char* d_octets, double* d_soft) {
-    if (!c || !d_r || !d_r_len || !d_pos_info || !tsc || !d_out || !d_octets || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    if (!post_args_ok(c, d_r, d_r_len, d_pos_info, d_out, d, stride) || !tsc || !d_octets) return GSMCAL_E_ARG;
     RET_IF(bcch_decode_args(c, ov, tsc, d));
-    ENTER(c);
-    c->cur = &c->lanes[0];                                      // the context's stream; the lane's buffers are not touched
+    ENTER_ON_CTX_STREAM(c);
     RET_IF(ensure(c, c->bd_part, (size_t)d * MAXH * BD_PART * sizeof(double)));
     RET_IF(upload_if_changed(c, c->bd_tsc, c->h_bd_tsc, tsc, (size_t)d, "BCCH_decode training sequence codes"));
     double* part = (double*)c->bd_part.p;
@@ -1006,18 +1002,15 @@ int gsmcal_bcch_decode_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, 
 
 int gsmcal_bcch_decode_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
                              const int* tsc, double* out, unsigned char* octets, double* soft) {
-    if (!c || !r || !r_len || !pos_info || !tsc || !out || !octets || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    if (!post_args_ok(c, r, r_len, pos_info, out, d, stride) || !tsc || !octets) return GSMCAL_E_ARG;
     RET_IF(bcch_decode_args(c, ov, tsc, d));
     ENTER(c);
-    const Stage io[] = {STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),
-                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
-                        STAGE(fd_pos, (size_t)d * 2 * MAXROWS * sizeof(double), pos_info, nullptr, 0),
+    const Stage io[] = {POST_STAGES_IN,
                         STAGE(bd_out, (size_t)d * GSMCAL_SI_COLS * sizeof(double), nullptr, out, 0),
                         STAGE(bd_oct, (size_t)d * MAXH * GSMCAL_BLOCK_OCTETS, nullptr, octets, 0),
                         STAGE(bd_soft, soft ? (size_t)d * MAXH * GSMCAL_BLOCK_CODED * sizeof(double) : 0, nullptr, soft, 0)};
     RET_IF(stage_up(c, io));
-    RET_IF(gsmcal_bcch_decode_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, (const double*)c->fd_pos.p, d,
-                                        ov, tsc, (double*)c->bd_out.p, (unsigned char*)c->bd_oct.p,
+    RET_IF(gsmcal_bcch_decode_batch_dev(c, POST_STAGED_IN, d, ov, tsc, (double*)c->bd_out.p, (unsigned char*)c->bd_oct.p,
                                         soft ? (double*)c->bd_soft.p : nullptr));
     return stage_down(c, io);
 }
@@ -1032,9 +1025,7 @@ int gsmcal_BCCH_decode(gsmcal_ctx* c, const double* s, long len, const double* p
     if (first) *first = si;
     c->report.clear();
     std::vector<double> row(GSMCAL_SI_COLS, NAN);
-    bool all_m1 = true;
-    for (int i = 0; i < rows; ++i) all_m1 = all_m1 && pos_info[i] == -1.0 && pos_info[ld + i] == -1.0;
-    if (all_m1) {                                               // nothing to read: the batch form's row for such a stream
+    if (pos_info_all_m1(pos_info, rows, ld)) {                  // nothing to read: the batch form's row for such a stream
         row[GSMCAL_I_NUM_BLOCKS] = row[GSMCAL_I_NUM_OK] = 0.0;
         row[GSMCAL_I_FIRST_OK] = -1.0;
         row[GSMCAL_I_STATUS] = GSMCAL_S_POST_NO_POS;
@@ -1045,9 +1036,7 @@ int gsmcal_BCCH_decode(gsmcal_ctx* c, const double* s, long len, const double* p
     }
     if (!s || len < 1) return GSMCAL_E_ARG;
     if (rows > MAXROWS) return GSMCAL_E_CAPACITY;
-    std::vector<double> pi((size_t)2 * MAXROWS, -1.0);          // the table as gsmcal_calibrate_batch hands it on: -1 padding
-    for (int i = 0; i < rows; ++i) { pi[i] = pos_info[i]; pi[MAXROWS + i] = pos_info[ld + i]; }
-    RET_IF(gsmcal_bcch_decode_batch(c, s, len, &len, pi.data(), 1, ov, &tsc, row.data(), octets, soft));
+    RET_IF(gsmcal_bcch_decode_batch(c, s, len, &len, pos_info_padded(pos_info, rows, ld).data(), 1, ov, &tsc, row.data(), octets, soft));
     if (table_row) memcpy(table_row, row.data(), row.size() * sizeof(double));
     const int status = (int)row[GSMCAL_I_STATUS];
     if (status < 0) return status;

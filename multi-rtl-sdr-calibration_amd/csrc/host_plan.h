@@ -1329,6 +1329,13 @@ int pipe_call(gsmcal_ctx* c, int d, F body) {
         HIPCHK(c, hipSetDevice((c)->device));      \
         RET_IF(pipe_join(c));                      \
     } while (0)
+// ... for a call that works on the context's stream alone (LAUNCH goes through c->cur, and lane 0 carries that stream): the
+// lane's buffers, the shared taps and the state of the calibrate / scan call before are not touched.
+#define ENTER_ON_CTX_STREAM(c)       \
+    do {                             \
+        ENTER(c);                    \
+        (c)->cur = &(c)->lanes[0];   \
+    } while (0)
 
 // Run `enqueue` (which only enqueues work on the context's streams) eagerly, or -- from the second identical
 // call on -- as a captured hipGraph replayed with one hipGraphLaunch.  The first call runs eagerly so that every

@@ -134,6 +134,132 @@ __global__ void __launch_bounds__(DM_THREADS) k_sch_equalise(const cplx* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// What the kernels below share: they all work on (r, r_len, pos_info) of D streams, pos_info[s] = [2][MAXROWS] with -1 padding
+// (DESIGN 11).
+//
+// pos_rows: one wave ranks the rows i of a stream's table for which pred(i, pi) holds, in table order.  Lane l evaluates rows
+// l, l + 64, ... (POS_NCH chunks); visit(c, is, rank) sees every chunk -- `is` and the 0-based `rank` of this lane's row, the
+// rank meaningful where `is` -- and the number of matching rows comes back, wave-uniform.  pos_row_pick turns (is, rank) into
+// the index of the b-th matching row by one ballot; pos_row_select does both and leaves -1 where there is no b-th row.
+// ------------------------------------------------------------------------------------------------
+constexpr int POS_NCH = (MAXROWS + 63) / 64;
+
+template <int T>
+struct PosType {                                 // pos_info(i, 2) == T: 0 FCCH, 1 SCH, 2 BCCH
+    __device__ bool operator()(int i, const double* pi) const { return pi[MAXROWS + i] == (double)T; }
+};
+struct PosBlock {                                // a BCCH block: type 1, and type 2 in the four rows behind it
+    __device__ bool operator()(int i, const double* pi) const {
+        bool isb = i + 4 < MAXROWS && pi[MAXROWS + i] == 1.0;
+        for (int q = 1; q <= 4; ++q) isb = isb && pi[MAXROWS + i + q] == 2.0;
+        return isb;
+    }
+};
+
+// the row lane `lane` evaluates in chunk c, or the last row where the chunk reaches past the table: every lane has a row to
+// load, so no load sits behind a branch and the loads of all chunks (and of several passes) go out together
+__device__ __forceinline__ int pos_row_clamped(int c, int lane) { return c * 64 + lane < MAXROWS ? c * 64 + lane : MAXROWS - 1; }
+
+template <class Pred, class Visit>
+__device__ __forceinline__ int pos_rows(const double* pi, int lane, Pred pred, Visit visit) {
+    int n = 0;
+    for (int c = 0; c < POS_NCH; ++c) {
+        const int i = c * 64 + lane;
+        const bool is = pred(pos_row_clamped(c, lane), pi) && i < MAXROWS;
+        const unsigned long long m = __ballot(is);
+        visit(c, is, n + __popcll(m & ((1ull << lane) - 1ull)));
+        n += __popcll(m);
+    }
+    return n;
+}
+template <class Pred>
+__device__ __forceinline__ int pos_rows_count(const double* pi, int lane, Pred pred) {
+    return pos_rows(pi, lane, pred, [](int, bool, int) {});
+}
+__device__ __forceinline__ void pos_row_pick(int c, bool is, int rank, int b, int& row) {
+    const unsigned long long sel = __ballot(is && rank == b);
+    if (sel) row = c * 64 + __ffsll((long long)sel) - 1;
+}
+template <class Pred>
+__device__ __forceinline__ int pos_row_select(const double* pi, int lane, int b, Pred pred, int& row) {
+    row = -1;
+    return pos_rows(pi, lane, pred, [&](int c, bool is, int rank) { pos_row_pick(c, is, rank, b, row); });
+}
+
+// The stream header.  len: the samples that can be read, min(r_len, stride) (r_len = -1: the reference returned r = -1; every
+// entry point refuses stride < 1, so len < 1 is r_len < 1).  has_pos: not every element of pos_info is -1 (`if pos_info == -1`),
+// formed by one wave.  status(): the two exits every *_finish kernel takes first, in this order; the first one reports no rows.
+struct StreamHead {
+    long len;
+    bool has_pos;
+    __device__ int status(int& count, int cap) const {
+        if (len < 1 || !has_pos) { count = 0; return GSMCAL_S_POST_NO_POS; }
+        return count > cap ? GSMCAL_E_CAPACITY : 0;
+    }
+};
+__device__ __forceinline__ long stream_len(const long* __restrict__ r_len, int s, long stride) {
+    return r_len[s] < stride ? r_len[s] : stride;
+}
+__device__ __forceinline__ StreamHead stream_head(const long* __restrict__ r_len, int s, long stride, const double* pi, int lane) {
+    const int n = pos_rows_count(pi, lane, [](int i, const double* p) {
+        const double pos = p[i], type = p[MAXROWS + i];            // both loads before the test: neither waits for the other
+        return pos != -1.0 || type != -1.0;
+    });
+    return StreamHead{stream_len(r_len, s, stride), n > 0};
+}
+
+// ------------------------------------------------------------------------------------------------
+// The burst detector of SCH_decode and BCCH_decode: what the two kernels have in common.
+//   vt_derotate   v (-j)^k: a swap and a negation.
+//   VtLane        the 16-state trellis of the rate-1/2 code G0 = 1 + D^3 + D^4, G1 = 1 + D + D^3 + D^4 (GSM 05.03 4.1.3): lane mod
+//                 16 = state u(k-1)<<3 | u(k-2)<<2 | u(k-3)<<1 | u(k-4); its two predecessors p0, p1 (older bit 0, older bit 1)
+//                 and the coded pair on either edge.  Start in state 0 (the others at -inf).
+//   acs           one add-compare-select step: two additions per candidate -- (+-s0) + (+-s1), then path metric + that: no
+//                 product, nothing contracts -- and a strict > that keeps the candidate whose older bit is 0.  pm becomes the
+//                 survivor's metric; the return value says that it came from p1.  Survivor storage is the caller's.
+//   vt_corrected  the hard channel bits that differ from the re-encoded word c(2k) = u(k)+u(k-3)+u(k-4), c(2k+1) = c(2k)+u(k-1),
+//                 counted by one wave from ballots; soft(j) and u(k) (0 for k < 0) are the caller's getters.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ cplx vt_derotate(cplx v, int k) {
+    const int q = k & 3;                                           // (-j)^k: 1, -j, -1, j
+    return q == 0 ? v : q == 1 ? make_double2(v.y, -v.x) : q == 2 ? make_double2(-v.x, -v.y) : make_double2(-v.y, v.x);
+}
+struct VtLane {
+    int bit, p0, p1;
+    bool a0, a1, b0, b1;                                           // c(2k), c(2k+1) coming from p0; ... from p1
+    double pm;
+    __device__ explicit VtLane(int lane) {
+        const int ns = lane & 15;
+        bit = ns >> 3; p0 = (ns & 7) << 1; p1 = p0 | 1;
+        a0 = (bit ^ (p0 >> 1) ^ p0) & 1; a1 = (a0 ^ (p0 >> 3)) & 1;
+        b0 = (bit ^ (p1 >> 1) ^ p1) & 1; b1 = (b0 ^ (p1 >> 3)) & 1;
+        pm = ns == 0 ? 0.0 : -__builtin_huge_val();
+    }
+    __device__ __forceinline__ bool acs(double s0, double s1) {
+        const double bm0 = (a0 ? -s0 : s0) + (a1 ? -s1 : s1);
+        const double bm1 = (b0 ? -s0 : s0) + (b1 ? -s1 : s1);
+        const double c0 = __shfl(pm, p0, 64) + bm0, c1 = __shfl(pm, p1, 64) + bm1;
+        const bool take = c1 > c0;                                 // strict: the first candidate stays
+        pm = take ? c1 : c0;
+        return take;
+    }
+};
+template <class Soft, class U>
+__device__ __forceinline__ int vt_corrected(int ncoded, int lane, Soft soft, U u) {
+    int corrected = 0;
+    for (int j0 = 0; j0 < ncoded; j0 += 64) {                      // (uniform)
+        const int j = j0 + lane, k = j >> 1;
+        bool differs = false;
+        if (j < ncoded) {
+            const unsigned c = u(k) ^ u(k - 3) ^ u(k - 4) ^ ((j & 1) ? u(k - 1) : 0u);
+            differs = (soft(j) < 0.0) != (c != 0u);
+        }
+        corrected += __popcll(__ballot(differs));
+    }
+    return corrected;
+}
+
+// ------------------------------------------------------------------------------------------------
 // FCCH_demod.m:5-66 -- the check behind the calibration: per FCCH burst of a corrected stream the tone frequency (:28-42, the
 // estimator of burst_tone_body on an array source), the bin of the spectrum's peak (:34,:66) and the in-band SNR of :51-63 (NOT
 // the gate of FCCH_fine_correction.m:185-189: other bins, another rule); per stream the mean frequency and the carrier error
@@ -143,42 +269,33 @@ __global__ void __launch_bounds__(DM_THREADS) k_sch_equalise(const cplx* __restr
 // of the stream's pos_info with type 0 (:18-19); a slot without a burst returns at once.  part[s][b] = {freq, snr, offset, status}.
 // LDS: xs[nfft] (the window; after the 37-point step P[nfft], the power spectrum in fftshift order) | B[37][N2+1] | w37 | wN2:
 // 39.2 KB at 8x, four workgroups per CU.  The window is read a second time from global memory for the phase step (the 37-point
-// step by symmetries consumes its LDS copy; a second copy would cost the third workgroup per CU).
+// step by symmetries consumes its LDS copy; a second copy would cost the third workgroup per CU).  Four workgroups per CU are
+// eight waves per SIMD: the launch bound says so, or the compiler spends registers (87 where 59 do) that leave room for two.
 // ------------------------------------------------------------------------------------------------
 #define FD_THREADS 512
 #define FD_PART 4       /* doubles per burst slot in the workspace */
 
 inline size_t fd_lds_bytes(int nfft) { return ((size_t)nfft + (size_t)37 * (nfft / 37 + 1) + 40 + nfft / 37) * sizeof(cplx); }
 
-__global__ void __launch_bounds__(FD_THREADS) k_fcch_demod(const cplx* __restrict__ r, long stride, const long* __restrict__ r_len,
+__global__ void __launch_bounds__(FD_THREADS, 8) k_fcch_demod(const cplx* __restrict__ r, long stride, const long* __restrict__ r_len,
                                                            const double* __restrict__ pos_info, int nfft, int ov, int hnl,
                                                            const cplx* __restrict__ tw_g, double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ unsigned char is_fcch[MAXROWS];
-    __shared__ double sh_sp;
-    __shared__ int sh_has;
     __shared__ double red_p[FD_THREADS / 64];
     __shared__ int red_t[FD_THREADS / 64];
     __shared__ double red[2 * (FD_THREADS / 64)];
     __shared__ int sh_key;
     const int s = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
-    const long len = r_len[s] < stride ? r_len[s] : stride;        // (r_len = -1: the reference returned r = -1)
+    const long len = stream_len(r_len, s, stride);
     if (len < 1) return;                                           // block-uniform
     const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
-    // ---- :18-19  fcch_pos = pos_info(pos_info(:,2)==0, 1): the b-th of them ----
-    if (tid == 0) sh_has = 0;
-    if (tid < MAXROWS) is_fcch[tid] = pi[MAXROWS + tid] == 0.0;
-    __syncthreads();
-    if (tid < MAXROWS && is_fcch[tid]) {
-        int rank = 0;
-        for (int i = 0; i < tid; ++i) rank += is_fcch[i];
-        if (rank == b) { sh_sp = pi[tid]; sh_has = 1; }
-    }
-    __syncthreads();
-    if (!sh_has) return;                                           // block-uniform
+    // ---- :18-19  fcch_pos = pos_info(pos_info(:,2)==0, 1): the b-th of them, found by every wave on its own ----
+    int row;
+    pos_row_select(pi, tid & 63, b, PosType<0>(), row);
+    if (row < 0) return;                                           // block-uniform
     double* out = part + ((size_t)s * MAXH + b) * FD_PART;
     // ---- :24-26  s(sp:ep): MATLAB stops with an index error outside the stream; decided before any sample is read ----
-    const double spd = sh_sp;
+    const double spd = pi[row];
     if (!(spd >= 1.0) || !(spd <= (double)len) || (long)spd - 1 + nfft > len) {
         if (tid == 0) { out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; out[3] = (double)GSMCAL_E_INDEX; }
         return;
@@ -240,7 +357,7 @@ __global__ void __launch_bounds__(FD_THREADS) k_fcch_demod(const cplx* __restric
                 sig += P[k];
             }
             const double noi = band - sig;                         // :61 (whether or not the five bins lie in the band)
-            out[1] = noi < 0.0 ? __longlong_as_double(0x7ff8000000000000LL) : 10.0 * log10(sig / noi);   // :62 (complex in MATLAB -> NaN)
+            out[1] = noi < 0.0 ? NAN_D : 10.0 * log10(sig / noi);   // :62 (complex in MATLAB -> NaN)
             out[2] = (double)jb;
             out[3] = 0.0;
         }
@@ -283,37 +400,27 @@ __global__ void __launch_bounds__(FD_THREADS) k_fcch_demod(const cplx* __restric
 //   more than MAXH type-0 rows                           status GSMCAL_E_CAPACITY, num_fcch = their number, the rest NaN
 //   a window outside the stream                          status GSMCAL_E_INDEX, num_fcch = the number of rows, the rest NaN
 //   no type-0 row                                        status 0, num_fcch 0, mean_freq = carrier_ppm = NaN (mean([]))
-__global__ void __launch_bounds__(64) k_fcch_demod_finish(const long* __restrict__ r_len, const double* __restrict__ pos_info,
+__global__ void __launch_bounds__(64) k_fcch_demod_finish(const long* __restrict__ r_len, long stride, const double* __restrict__ pos_info,
                                                           const double* __restrict__ carrier_freq, const double* __restrict__ part,
                                                           double* __restrict__ out) {
     const int s = blockIdx.x, lane = threadIdx.x;
     const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
     const double* ps = part + (size_t)s * MAXH * FD_PART;
     double* o = out + (size_t)s * GSMCAL_DEMOD_COLS;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    unsigned n0 = 0, not_m1 = 0;
-    for (int i = lane; i < MAXROWS; i += 64) {
-        const double p = pi[i], t = pi[MAXROWS + i];
-        n0 += t == 0.0;
-        not_m1 += (p != -1.0) || (t != -1.0);
-    }
-    n0 = wave_sum_u32(n0);
-    not_m1 = wave_sum_u32(not_m1);
-    int status = 0, nb = (int)n0;
-    if (r_len[s] < 1 || not_m1 == 0) { status = GSMCAL_S_POST_NO_POS; nb = 0; }
-    else if (nb > MAXH) status = GSMCAL_E_CAPACITY;
-    else
+    int nb = pos_rows_count(pi, lane, PosType<0>());
+    int status = stream_head(r_len, s, stride, pi, lane).status(nb, MAXH);
+    if (status == 0)
         for (int i = 0; i < nb; ++i)                               // (uniform loop, uniform loads)
             if (status == 0 && ps[i * FD_PART + 3] != 0.0) status = GSMCAL_E_INDEX;
     const bool ok = status == 0;
     for (int i = lane; i < MAXH; i += 64) {
         const bool use = ok && i < nb;
-        o[GSMCAL_D_FREQ + i] = use ? ps[i * FD_PART + 0] : nan;
-        o[GSMCAL_D_SNR + i] = use ? ps[i * FD_PART + 1] : nan;
-        o[GSMCAL_D_MAX_IDX + i] = use ? ps[i * FD_PART + 2] : nan;
+        o[GSMCAL_D_FREQ + i] = use ? ps[i * FD_PART + 0] : NAN_D;
+        o[GSMCAL_D_SNR + i] = use ? ps[i * FD_PART + 1] : NAN_D;
+        o[GSMCAL_D_MAX_IDX + i] = use ? ps[i * FD_PART + 2] : NAN_D;
     }
     if (lane == 0) {
-        double mean = nan, ppm = nan;
+        double mean = NAN_D, ppm = NAN_D;
         if (ok && nb > 0) {
             double acc = 0.0;
             for (int i = 0; i < nb; ++i) acc += ps[i * FD_PART + 0];                 // :44 mean(freq): left to right
@@ -334,8 +441,8 @@ __global__ void __launch_bounds__(64) k_fcch_demod_finish(const long* __restrict
 // The tone estimate is k_fcch_demod's (FCCH_demod.m:28-42 is the same block): these kernels read its workspace.
 //
 // k_bcch_corr: grid (BC_GRID_X, D), block BC_THREADS.  Workgroup (g, s) takes the type-2 rows g, g + BC_GRID_X, ... of stream
-// s's pos_info (the slot-to-row mapping of k_fcch_demod with type 2 in place of type 0; every wave ranks the rows itself from
-// three ballots, so a workgroup without a row returns before the first barrier).  Per row: the 26*ov window r(sp:ep), sp =
+// s's pos_info (every wave ranks them itself, so a workgroup without a row returns before the first barrier).  Per row: the
+// 26*ov window r(sp:ep), sp =
 // bcch_pos + 61*ov (:93-95), read once, rotated by exp(1i*n*comp_phase_rotate) at its absolute sample index n (:76) and kept in
 // LDS; wave w forms the conjugated dot products with templates 2w and 2w+1 (:97) -- fp64 FMAs, lane l takes samples l, l+64,
 // ..., then the wave sum, lane 0 writes: a fixed order, the same for every template.  corr[s][slot][8], flag[s][slot] = 0 or
@@ -349,7 +456,7 @@ __global__ void __launch_bounds__(64) k_fcch_demod_finish(const long* __restrict
 __device__ __forceinline__ double bc_mean_fo(const double* __restrict__ ps, int n0) {
     double acc = 0.0;
     for (int i = 0; i < n0; ++i) acc += ps[i * FD_PART];                         // :70 mean(fo): left to right
-    return n0 > 0 ? acc / (double)n0 : __longlong_as_double(0x7ff8000000000000LL);   // mean([]) = NaN
+    return n0 > 0 ? acc / (double)n0 : NAN_D;   // mean([]) = NaN
 }
 __device__ __forceinline__ double bc_comp_phase(double mean_fo, int ov) {
     return (GSM_SYMBOL_RATE / 4.0 - mean_fo) * 2.0 * PI_D / (GSM_SYMBOL_RATE * (double)ov);   // :74-75
@@ -362,40 +469,27 @@ __global__ void __launch_bounds__(BC_THREADS) k_bcch_corr(const cplx* __restrict
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     cplx* win = (cplx*)smem;
     const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long len = r_len[s] < stride ? r_len[s] : stride;
+    const long len = stream_len(r_len, s, stride);
     if (len < 1) return;                                           // block-uniform
     const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
-    // ---- :13, :49  the type-2 and the type-0 rows, ranked by every wave on its own ----
-    constexpr int NCH = (MAXROWS + 63) / 64;
-    bool is2[NCH];
-    int rank[NCH];
-    int nb = 0, n0 = 0;
-    for (int c = 0; c < NCH; ++c) {
-        const int i = c * 64 + lane;
-        const double t = i < MAXROWS ? pi[MAXROWS + i] : -1.0;
-        is2[c] = t == 2.0;
-        const unsigned long long m2 = __ballot(is2[c]), m0 = __ballot(t == 0.0);
-        rank[c] = nb + __popcll(m2 & ((1ull << lane) - 1ull));
-        nb += __popcll(m2);
-        n0 += __popcll(m0);
-    }
+    // ---- :13, :49  the type-2 and the type-0 rows, ranked by every wave on its own; (is2, rank) stay in registers for the slots ----
+    bool is2[POS_NCH];
+    int rank[POS_NCH];
+    int nb = pos_rows(pi, lane, PosType<2>(), [&](int c, bool is, int rk) { is2[c] = is; rank[c] = rk; });
+    const int n0 = pos_rows_count(pi, lane, PosType<0>());
     if (nb < 4 || n0 > MAXH) return;                               // :14 / more FCCH rows than the workspace holds: k_bcch_finish says which
     if (nb > BC_SLOTS) nb = BC_SLOTS;
     if ((int)blockIdx.x >= nb) return;                             // no row for this workgroup
     const double cpr = bc_comp_phase(bc_mean_fo(fd_part + (size_t)s * MAXH * FD_PART, n0), ov);
     const int lts = 26 * ov;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (int b = blockIdx.x; b < nb; b += BC_GRID_X) {             // (uniform)
         int row = 0;
-        for (int c = 0; c < NCH; ++c) {
-            const unsigned long long sel = __ballot(is2[c] && rank[c] == b);
-            if (sel) row = c * 64 + __ffsll((long long)sel) - 1;
-        }
+        for (int c = 0; c < POS_NCH; ++c) pos_row_pick(c, is2[c], rank[c], b, row);
         cplx* oc = corr + ((size_t)s * BC_SLOTS + b) * 8;
         int* of = flag + (size_t)s * BC_SLOTS + b;
         const double spd = pi[row] + (double)(61 * ov);            // :93
         if (!(spd >= 1.0) || !(spd <= (double)len) || (long)spd - 1 + lts > len) {   // :95 would stop with an index error
-            if (tid < 8) oc[tid] = make_double2(nan, nan);
+            if (tid < 8) oc[tid] = make_double2(NAN_D, NAN_D);
             if (tid == 0) *of = GSMCAL_E_INDEX;
             continue;
         }
@@ -447,35 +541,26 @@ __global__ void __launch_bounds__(64) k_bcch_finish(const long* __restrict__ r_l
     const cplx* cs = corr + (size_t)s * BC_SLOTS * 8;
     const int* fs = flag + (size_t)s * BC_SLOTS;
     double* o = out + (size_t)s * GSMCAL_BCCH_COLS;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    unsigned n0 = 0, n2 = 0, not_m1 = 0;
-    for (int i = lane; i < MAXROWS; i += 64) {
-        const double p = pi[i], t = pi[MAXROWS + i];
-        n0 += t == 0.0;
-        n2 += t == 2.0;
-        not_m1 += (p != -1.0) || (t != -1.0);
-    }
-    n0 = wave_sum_u32(n0);
-    n2 = wave_sum_u32(n2);
-    not_m1 = wave_sum_u32(not_m1);
-    const long len = r_len[s] < stride ? r_len[s] : stride;
-    int status = 0, nb = (int)n2;
-    if (len < 1 || not_m1 == 0) { status = GSMCAL_S_POST_NO_POS; nb = 0; }
-    else if (nb < 4) status = GSMCAL_S_POST_FEW_BCCH;              // the literal 4 of :14
-    else if (nb > BC_SLOTS || n0 > MAXH) status = GSMCAL_E_CAPACITY;
-    else {
-        for (unsigned i = 0; i < n0; ++i)                          // (uniform loops, uniform loads)
+    const int n0 = pos_rows_count(pi, lane, PosType<0>());
+    int nb = pos_rows_count(pi, lane, PosType<2>());
+    const StreamHead head = stream_head(r_len, s, stride, pi, lane);
+    const long len = head.len;
+    int status = head.status(nb, BC_SLOTS);
+    if (status != GSMCAL_S_POST_NO_POS && nb < 4) status = GSMCAL_S_POST_FEW_BCCH;     // the literal 4 of :14
+    else if (status == 0 && n0 > MAXH) status = GSMCAL_E_CAPACITY;
+    if (status == 0) {
+        for (int i = 0; i < n0; ++i)                               // (uniform loops, uniform loads)
             if (status == 0 && ps[i * FD_PART + 3] != 0.0) status = GSMCAL_E_INDEX;
         for (int i = 0; i < 4; ++i)
             if (status == 0 && fs[i] != 0) status = GSMCAL_E_INDEX;
     }
     const bool ok = status == 0;
-    double idx0 = nan, idx1 = nan, idx2 = nan, idx3 = nan;
+    double idx0 = NAN_D, idx1 = NAN_D, idx2 = NAN_D, idx3 = NAN_D;
     unsigned agree = 0;
     for (int b0 = 0; b0 < BC_SLOTS; b0 += 64) {                    // (uniform)
         const int b = b0 + lane;
         const bool use = ok && b < nb && b < BC_SLOTS && fs[b] == 0;
-        double best = -1.0, second = -1.0, ph = nan;
+        double best = -1.0, second = -1.0, ph = NAN_D;
         int bi = -1;
         if (use) {
             for (int k = 0; k < 8; ++k) {
@@ -485,13 +570,13 @@ __global__ void __launch_bounds__(64) k_bcch_finish(const long* __restrict__ r_l
             }
             if (bi >= 0) ph = atan2(cs[b * 8 + bi].y, cs[b * 8 + bi].x);
         }
-        const double idx = bi >= 0 ? (double)(bi + 1) : nan;
+        const double idx = bi >= 0 ? (double)(bi + 1) : NAN_D;
         if (b0 == 0) { idx0 = __shfl(idx, 0, 64); idx1 = __shfl(idx, 1, 64); idx2 = __shfl(idx, 2, 64); idx3 = __shfl(idx, 3, 64); }
         agree += idx == idx0;
         if (b < BC_SLOTS) {
             o[GSMCAL_B_IDX + b] = idx;
-            o[GSMCAL_B_PEAK + b] = bi >= 0 ? best : nan;
-            o[GSMCAL_B_RUNNER_UP + b] = bi >= 0 ? second : nan;
+            o[GSMCAL_B_PEAK + b] = bi >= 0 ? best : NAN_D;
+            o[GSMCAL_B_RUNNER_UP + b] = bi >= 0 ? second : NAN_D;
             o[GSMCAL_B_PHASE + b] = ph;
         }
     }
@@ -504,10 +589,10 @@ __global__ void __launch_bounds__(64) k_bcch_finish(const long* __restrict__ r_l
     if (corr_out)
         for (int i = lane; i < BC_SLOTS * 8; i += 64) {
             const int b = i >> 3;
-            corr_out[(size_t)s * BC_SLOTS * 8 + i] = ok && b < nb && fs[b] == 0 ? cs[i] : make_double2(nan, nan);
+            corr_out[(size_t)s * BC_SLOTS * 8 + i] = ok && b < nb && fs[b] == 0 ? cs[i] : make_double2(NAN_D, NAN_D);
         }
     if (lane == 0) {
-        double mean = nan, ppm = nan;
+        double mean = NAN_D, ppm = NAN_D;
         if (ok) {
             mean = bc_mean_fo(ps, (int)n0);                                      // :70
             ppm = 1e6 * (mean - GSM_SYMBOL_RATE / 4.0) / carrier_freq[s];        // :71
@@ -517,7 +602,7 @@ __global__ void __launch_bounds__(64) k_bcch_finish(const long* __restrict__ r_l
         o[GSMCAL_B_MEAN_FO] = mean;
         o[GSMCAL_B_CARRIER_PPM] = ppm;
         o[GSMCAL_B_STATUS] = (double)status;
-        o[GSMCAL_B_NUM_AGREE] = ok ? (double)agree : nan;
+        o[GSMCAL_B_NUM_AGREE] = ok ? (double)agree : NAN_D;
         if (r_len_out) r_len_out[s] = ok ? len : -1;
     }
 }
@@ -544,19 +629,17 @@ __global__ void __launch_bounds__(256) k_bcch_rotate(const cplx* __restrict__ r,
 // has no outputs and demodulates with Communications Toolbox code, so there is nothing to be in parity with; the definition is
 // DESIGN 16's and tests/sch_decode_ref.py restates it line by line.
 //
-// k_sch_decode: grid (MAXH, D), block 64 -- one wave per SCH burst slot.  The wave ranks the type-1 rows of its stream's pos_info
-// from ballots and takes the blockIdx.x-th (1-based start p).  delta = (5 ov - 1) div 2.
-//   1  y_k = s(p + k ov + delta) (-j)^k, k = 3..144: 142 strided reads, rotated by a swap and a negation, kept in LDS.  A burst
-//      whose reads leave the stream, or whose p is NaN or < 1, is not evaluated (decided before a sample is read).
+// k_sch_decode: grid (MAXH, D), block 64 -- one wave per SCH burst slot: the blockIdx.x-th type-1 row of its stream's pos_info
+// (1-based start p).  delta = (5 ov - 1) div 2.
+//   1  y_k = s(p + k ov + delta) (-j)^k, k = 3..144: 142 strided reads, kept in LDS.  A burst whose reads leave the stream, or
+//      whose p is NaN or < 1, is not evaluated (decided before a sample is read).
 //   2  lane i holds y_{42+i} a_i, a_i = 1 - 2 SCH_TRAINING_BITS[i]; five xor-shuffle steps inside each half of the wave leave h1
 //      in lanes 0..31 and h2 in lanes 32..63: one fixed order.  h = h1 + h2, slope = angle(h2 conj(h1)) / 32, amp = |h| / 64.
 //   3  soft_k = Re(y_k conj(h)/|h| exp(-j slope (k - 73.5))) for k = 3..144, in LDS.
-//   4  the 16-state Viterbi decoder over soft[3..41], soft[106..144]: lane (state) = u(k-1)<<3 | u(k-2)<<2 | u(k-3)<<1 | u(k-4)
-//      (every group of 16 lanes runs the same trellis); per step two additions per candidate -- (+-soft[2k]) + (+-soft[2k+1]),
-//      then path metric + that: no product, nothing contracts -- a strict > that keeps the candidate whose older bit is 0, and
-//      the survivor's 39-bit history in one 64-bit register, taken from the predecessor lane by __shfl (register exchange: no
-//      traceback memory, no atomics).  Start in state 0 (the others at -inf), the answer is state 0's history.
-//   5  ts_err and corrected from two ballots; CRC, tail bits and the fields on lane 0 (SD_INFO_MAP is the bit map, the one
+//   4  the trellis (VtLane) over soft[3..41], soft[106..144]; every group of 16 lanes runs the same one.  The survivor's 39-bit
+//      history is one 64-bit register, taken from the predecessor lane by __shfl (register exchange: no traceback memory, no
+//      atomics); the answer is state 0's history.
+//   5  ts_err from a ballot, corrected by vt_corrected; CRC, tail bits and the fields on lane 0 (SD_INFO_MAP is the bit map, the one
 //      table to pin against a capture).
 // part[s][slot][SD_PART] = {evaluated, ok, bsic, fn, ts_err, corrected, slope, amp}; every block writes its record.  Optional:
 // soft_out[s][slot][148] (NaN outside 3..144 and for a slot that was not evaluated), u_out[s][slot][39] bytes (255 likewise).
@@ -586,39 +669,25 @@ __global__ void __launch_bounds__(64) k_sch_decode(const cplx* __restrict__ r, l
     __shared__ cplx ys[148];
     __shared__ double soft[148];
     const int s = blockIdx.y, b = blockIdx.x, lane = threadIdx.x;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
     double* out = part + ((size_t)s * MAXH + b) * SD_PART;
-    const long len = r_len[s] < stride ? r_len[s] : stride;
+    const long len = stream_len(r_len, s, stride);
     const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
-    // ---- the b-th type-1 row ----
-    constexpr int NCH = (MAXROWS + 63) / 64;
-    int n1 = 0, row = -1;
-    for (int c = 0; c < NCH; ++c) {
-        const int i = c * 64 + lane;
-        const bool is1 = i < MAXROWS && pi[MAXROWS + i] == 1.0;
-        const unsigned long long m = __ballot(is1);
-        const unsigned long long sel = __ballot(is1 && n1 + __popcll(m & ((1ull << lane) - 1ull)) == b);
-        if (sel) row = c * 64 + __ffsll((long long)sel) - 1;
-        n1 += __popcll(m);
-    }
+    int row;                                                       // the b-th type-1 row
+    const int n1 = pos_row_select(pi, lane, b, PosType<1>(), row);
     const int dl = (5 * ov - 1) / 2;
     const double spd = row >= 0 ? pi[row] : 0.0;
     // p NaN or < 1, or symbol 144 behind the last sample: not evaluated (wave-uniform)
     if (len < 1 || row < 0 || n1 > MAXH || !(spd >= 1.0) || !(spd + (double)(144 * ov + dl) <= (double)len)) {
         if (lane == 0) out[0] = 0.0;
-        else if (lane < SD_PART) out[lane] = nan;
+        else if (lane < SD_PART) out[lane] = NAN_D;
         if (soft_out)
-            for (int k = lane; k < 148; k += 64) soft_out[((size_t)s * MAXH + b) * 148 + k] = nan;
+            for (int k = lane; k < 148; k += 64) soft_out[((size_t)s * MAXH + b) * 148 + k] = NAN_D;
         if (u_out && lane < 39) u_out[((size_t)s * MAXH + b) * 39 + lane] = 255;
         return;
     }
     // ---- 1  the 142 symbols, derotated ----
     const cplx* x = r + (size_t)s * stride + ((long)spd - 1 + dl);
-    for (int k = 3 + lane; k <= 144; k += 64) {
-        const cplx v = x[(long)k * ov];
-        const int q = k & 3;                                       // (-j)^k: 1, -j, -1, j
-        ys[k] = q == 0 ? v : q == 1 ? make_double2(v.y, -v.x) : q == 2 ? make_double2(-v.x, -v.y) : make_double2(-v.y, v.x);
-    }
+    for (int k = 3 + lane; k <= 144; k += 64) ys[k] = vt_derotate(x[(long)k * ov], k);
     __syncthreads();
     // ---- 2  the two half-sums over the training sequence ----
     const bool tbit = (SD_TRAINING_MASK >> lane) & 1ull;
@@ -641,37 +710,20 @@ __global__ void __launch_bounds__(64) k_sch_decode(const cplx* __restrict__ r, l
         soft[k] = ys[k].x * q.x - ys[k].y * q.y;
     }
     __syncthreads();
-    // ---- 4  the trellis: this lane's state and its two predecessors (older bit 0, older bit 1) ----
-    const int ns = lane & 15, bit = ns >> 3, p0 = (ns & 7) << 1, p1 = p0 | 1;
-    const bool a0 = (bit ^ (p0 >> 1) ^ p0) & 1, a1 = (a0 ^ (p0 >> 3)) & 1;      // c(2k), c(2k+1) coming from p0
-    const bool b0 = (bit ^ (p1 >> 1) ^ p1) & 1, b1 = (b0 ^ (p1 >> 3)) & 1;      // ... from p1
-    double pm = ns == 0 ? 0.0 : -__builtin_huge_val();
+    // ---- 4  the trellis; the survivor's history travels with the metric ----
+    VtLane vt(lane);
     unsigned long long hist = 0;
     for (int k = 0; k < 39; ++k) {
-        const double s0 = soft[sd_soft_index(2 * k)], s1 = soft[sd_soft_index(2 * k + 1)];
-        const double bm0 = (a0 ? -s0 : s0) + (a1 ? -s1 : s1);
-        const double bm1 = (b0 ? -s0 : s0) + (b1 ? -s1 : s1);
-        const double c0 = __shfl(pm, p0, 64) + bm0, c1 = __shfl(pm, p1, 64) + bm1;
-        const unsigned long long g0 = sd_shfl_u64(hist, p0), g1 = sd_shfl_u64(hist, p1);
-        const bool take = c1 > c0;                                 // strict: the first candidate stays
-        pm = take ? c1 : c0;
-        hist = (take ? g1 : g0) | ((unsigned long long)bit << k);
+        const unsigned long long g0 = sd_shfl_u64(hist, vt.p0), g1 = sd_shfl_u64(hist, vt.p1);
+        const bool take = vt.acs(soft[sd_soft_index(2 * k)], soft[sd_soft_index(2 * k + 1)]);
+        hist = (take ? g1 : g0) | ((unsigned long long)vt.bit << k);
     }
     const unsigned long long u = sd_shfl_u64(hist, 0);             // end in state 0: u(k) = bit k
     // ---- 5  hard errors in the training bits; hard channel bits against the re-encoded word ----
     const int ts_err = __popcll(__ballot((soft[42 + lane] < 0.0) != tbit));
-    int corrected = 0;
-    for (int j0 = 0; j0 < 78; j0 += 64) {                          // (uniform)
-        const int j = j0 + lane, k = j >> 1;
-        bool differs = false;
-        if (j < 78) {
-            const unsigned c = sd_u(u, k) ^ sd_u(u, k - 3) ^ sd_u(u, k - 4) ^ ((j & 1) ? sd_u(u, k - 1) : 0u);
-            differs = (soft[sd_soft_index(j)] < 0.0) != (c != 0u);
-        }
-        corrected += __popcll(__ballot(differs));
-    }
+    const int corrected = vt_corrected(78, lane, [&](int j) { return soft[sd_soft_index(j)]; }, [&](int k) { return sd_u(u, k); });
     if (soft_out)
-        for (int k = lane; k < 148; k += 64) soft_out[((size_t)s * MAXH + b) * 148 + k] = k >= 3 && k <= 144 ? soft[k] : nan;
+        for (int k = lane; k < 148; k += 64) soft_out[((size_t)s * MAXH + b) * 148 + k] = k >= 3 && k <= 144 ? soft[k] : NAN_D;
     if (u_out && lane < 39) u_out[((size_t)s * MAXH + b) * 39 + lane] = (unsigned char)sd_u(u, lane);
     if (lane == 0) {
         unsigned reg = 0;                                          // u(0..34) divided by g(D): the remainder must be all ones
@@ -686,8 +738,8 @@ __global__ void __launch_bounds__(64) k_sch_decode(const cplx* __restrict__ r, l
         const bool ok = reg == 0x3ffu && (u >> 35) == 0ull && f[SD_T3P] <= 4 && f[SD_T2] <= 25;
         out[0] = 1.0;
         out[1] = ok ? 1.0 : 0.0;
-        out[2] = ok ? (double)f[SD_BSIC] : nan;
-        out[3] = ok ? (double)fn : nan;
+        out[2] = ok ? (double)f[SD_BSIC] : NAN_D;
+        out[3] = ok ? (double)fn : NAN_D;
         out[4] = (double)ts_err;
         out[5] = (double)corrected;
         out[6] = slope;
@@ -710,31 +762,19 @@ __global__ void __launch_bounds__(64) k_sch_finish(const long* __restrict__ r_le
     const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
     const double* ps = part + (size_t)s * MAXH * SD_PART;
     double* o = out + (size_t)s * GSMCAL_SCH_COLS;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    constexpr int NCH = (MAXROWS + 63) / 64;
-    int n1 = 0;
-    unsigned not_m1 = 0;
-    for (int c = 0; c < NCH; ++c) {
-        const int i = c * 64 + lane;
-        const double p = i < MAXROWS ? pi[i] : -1.0, t = i < MAXROWS ? pi[MAXROWS + i] : -1.0;
-        not_m1 += (p != -1.0) || (t != -1.0);
-        const unsigned long long m = __ballot(t == 1.0);
-        const int rank = n1 + __popcll(m & ((1ull << lane) - 1ull));
-        if (t == 1.0 && rank < MAXH) pos[rank] = p;
-        n1 += __popcll(m);
-    }
-    not_m1 = wave_sum_u32(not_m1);
+    const StreamHead head = stream_head(r_len, s, stride, pi, lane);      // (first: its loads are the ones the ranking needs)
+    int nb = pos_rows(pi, lane, PosType<1>(), [&](int c, bool is, int rank) {
+        const double p = pi[pos_row_clamped(c, lane)];
+        if (is && rank < MAXH) pos[rank] = p;
+    });
     __syncthreads();
-    const long len = r_len[s] < stride ? r_len[s] : stride;
-    int status = 0, nb = n1;
-    if (len < 1 || not_m1 == 0) { status = GSMCAL_S_POST_NO_POS; nb = 0; }
-    else if (nb > MAXH) status = GSMCAL_E_CAPACITY;
+    int status = head.status(nb, MAXH);
     const bool mine = status == 0 && lane < nb;
     const bool ev = mine && ps[lane * SD_PART] == 1.0;
     const bool ok = ev && ps[lane * SD_PART + 1] == 1.0;
-    const double bsic = ok ? ps[lane * SD_PART + 2] : nan, fnd = ok ? ps[lane * SD_PART + 3] : nan;
+    const double bsic = ok ? ps[lane * SD_PART + 2] : NAN_D, fnd = ok ? ps[lane * SD_PART + 3] : NAN_D;
     const long fn = ok ? (long)fnd : 0;
-    const double p = mine ? pos[lane] : 0.0, slope = ev ? ps[lane * SD_PART + 6] : nan;
+    const double p = mine ? pos[lane] : 0.0, slope = ev ? ps[lane * SD_PART + 6] : NAN_D;
     const double frame = 1250.0 * (double)ov;
     int cnt = 0, num_ok = 0;
     double acc = 0.0;
@@ -756,13 +796,13 @@ __global__ void __launch_bounds__(64) k_sch_finish(const long* __restrict__ r_le
     }
     if (status == 0 && best < 2) status = GSMCAL_S_SCH_NO_DECODE;
     if (lane < MAXH) {
-        o[GSMCAL_C_OK + lane] = ev ? (ok ? 1.0 : 0.0) : nan;
+        o[GSMCAL_C_OK + lane] = ev ? (ok ? 1.0 : 0.0) : NAN_D;
         o[GSMCAL_C_BSIC_B + lane] = bsic;
         o[GSMCAL_C_FN + lane] = fnd;
-        o[GSMCAL_C_TS_ERR + lane] = ev ? ps[lane * SD_PART + 4] : nan;
-        o[GSMCAL_C_CORRECTED + lane] = ev ? ps[lane * SD_PART + 5] : nan;
+        o[GSMCAL_C_TS_ERR + lane] = ev ? ps[lane * SD_PART + 4] : NAN_D;
+        o[GSMCAL_C_CORRECTED + lane] = ev ? ps[lane * SD_PART + 5] : NAN_D;
         o[GSMCAL_C_SLOPE + lane] = slope;
-        o[GSMCAL_C_AMP + lane] = ev ? ps[lane * SD_PART + 7] : nan;
+        o[GSMCAL_C_AMP + lane] = ev ? ps[lane * SD_PART + 7] : NAN_D;
     }
     const int an = anchor < 0 ? 0 : anchor;
     const double a_bsic = __shfl(bsic, an, 64), a_fn = __shfl(fnd, an, 64), a_pos = __shfl(p, an, 64);
@@ -775,7 +815,7 @@ __global__ void __launch_bounds__(64) k_sch_finish(const long* __restrict__ r_le
         o[GSMCAL_C_FN_ANCHOR] = good ? a_fn : -1.0;
         o[GSMCAL_C_POS_ANCHOR] = good ? a_pos : -1.0;
         o[GSMCAL_C_STATUS] = (double)status;
-        o[GSMCAL_C_MEAN_SLOPE] = num_ok > 0 ? acc / (double)num_ok : nan;
+        o[GSMCAL_C_MEAN_SLOPE] = num_ok > 0 ? acc / (double)num_ok : NAN_D;
     }
 }
 
@@ -783,14 +823,12 @@ __global__ void __launch_bounds__(64) k_sch_finish(const long* __restrict__ r_le
 // BCCH_decode -- the system information in the BCCH blocks: which cell this is.  The project's own function:
 // BCCH_demod.m stops at the training sequence index; the definition is DESIGN 17's and tests/bcch_decode_ref.py restates it.
 //
-// k_bcch_decode: grid (MAXH, D), block 256 -- one workgroup per block slot, wave w takes burst w of the block.  Every wave ranks
-// the block rows of its stream's pos_info from ballots (a type-1 row that four type-2 rows follow directly) and takes the
-// blockIdx.x-th; its bursts start at rows +1..+4 (1-based starts p).  delta = (5 ov - 1) div 2.  A block that is absent, or of which
-// one burst would read outside the stream or has p NaN or < 1, writes its empty record and returns before the barrier (the
-// decision is the same in all four waves).
-//   1  y_k = s(p + k ov + delta) (-j)^k, k = 3..144: 142 strided reads, rotated by a swap and a negation.  Lane l keeps k = 3 + l,
-//      67 + l and (l < 14) 131 + l in registers: nothing of the detector goes through LDS, so no wave waits for another one's
-//      stores before the one barrier.
+// k_bcch_decode: grid (MAXH, D), block 256 -- one workgroup per block slot, wave w takes burst w of the block.  Every wave finds
+// the blockIdx.x-th block row (PosBlock) of its stream's pos_info itself; its bursts start at rows +1..+4 (1-based starts p).
+// delta = (5 ov - 1) div 2.  A block that is absent, or of which one burst would read outside the stream or has p NaN or < 1,
+// writes its empty record and returns before the barrier (the decision is the same in all four waves).
+//   1  y_k = s(p + k ov + delta) (-j)^k, k = 3..144: 142 strided reads.  Lane l keeps k = 3 + l, 67 + l and (l < 14) 131 + l in
+//      registers: nothing of the detector goes through LDS, so no wave waits for another one's stores before the one barrier.
 //   2  pass 0: every lane adds its own mid-amble symbols y_{61+i} a_i (a_i = 1 - 2 TSC[tsc][i], bits of BD_TSC_MASK), six
 //      xor-shuffle steps leave h in every lane: one fixed order.  amp = |h| / 26, soft_k = Re(y_k conj(h)/|h|).
 //   3  two refinements: b_k = sign(soft_k) (+1 at zero), a_{k-61} inside the mid-amble; g1 (k <= 73), g2 (k >= 74) by the same
@@ -799,11 +837,10 @@ __global__ void __launch_bounds__(64) k_sch_finish(const long* __restrict__ r_le
 //   4  each wave stores its 114 data values at their places c(0..455) of the coded word in LDS (bd_coded_index: the inverse of
 //      the interleaver, the one table to pin), counts its mid-amble errors and the two stealing flags from ballots, and leaves
 //      {ts_err, steal, slope, amp} in LDS.  ONE barrier; waves 1..3 are done.
-//   5  wave 0: the 16-state trellis of k_sch_decode over 228 steps (lane mod 16 = state, metrics by __shfl, the same two additions
-//      per candidate and the same strict >).  The survivor no longer fits a register: the low 16 bits of __ballot(take) are the
-//      step's decision word, stored by lane 0 (456 bytes of LDS), and lane 0 traces back from state 0 into four 64-bit registers
-//      that one __shfl hands to the wave.  No atomics, no global traceback memory, no scratch.
-//   6  integer work: corrected from eight ballots against the re-encoded word, the Fire remainder of u(0..223) (a 40-bit shift
+//   5  wave 0: the trellis (VtLane) over 228 steps.  The survivor no longer fits a register: the low 16 bits of __ballot(take)
+//      are the step's decision word, stored by lane 0 (456 bytes of LDS), and lane 0 traces back from state 0 into four 64-bit
+//      registers that one __shfl hands to the wave.  No atomics, no global traceback memory, no scratch.
+//   6  integer work: corrected by vt_corrected, the Fire remainder of u(0..223) (a 40-bit shift
 //      register), the tail bits, and lanes 0..22 pack one octet each (bit k of octet n = u(8n + k)).
 // part[s][slot][BD_PART] = {evaluated, ok, corrected, ts_err, steal, mean_slope, amp, pos}; oct_out[s][slot][23]: zeros unless ok;
 // optional soft_out[s][slot][456]: the de-interleaved soft values, NaN for a slot that was not evaluated.  Every workgroup writes
@@ -835,23 +872,12 @@ __global__ void __launch_bounds__(256) k_bcch_decode(const cplx* __restrict__ r,
     __shared__ double bstat[4][4];
     __shared__ unsigned short dec[228];
     const int s = blockIdx.y, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
     const size_t slot = (size_t)s * MAXH + b;
     double* out = part + slot * BD_PART;
-    const long len = r_len[s] < stride ? r_len[s] : stride;
+    const long len = stream_len(r_len, s, stride);
     const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
-    // ---- the b-th block row: type 1, and type 2 in the four rows behind it ----
-    constexpr int NCH = (MAXROWS + 63) / 64;
-    int nb = 0, row = -1;
-    for (int c = 0; c < NCH; ++c) {
-        const int i = c * 64 + lane;
-        bool isb = i + 4 < MAXROWS && pi[MAXROWS + i] == 1.0;
-        for (int q = 1; q <= 4; ++q) isb = isb && pi[MAXROWS + i + q] == 2.0;
-        const unsigned long long m = __ballot(isb);
-        const unsigned long long sel = __ballot(isb && nb + __popcll(m & ((1ull << lane) - 1ull)) == b);
-        if (sel) row = c * 64 + __ffsll((long long)sel) - 1;
-        nb += __popcll(m);
-    }
+    int row;                                                           // the b-th block row
+    const int nb = pos_row_select(pi, lane, b, PosBlock(), row);
     const int dl = (5 * ov - 1) / 2;
     // any of the four p NaN or < 1, or its symbol 144 behind the last sample: the block is not evaluated (uniform in the workgroup)
     bool evaluated = len >= 1 && row >= 0 && nb <= MAXH;
@@ -862,10 +888,10 @@ __global__ void __launch_bounds__(256) k_bcch_decode(const cplx* __restrict__ r,
         }
     if (!evaluated) {
         if (tid == 0) out[0] = 0.0;
-        else if (tid < BD_PART) out[tid] = nan;
+        else if (tid < BD_PART) out[tid] = NAN_D;
         if (tid < 23) oct_out[slot * 23 + tid] = 0;
         if (soft_out)
-            for (int k = tid; k < 456; k += 256) soft_out[slot * 456 + k] = nan;
+            for (int k = tid; k < 456; k += 256) soft_out[slot * 456 + k] = NAN_D;
         return;
     }
     // ---- 1  this wave's burst: 142 symbols, derotated, three per lane ----
@@ -880,9 +906,7 @@ __global__ void __launch_bounds__(256) k_bcch_decode(const cplx* __restrict__ r,
         y[m] = make_double2(0.0, 0.0);
         a[m] = 0.0;
         if (k <= 144) {
-            const cplx v = x[(long)k * ov];
-            const int q = k & 3;                                       // (-j)^k: 1, -j, -1, j
-            y[m] = q == 0 ? v : q == 1 ? make_double2(v.y, -v.x) : q == 2 ? make_double2(-v.x, -v.y) : make_double2(-v.y, v.x);
+            y[m] = vt_derotate(x[(long)k * ov], k);
             if (k >= 61 && k <= 86) a[m] = (mask >> (k - 61)) & 1u ? -1.0 : 1.0;
         }
     }
@@ -951,19 +975,10 @@ __global__ void __launch_bounds__(256) k_bcch_decode(const cplx* __restrict__ r,
     }
     __syncthreads();
     if (w != 0) return;
-    // ---- 5  the trellis: this lane's state and its two predecessors (older bit 0, older bit 1) ----
-    const int ns = lane & 15, bit = ns >> 3, p0 = (ns & 7) << 1, p1 = p0 | 1;
-    const bool a0 = (bit ^ (p0 >> 1) ^ p0) & 1, a1 = (a0 ^ (p0 >> 3)) & 1;      // c(2k), c(2k+1) coming from p0
-    const bool b0 = (bit ^ (p1 >> 1) ^ p1) & 1, b1 = (b0 ^ (p1 >> 3)) & 1;      // ... from p1
-    double pm = ns == 0 ? 0.0 : -__builtin_huge_val();
+    // ---- 5  the trellis; the decisions of a step are one word in LDS ----
+    VtLane vt(lane);
     for (int k = 0; k < 228; ++k) {
-        const double s0 = cs[2 * k], s1 = cs[2 * k + 1];
-        const double bm0 = (a0 ? -s0 : s0) + (a1 ? -s1 : s1);
-        const double bm1 = (b0 ? -s0 : s0) + (b1 ? -s1 : s1);
-        const double c0 = __shfl(pm, p0, 64) + bm0, c1 = __shfl(pm, p1, 64) + bm1;
-        const bool take = c1 > c0;                                     // strict: the first candidate stays
-        pm = take ? c1 : c0;
-        const unsigned long long word = __ballot(take);
+        const unsigned long long word = __ballot(vt.acs(cs[2 * k], cs[2 * k + 1]));
         if (lane == 0) dec[k] = (unsigned short)word;                  // bit ns: state ns came from its predecessor p1
     }
     unsigned long long u0 = 0, u1 = 0, u2 = 0, u3 = 0;                // u(k) = bit k & 63 of word k >> 6
@@ -979,17 +994,7 @@ __global__ void __launch_bounds__(256) k_bcch_decode(const cplx* __restrict__ r,
     u2 = sd_shfl_u64(u2, 0);
     u3 = sd_shfl_u64(u3, 0);
     // ---- 6  hard channel bits against the re-encoded word; the Fire code; the octets ----
-    int corrected = 0;
-    for (int j0 = 0; j0 < 456; j0 += 64) {                             // (uniform)
-        const int j = j0 + lane, k = j >> 1;
-        bool differs = false;
-        if (j < 456) {
-            const unsigned c = bd_u(u0, u1, u2, u3, k) ^ bd_u(u0, u1, u2, u3, k - 3) ^ bd_u(u0, u1, u2, u3, k - 4) ^
-                               ((j & 1) ? bd_u(u0, u1, u2, u3, k - 1) : 0u);
-            differs = (cs[j] < 0.0) != (c != 0u);
-        }
-        corrected += __popcll(__ballot(differs));
-    }
+    const int corrected = vt_corrected(456, lane, [&](int j) { return cs[j]; }, [&](int k) { return bd_u(u0, u1, u2, u3, k); });
     unsigned long long reg = 0;                                        // u(0..223) divided by g(D): the remainder must be all ones
     for (int k = 0; k < 224; ++k) {
         reg = (reg << 1) | bd_u(u0, u1, u2, u3, k);
@@ -1026,36 +1031,21 @@ __global__ void __launch_bounds__(64) k_bcch_decode_finish(const long* __restric
     const double* pi = pos_info + (size_t)s * 2 * MAXROWS;
     const double* ps = part + (size_t)s * MAXH * BD_PART;
     double* o = out + (size_t)s * GSMCAL_SI_COLS;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    constexpr int NCH = (MAXROWS + 63) / 64;
-    int nb = 0;
-    unsigned not_m1 = 0;
-    for (int c = 0; c < NCH; ++c) {
-        const int i = c * 64 + lane;
-        const double p = i < MAXROWS ? pi[i] : -1.0, t = i < MAXROWS ? pi[MAXROWS + i] : -1.0;
-        not_m1 += (p != -1.0) || (t != -1.0);
-        bool isb = i + 4 < MAXROWS && t == 1.0;
-        for (int q = 1; q <= 4; ++q) isb = isb && pi[MAXROWS + i + q] == 2.0;
-        nb += __popcll(__ballot(isb));
-    }
-    not_m1 = wave_sum_u32(not_m1);
-    const long len = r_len[s] < stride ? r_len[s] : stride;
-    int status = 0;
-    if (len < 1 || not_m1 == 0) { status = GSMCAL_S_POST_NO_POS; nb = 0; }
-    else if (nb > MAXH) status = GSMCAL_E_CAPACITY;
+    int nb = pos_rows_count(pi, lane, PosBlock());
+    int status = stream_head(r_len, s, stride, pi, lane).status(nb, MAXH);
     const bool mine = status == 0 && lane < nb;
     const bool ev = mine && ps[lane * BD_PART] == 1.0;
     const bool ok = ev && ps[lane * BD_PART + 1] == 1.0;
     const unsigned long long okm = __ballot(ok);
     if (status == 0 && okm == 0ull) status = GSMCAL_S_BCCH_NO_DECODE;
     if (lane < MAXH) {
-        o[GSMCAL_I_OK + lane] = ev ? (ok ? 1.0 : 0.0) : nan;
-        o[GSMCAL_I_POS + lane] = ev ? ps[lane * BD_PART + 7] : nan;
-        o[GSMCAL_I_CORRECTED + lane] = ev ? ps[lane * BD_PART + 2] : nan;
-        o[GSMCAL_I_TS_ERR + lane] = ev ? ps[lane * BD_PART + 3] : nan;
-        o[GSMCAL_I_STEAL + lane] = ev ? ps[lane * BD_PART + 4] : nan;
-        o[GSMCAL_I_MEAN_SLOPE + lane] = ev ? ps[lane * BD_PART + 5] : nan;
-        o[GSMCAL_I_AMP + lane] = ev ? ps[lane * BD_PART + 6] : nan;
+        o[GSMCAL_I_OK + lane] = ev ? (ok ? 1.0 : 0.0) : NAN_D;
+        o[GSMCAL_I_POS + lane] = ev ? ps[lane * BD_PART + 7] : NAN_D;
+        o[GSMCAL_I_CORRECTED + lane] = ev ? ps[lane * BD_PART + 2] : NAN_D;
+        o[GSMCAL_I_TS_ERR + lane] = ev ? ps[lane * BD_PART + 3] : NAN_D;
+        o[GSMCAL_I_STEAL + lane] = ev ? ps[lane * BD_PART + 4] : NAN_D;
+        o[GSMCAL_I_MEAN_SLOPE + lane] = ev ? ps[lane * BD_PART + 5] : NAN_D;
+        o[GSMCAL_I_AMP + lane] = ev ? ps[lane * BD_PART + 6] : NAN_D;
     }
     if (lane == 0) {
         o[GSMCAL_I_NUM_BLOCKS] = (double)nb;

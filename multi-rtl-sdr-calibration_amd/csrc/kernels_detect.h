@@ -67,7 +67,7 @@ __device__ __forceinline__ double snr_from_power(const double (&P)[L], double fl
 #pragma unroll
     for (int k = 0; k < L; ++k) tot += P[k];
     const double noise = tot - sig;
-    if (tot <= floor2) return __longlong_as_double(0x7ff8000000000000LL);
+    if (tot <= floor2) return NAN_D;
     return 10.0 * log10(sig / noise);
 }
 
@@ -1049,7 +1049,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                                         for (int k = 0; k < 16; ++k) tot += P[k];
                                         c_sig = sig; c_noise = tot - sig;
                                         v = 10.0 * log10(c_sig / c_noise);
-                                        if (tot <= s.floor2) v = __longlong_as_double(0x7ff8000000000000LL);   // rounding residue of the DC removal: 0/0 in the reference (snr_from_power)
+                                        if (tot <= s.floor2) v = NAN_D;   // rounding residue of the DC removal: 0/0 in the reference (snr_from_power)
                                     } else {                             // (the tree total differs from the sequential one by ~1e-16: inside eps)
                                         double t8[8];
 #pragma unroll

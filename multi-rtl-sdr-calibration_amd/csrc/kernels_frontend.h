@@ -14,6 +14,7 @@
 #include "state.h"
 
 typedef double2 cplx;
+#define NAN_D __longlong_as_double(0x7ff8000000000000LL)   /* MATLAB's NaN: quiet, sign clear, payload 0 */
 
 // sin/cos of a LARGE fp64 argument t (|t| up to ~1e6 rad: t = k*comp_phase_rotate, k up to 1e6) with the
 // accuracy of a correctly reduced argument, several times cheaper than the library's general path:
