@@ -224,6 +224,10 @@ long gsmcal_coarse_scan_lds_fixed(void);
  *     i+D, or after gsmcal_sync(), or after ANY other entry point of this context (they all join the calls in flight first).  The
  *     raw bytes and output buffers of call i must stay untouched until then: give D consecutive calls distinct output buffers.
  *     Each call starts behind whatever the context's stream held when it was made (its input is ordered like at depth 1).
+ *     (Inside call i+D the library first hands the context's stream position to the internal stream and only then makes the
+ *     context's stream wait for the end of call i: call i+D follows call i on the same in-order internal stream anyway, so its
+ *     first kernel does not wait for that join, and the outputs of call i are complete in the context's stream order when call
+ *     i+D RETURNS -- work the caller enqueues on the context's stream after that sees them.)
  *     gsmcal_allgather_table[_async] right behind a pipelined call is enqueued behind THAT call (the gathered table completes where
  *     the call's own outputs do).  gsmcal_last_batch_details describes the most recent call.
  * Results are identical at every depth (same kernels, same order per call).  Returns GSMCAL_E_ARG for depth < 1 or > 8.

@@ -1217,8 +1217,17 @@ int pipe_pick_streams(gsmcal_ctx* c) {
     // (work still queued on the context's stream would hold up a probe kernel that shares its hardware queue and make two good
     // streams look like one: the first call in flight of a context waits for it -- once)
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < NC; ++i) HIPCHK(c, hipStreamCreateWithFlags(&cand[i], hipStreamNonBlocking));   // (default priority: a higher one for some slots measured no better, NOTES_r06)
     unsigned* d_words = nullptr;
+    // (a failed creation gives back the candidates made so far: nothing of the probe outlives an error return)
+    const int made = [&]() -> int {
+        for (int i = 0; i < NC; ++i) HIPCHK(c, hipStreamCreateWithFlags(&cand[i], hipStreamNonBlocking));   // (default priority: a higher one for some slots measured no better, NOTES_r06)
+        return 0;
+    }();
+    if (made < 0) {
+        for (int i = 0; i < NC; ++i)
+            if (cand[i]) (void)hipStreamDestroy(cand[i]);
+        return made;
+    }
     int rc = hipMalloc((void**)&d_words, 2 * sizeof(unsigned)) == hipSuccess ? 0 : GSMCAL_E_HIP;
     std::vector<int> kept;
     for (int i = 0; rc >= 0 && i < NC && (int)kept.size() < gsmcal_ctx::PIPE_MAX_DEPTH; ++i) {
@@ -1294,12 +1303,16 @@ bool pipe_may_fly(gsmcal_ctx* c, int d, bool latency_bound, bool* wanted = nullp
     return want && !c->prof && !stream_capturing(c);
 }
 
-// One call in flight: slot = workspace and stream of this call.  The context's stream first waits for the call that used the slot
-// `depth` calls ago (that call's outputs are complete in the context's stream order from here on), then the slot's stream takes
-// `body(L)` -- which enqueues on c->cur = &L and returns a status -- behind whatever the context's stream holds now.  Whatever the
+// One call in flight: slot = workspace and stream of this call.  The slot's stream takes `body(L)` -- which enqueues on c->cur = &L
+// and returns a status -- behind whatever the context's stream holds now: side_in is recorded on the context's stream and the slot's
+// stream waits for it FIRST.  Only then does the context's stream wait for the call that used the slot `depth` calls ago (that
+// call's outputs are complete in the context's stream order from here on, i.e. when this call returns).  In that order side_in does
+// not sit behind the end of call k - depth: that call ran on this very slot's in-order stream, so its workspace and the slot are
+// free when call k runs anyway, and call k's first kernel follows it on the stream with no cross-stream hand-over in between
+// (recording side_in behind the wait put two of them, ~11 us each, on every call's chain).  Whatever the
 // body returns, the slot is released: its end recorded and pending, the context back on lane 0 with nothing of a call being
 // enqueued left set; after an error the calls in flight are drained as well.  (The lane fields are set before side_in is recorded,
-// as the calibration call had it; the scanner set them behind it.  The HIP calls and their order are those of both.)
+// as the calibration call had it; the scanner set them behind it.)
 template <class F>
 int pipe_call(gsmcal_ctx* c, int d, F body) {
     RET_IF(pipe_prepare(c));
@@ -1308,12 +1321,12 @@ int pipe_call(gsmcal_ctx* c, int d, F body) {
     L.stream = c->side_stream[slot]; L.lo = 0; L.n = d;
     c->cur = &L; c->n_lanes_used = 1;
     int rc = [&]() -> int {
-        if (c->pipe_pending[slot]) {
+        HIPCHK(c, hipEventRecord(c->side_in[slot], c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->side_stream[slot], c->side_in[slot], 0));
+        if (c->pipe_pending[slot]) {                       // (pipe_done[slot] is recorded anew only at the end of this call)
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->pipe_done[slot], 0));
             c->pipe_pending[slot] = false;
         }
-        HIPCHK(c, hipEventRecord(c->side_in[slot], c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->side_stream[slot], c->side_in[slot], 0));
         return body(L);
     }();
     c->cf_lane = nullptr; c->no_fuse_now = false;

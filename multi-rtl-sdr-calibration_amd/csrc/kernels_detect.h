@@ -921,8 +921,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
             } else {
                 // ---- hop loop of FCCH_coarse_position.m:32-86 (positions 1-based, decimated units), whole block ----
                 if (tw_lazy) make_tw();                                  // (block-uniform; the barrier below the set-up covers it)
-                __shared__ long sh_cur;
-                __shared__ int sh_stop, sh_need1, sh_took1;
                 const int lane = tid & 63;
                 const double hit_avg_snr = st->hit_avg_snr;
                 const int dec = a.decimation_ratio;
@@ -935,7 +933,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                 if (tid == 0) {
                     st->coarse_pos[0] = (double)((cur - 1) * dec + 1);  // :91
                     st->coarse_snr[0] = st->mv_hit_snr;
-                    sh_stop = 0; sh_need1 = 0; sh_took1 = 0;
                 }
                 // Certified decisions without the logarithm: 10 log10(sig/noise) - hit_avg_snr > th  <=>  sig/noise > R,
                 // R = 10^((hit_avg_snr + th)/10).  The reference's rounded evaluation sits within 1e-12 dB of the true
@@ -950,7 +947,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                 constexpr bool fast = FFT16;
                 const bool ratio_mode = !exact && fast;
                 // loader threads (tid < 4*CS_ROW): one look-ahead sample each; spectrum threads (tid < 11*16): one
-                // (window, bin) each; wave 0 lanes < 11 turn a group's powers into decisions
+                // (window, bin) each, the 16 bins of window dw in the 16 lanes of one DPP row.  Ratio mode decides a window
+                // inside its row: first maximum and total by the reference trees over row DPP moves, the neighbours of every
+                // bin by row rotates, and the lane that holds the maximum publishes the window's record (signal, noise,
+                // hit / undecided bits).  The exact replay and the generic lengths keep the trip through Pb (the reference's
+                // sequential total needs all 16 powers in one lane): lanes < 11 of wave 0 publish the same record a barrier
+                // later.  EVERY wave then takes the ballots from the group's 11 records and walks on by itself -- cur, n,
+                // took1 and the exits are the same in all of them, nothing goes back through LDS and one barrier per
+                // group (records complete) is all a hop of ratio mode needs behind the one for its rows.  The records of the
+                // two groups lie apart: a wave may publish the +11-frame group while another still reads the +10-frame one;
+                // those of the next hop are written behind that hop's row barrier, which every wave passes with its
+                // ballots taken.
+                double* recs = Pb + 11 * 17;                               // [group][window][4]: a | b | bits (int) | -
+                bool took1 = false;                                        // the hop before settled on a +11-frame candidate
                 cplx pf = make_double2(0.0, 0.0);
                 long pg = -1;
                 long pbase0 = 0, pbase1 = 0;                               // nx0 - 11, nx1 - 11 of the hop that fetched the rows
@@ -959,6 +968,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                 const int dw = tid >> 4, dk = tid & 15;                    // spectrum role
                 __syncthreads();
 #ifdef GSMCAL_DEVTIMING
+                // cycles of thread 0 per hop phase, as tools/devtiming.py prints them ([8->9] .. [12->13]): [0] loads,
+                // [1] the row barrier, [2] the sixteen-point DFTs (ratio mode: with the decision inside the row and the record),
+                // [3] the decision (the record barrier and the ballots; exact replay: with the trip through Pb), [4] what is left of
+                // the hop behind it (no barrier any more)
                 unsigned long long cyc[5] = {0, 0, 0, 0, 0}, c0 = 0;
 #define HOP_CYC(i) do { const unsigned long long c1 = __builtin_readcyclecounter(); cyc[i] += c1 - c0; c0 = c1; } while (0)
 #else
@@ -971,7 +984,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                     c0 = __builtin_readcyclecounter();
 #endif
                     const bool g1ok = nx1 <= limit;
-                    const bool took1 = sh_took1 != 0;
                     int r0 = 0, r1 = 1, off0 = 0, off1 = 0;              // row and offset of each group's first window (start nx - 6)
                     if (fast) {
                         if (have_pf) {
@@ -1002,34 +1014,80 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                     HOP_CYC(0);
                     __syncthreads();                                     // rows of this hop are in LDS
                     HOP_CYC(1);
-                    double v = -INFINITY, c_sig = 0.0, c_noise = 0.0;
-                    int found = -1;                                      // (wave 0) candidate the hop settles on, -1: none
-                    bool stop = false;
-                    for (int grp = 0; grp < 2; ++grp) {                  // +10-frame candidates, then (rarely) the +11-frame ones
-                        if (grp == 1 && !(sh_need1 && g1ok)) break;      // block-uniform
+                    bool stop = false, settled = false;                  // (the same in every wave)
+                    for (int grp = 0; grp < 2 && !stop && !settled; ++grp) {   // +10-frame candidates, then (rarely) the +11-frame ones
+                        double* rec = recs + grp * (11 * 4);
                         if (fast) {
                             if (tid < nt * 16) {                         // bin dk of window dw: direct 16-point DFT, four partial sums
                                 const cplx* x = rows + (grp ? r1 : r0) * CS_ROW + (grp ? off1 : off0) + dw;
                                 double pr_[4] = {0.0, 0.0, 0.0, 0.0}, pi_[4] = {0.0, 0.0, 0.0, 0.0};
+                                // the two LDS reads of step m + 3 (sample and twiddle) go out ahead of the FMAs of step m: four steps
+                                // in registers, the scheduler kept from sinking a read down to its first use.  (The 15 twiddle
+                                // addresses of a lane are formed here, under the latency of the reads in flight: hoisted out of
+                                // the walk they held 15 registers through the whole kernel and pushed it into a scratch frame.)
+                                constexpr int HOP_NB = 4;
+                                cplx xq[HOP_NB], tq[HOP_NB];
+                                int dkv = dk;
+                                asm volatile("" : "+v"(dkv));
+#define HOP_LOAD(m) { tq[(m) % HOP_NB] = tw[(dkv * (m)) & 15]; xq[(m) % HOP_NB] = x[m]; }
+#pragma unroll
+                                for (int m = 0; m < HOP_NB - 1; ++m) HOP_LOAD(m)
 #pragma unroll
                                 for (int m = 0; m < 16; ++m) {
-                                    const cplx t = tw[(dk * m) & 15], xv = x[m];
+                                    if (m + HOP_NB - 1 < 16) HOP_LOAD(m + HOP_NB - 1)
+                                    __builtin_amdgcn_sched_barrier(0);
+                                    const cplx t = tq[m % HOP_NB], xv = xq[m % HOP_NB];
                                     pr_[m & 3] = fma(xv.x, t.x, pr_[m & 3]); pi_[m & 3] = fma(xv.x, t.y, pi_[m & 3]);
                                     pr_[m & 3] = fma(-xv.y, t.y, pr_[m & 3]); pi_[m & 3] = fma(xv.y, t.x, pi_[m & 3]);
+                                    __builtin_amdgcn_sched_barrier(0);
                                 }
+#undef HOP_LOAD
                                 const double xr = (pr_[0] + pr_[1]) + (pr_[2] + pr_[3]), xi = (pi_[0] + pi_[1]) + (pi_[2] + pi_[3]);
-                                Pb[dw * 17 + dk] = xr * xr + xi * xi;
+                                const double p = xr * xr + xi * xi;
+                                if (ratio_mode) {
+                                    // candidate dw (move_fft_snr_runtime_avg.m:22-27) inside its row.  First maximum: the reference
+                                    // tree (pairs, ties and unordered compares to the lower index), both lanes of a pair forming the
+                                    // same result; after xor 1 and xor 2 a quad is uniform, so the mirrors pair the right subtrees.
+                                    const double pm = dpp_move_f64<0x121, 0xF>(p), pp = dpp_move_f64<0x12F, 0xF>(p);   // row_ror 1 / 15: bins dk - 1, dk + 1 (mod 16)
+                                    double sig = pm + p;
+                                    sig = sig + pp;
+                                    double mv = p, tot = p;
+                                    int mi = dk;
+#define HOP_ROWSTEP(CTRL, BIT) {                                                                                        \
+                                        const double ov = dpp_move_f64<CTRL, 0xF>(mv);                                   \
+                                        const int oi = (int)dpp_move_u32<CTRL, 0xF>((unsigned)mi);                       \
+                                        const bool up = (dk & (BIT)) != 0;                                               \
+                                        const double lo = up ? ov : mv, hi = up ? mv : ov;                               \
+                                        const bool r = hi > lo;                                                          \
+                                        mv = r ? hi : lo;                                                                \
+                                        mi = r ? (up ? mi : oi) : (up ? oi : mi);                                        \
+                                        tot += dpp_move_f64<CTRL, 0xF>(tot);     /* the tree total: (((0+1)+(2+3))+...) */ \
+                                    }
+                                    HOP_ROWSTEP(0xB1, 1)                 // quad_perm [1,0,3,2]
+                                    HOP_ROWSTEP(0x4E, 2)                 // quad_perm [2,3,0,1]
+                                    HOP_ROWSTEP(0x141, 4)                // row_half_mirror: the other quad
+                                    HOP_ROWSTEP(0x140, 8)                // row_mirror: the other half
+#undef HOP_ROWSTEP
+                                    if (dk == mi) {                      // (one lane per row: mv is this lane's own power)
+                                        const double c_sig = sig, c_noise = tot - sig;   // (the tree total differs from the sequential one by ~1e-16: inside eps)
+                                        const bool residue = tot <= s.floor2;            // rounding residue of the DC removal, a NaN SNR: a definite miss
+                                        const bool okn = c_noise > 0.0 && c_noise < INFINITY && c_sig < INFINITY;
+                                        const bool is_hit = !residue && okn && c_sig > Rhi * c_noise;
+                                        const bool is_unc = !residue && !(is_hit || (okn && c_sig < Rlo * c_noise));
+                                        rec[dw * 4] = c_sig; rec[dw * 4 + 1] = c_noise;
+                                        ((int*)(rec + dw * 4 + 2))[0] = (is_hit ? 1 : 0) | (is_unc ? 2 : 0);
+                                    }
+                                } else Pb[dw * 17 + dk] = p;
                             }
                             HOP_CYC(2);
-                            __syncthreads();
+                            if (!ratio_mode) __syncthreads();            // (block-uniform)
                         }
-                        if (tid < 64) {
-                            const bool cand = lane < nt;
-                            bool residue = false;
+                        if (!ratio_mode && tid < nt) {                   // candidate `tid`, from all its powers in one lane
+                            double v = -INFINITY;
                             if (fast) {
-                                if (cand) {                              // candidate `lane` (move_fft_snr_runtime_avg.m:22-27)
+                                {                                        // (move_fft_snr_runtime_avg.m:22-27)
                                     double P[16];
-                                    const double* pr = Pb + lane * 17;
+                                    const double* pr = Pb + tid * 17;
 #pragma unroll
                                     for (int k = 0; k < 16; ++k) P[k] = pr[k];
                                     // first maximum by a tree (ties: the lower index), total by a tree
@@ -1043,66 +1101,48 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                                     const double pc = mv[0], pm = pr[(mi[0] + 15) & 15], pp = pr[(mi[0] + 1) & 15];
                                     double sig = pm + pc;
                                     sig = sig + pp;
-                                    if (exact) {
-                                        double tot = 0.0;                // the reference's sequential sum(chn_tmp)
+                                    double tot = 0.0;                    // the reference's sequential sum(chn_tmp): the exact replay
 #pragma unroll
-                                        for (int k = 0; k < 16; ++k) tot += P[k];
-                                        c_sig = sig; c_noise = tot - sig;
-                                        v = 10.0 * log10(c_sig / c_noise);
-                                        if (tot <= s.floor2) v = NAN_D;   // rounding residue of the DC removal: 0/0 in the reference (snr_from_power)
-                                    } else {                             // (the tree total differs from the sequential one by ~1e-16: inside eps)
-                                        double t8[8];
-#pragma unroll
-                                        for (int k = 0; k < 8; ++k) t8[k] = P[2 * k] + P[2 * k + 1];
-                                        const double tot = ((t8[0] + t8[1]) + (t8[2] + t8[3])) + ((t8[4] + t8[5]) + (t8[6] + t8[7]));
-                                        c_sig = sig; c_noise = tot - sig;
-                                        residue = tot <= s.floor2;       // ... a NaN SNR there: a definite miss
-                                    }
+                                    for (int k = 0; k < 16; ++k) tot += P[k];
+                                    v = 10.0 * log10(sig / (tot - sig));
+                                    if (tot <= s.floor2) v = NAN_D;       // rounding residue of the DC removal: 0/0 in the reference (snr_from_power)
                                 }
-                            } else if (cand) {
-                                if (!FFT16) v = window_snr_generic(s, (grp ? nx1 : nx0) - max_offset - 1 + lane, fft_len, tw);
-                            }
-                            bool is_hit, is_unc;
-                            if (ratio_mode) {
-                                const bool okn = c_noise > 0.0 && c_noise < INFINITY && c_sig < INFINITY;
-                                is_hit = cand && !residue && okn && c_sig > Rhi * c_noise;
-                                is_unc = cand && !residue && !(is_hit || (okn && c_sig < Rlo * c_noise));
-                            } else {
-                                is_hit = cand && (v - hit_avg_snr > th);     // NaN compares false
-                                is_unc = !exact && cand && !(fabs((v - hit_avg_snr) - th) > cert_delta);
-                            }
-                            const unsigned long long hm = __ballot(is_hit);
+                            } else v = window_snr_generic(s, (grp ? nx1 : nx0) - max_offset - 1 + tid, fft_len, tw);
+                            const bool is_hit = v - hit_avg_snr > th;    // NaN compares false
+                            const bool is_unc = !exact && !(fabs((v - hit_avg_snr) - th) > cert_delta);
+                            rec[tid * 4] = v;
+                            ((int*)(rec + tid * 4 + 2))[0] = (is_hit ? 1 : 0) | (is_unc ? 2 : 0);
+                        }
+                        __syncthreads();                                 // the group's 11 records are complete
+                        {
+                            const bool cand = lane < nt;
+                            const double ra = cand ? rec[lane * 4] : 0.0, rb = cand ? rec[lane * 4 + 1] : 0.0;
+                            const int bits = cand ? ((const int*)(rec + lane * 4 + 2))[0] : 0;
+                            const unsigned long long hm = __ballot((bits & 1) != 0);
                             if (!exact) {
                                 // every candidate the reference looks at (up to the first hit, else all of the group) must be
                                 // decided for good
-                                const unsigned long long unc = __ballot(is_unc);
+                                const unsigned long long unc = __ballot((bits & 2) != 0);
                                 const unsigned long long looked = hm ? (2ull << (__ffsll((long long)hm) - 1)) - 1 : (1ull << nt) - 1;
-                                if (unc & looked) { if (lane == 0) { sh_redo = 1; sh_stop = 1; } stop = true; }
+                                if (unc & looked) { if (tid == 0) sh_redo = 1; stop = true; }
                             }
                             if (!stop) {
                                 if (hm) {
-                                    found = __ffsll((long long)hm) - 1;
-                                    const long nxt = grp ? nx1 : nx0;
-                                    const long ncur = nxt - max_offset + found;
-                                    if (lane == found) {
+                                    const int found = __ffsll((long long)hm) - 1;    // candidate the hop settles on
+                                    const long ncur = (grp ? nx1 : nx0) - max_offset + found;
+                                    if (tid == found) {
                                         st->coarse_pos[n] = (double)((ncur - 1) * dec + 1);
-                                        if (ratio_mode) { hop_sig[2 * n] = c_sig; hop_sig[2 * n + 1] = c_noise; }
-                                        else st->coarse_snr[n] = v;
-                                        sh_cur = ncur; sh_took1 = grp; sh_need1 = 0;
+                                        if (ratio_mode) { hop_sig[2 * n] = ra; hop_sig[2 * n + 1] = rb; }
+                                        else st->coarse_snr[n] = ra;
                                     }
-                                } else if (grp == 0 && g1ok) {           // :65 try across the idle frame
-                                    if (lane == 0) sh_need1 = 1;
-                                } else if (lane == 0) sh_stop = 1;       // :67 / both miss
+                                    cur = ncur; took1 = grp != 0; settled = true;
+                                } else if (!(grp == 0 && g1ok)) stop = true;   // :67 / both miss; else :65 try across the idle frame
                             }
                         }
                         HOP_CYC(3);
-                        __syncthreads();
-                        if (sh_stop || !sh_need1) break;                 // block-uniform
                     }
-                    if (sh_stop) break;
-                    cur = sh_cur;
+                    if (stop) break;
                     ++n;
-                    __syncthreads();                                     // (sh_* are rewritten by the next hop)
                     HOP_CYC(4);
                 }
 #ifdef GSMCAL_DEVTIMING
@@ -1115,7 +1155,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                 }
 #endif
                 __syncthreads();
-                if (ratio_mode && tid >= 1 && tid < n)                   // the reported SNRs of hops 1..n-1 (:25)
+                // the reported SNRs of hops 1..n-1 (:25), one lane per hop.  Batch path: the value k_coarse_snr's table holds for the
+                // window (window_snr16: its FFT, DC term and sequential total), so that a hop reports the same bits whether it was
+                // looked up in the full table (small batches, depth 1) or decided on the walk's own spectra (calls in flight,
+                // throughput batches) -- "results are identical at every depth" (gsmcal.h) holds for the details too.  The direct
+                // DFT's powers differ from the FFT's in the last places (<= 4e-14 dB on the SNR): they decide, with their margin,
+                // and are not reported.  (A hop lies >= d0 - 5 windows in: past the head rows; its 16 samples end inside the stream.
+                // The reference geometry's forms only: in the general form the 16-point FFT's registers open a scratch frame.)
+                if (REFG && fast && a.mean_corr) {
+                    if (tid >= 1 && tid < n) st->coarse_snr[tid] = window_snr16(s, (long)((st->coarse_pos[tid] - 1.0) / (double)dec));
+                } else if (ratio_mode && tid >= 1 && tid < n)
                     st->coarse_snr[tid] = 10.0 * log10(hop_sig[2 * tid] / hop_sig[2 * tid + 1]);
                 if (tid == 0) st->n_coarse = n;
             }
