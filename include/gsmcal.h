@@ -538,6 +538,69 @@ int gsmcal_cw_check_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, do
 int gsmcal_cw_check_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, double thr, double* d_summary,
                               double* d_r, long r_stride);
 
+/* I/Q imbalance and clipping check of the analogue front end (the reference's TODO item 4.5; no .m file exists for it).  Model: the
+ * dongle delivers I = x_I, Q = g*(x_Q cos(phi) + x_I sin(phi)) of a circular x (equal variance on both rails, uncorrelated: any
+ * signal that sits off 0 Hz for the length of a capture), so var_Q/var_I = g^2 and cov_IQ/sqrt(var_I var_Q) = sin(phi).
+ * Raw form, per capture of N samples with I bytes a_n and Q bytes b_n (raw2iq.m:6), raw: D x 2N bytes, capture-major:
+ *   S_I = sum a, S_Q = sum b, S_II = sum a^2, S_QQ = sum b^2, S_IQ = sum a b, per rail min, max and clip = bytes equal to 0 or 255;
+ *   A_I = N S_II - S_I^2, A_Q = N S_QQ - S_Q^2, C = N S_IQ - S_I S_Q as exact signed 64-bit integers (N <= 2^23 keeps them below
+ *   2^62; a larger n is GSMCAL_E_UNSUPPORTED, decided before anything is enqueued); then in fp64, each integer converted once:
+ *   dc_I = S_I/N, dc_Q = S_Q/N, var_I = A_I/(N*N), var_Q = A_Q/(N*N), gain = sqrt(A_Q/A_I),
+ *   s = C/(sqrt(A_I)*sqrt(A_Q)) clamped to [-1, 1], c = sqrt(1 - s*s), phase_deg = asin(s)*180/pi,
+ *   level_dbfs = 10 log10((var_I + var_Q)/(2*127.5^2)) (-Inf for two constant rails),
+ *   irr_db = 10 log10(((gain+1)^2 - k)/((gain-1)^2 + k)) with k = 2*gain*s*s/(1 + c): |K1|^2/|K2|^2 of K1 = (1 + g e^{j phi})/2,
+ *   K2 = (1 - g e^{-j phi})/2, written so that g ~ 1, phi ~ 0 does not cancel; a zero denominator gives +Inf.
+ * table: [D][GSMCAL_IQ_COLS] doubles, row = the GSMCAL_Q_* columns below; every integer column is below 2^53.
+ * status GSMCAL_IQ_OK; GSMCAL_IQ_SHORT: N < 2 -- the integer columns and dc are written, var_I .. level_dbfs are NaN;
+ * GSMCAL_IQ_FLAT: A_I == 0 or A_Q == 0 (a constant rail) -- gain, sin_phase, phase_deg and irr_db are NaN, the rest is written.
+ * The sums are integers: a row depends on the capture's bytes alone, whatever the batch, its position in it or the alignment.
+ * d >= 1, n >= 1, no NULL pointer, raw 2-byte aligned in the _dev form: anything else GSMCAL_E_ARG with a message.  Workspaces of
+ * their own: gsmcal_last_batch_details / _snr and gsmcal_last_call_report keep answering for the call before.  _dev: enqueues on
+ * the context's stream only; d_table may be device or pinned host memory.
+ * gsmcal_IQ_imbalance is the complex form on one stream s (len complex samples, 1 <= len <= 2^23: raw2iq's output, r_correct):
+ * the same five sums and the min / max of the real and imaginary parts in fp64, the clip columns NaN, A_I, A_Q and C formed in
+ * fp64 -- a DC far above the signal cancels there (raw2iq's output has none); a rail whose A is not positive is GSMCAL_IQ_FLAT.
+ * GSMCAL_IQ_TILE samples per workgroup, one fixed reduction order that depends on len only, no float atomics: a row is
+ * bit-identical from call to call and at any address.  It leaves in gsmcal_last_call_report one line
+ * "I/Q gain g phase p deg image rejection r dB DC i q", or "I/Q imbalance undefined: constant rail." /
+ * "I/Q imbalance undefined: fewer than two samples.".
+ * gsmcal_iq_correct removes a measured imbalance from d complex streams of len samples each (s: [d][len], host), with the
+ * per-stream host arrays gain[d] and sin_phase[d] of their rows: out_I = I, out_Q = (Q/g - I*s)/c, c = sqrt(1 - s*s), which makes
+ * the sample moments of the output balanced.  out may equal s exactly; any partial overlap, a non-finite or non-positive gain or
+ * |sin_phase| >= 1 (or not finite) is GSMCAL_E_ARG.  The output is a complex stream for the per-function entry points. */
+#define GSMCAL_IQ_COLS 22
+#define GSMCAL_IQ_TILE 16384
+#define GSMCAL_IQ_MAX_N (1L << 23)
+#define GSMCAL_IQ_OK 0
+#define GSMCAL_IQ_SHORT 1
+#define GSMCAL_IQ_FLAT 2
+#define GSMCAL_Q_N 0
+#define GSMCAL_Q_S_I 1
+#define GSMCAL_Q_S_Q 2
+#define GSMCAL_Q_S_II 3
+#define GSMCAL_Q_S_QQ 4
+#define GSMCAL_Q_S_IQ 5
+#define GSMCAL_Q_MIN_I 6
+#define GSMCAL_Q_MAX_I 7
+#define GSMCAL_Q_MIN_Q 8
+#define GSMCAL_Q_MAX_Q 9
+#define GSMCAL_Q_CLIP_I 10
+#define GSMCAL_Q_CLIP_Q 11
+#define GSMCAL_Q_DC_I 12
+#define GSMCAL_Q_DC_Q 13
+#define GSMCAL_Q_VAR_I 14
+#define GSMCAL_Q_VAR_Q 15
+#define GSMCAL_Q_GAIN 16
+#define GSMCAL_Q_SIN_PHASE 17
+#define GSMCAL_Q_PHASE_DEG 18
+#define GSMCAL_Q_IRR_DB 19
+#define GSMCAL_Q_LEVEL_DBFS 20
+#define GSMCAL_Q_STATUS 21
+int gsmcal_IQ_imbalance(gsmcal_ctx* ctx, const double* s, long len, double* table_row);
+int gsmcal_iq_imbalance_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, double* table);
+int gsmcal_iq_imbalance_batch_dev(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, double* d_table);
+int gsmcal_iq_correct(gsmcal_ctx* ctx, const double* s, long len, int d, const double* gain, const double* sin_phase, double* out);
+
 /* Scanner detect loop for D captures (multi_rtl_sdr_gsm_FCCH_scanner.m:132-135 front end,
  * :164 FCCH_coarse_position, :168-185 acceptance).  Outputs per capture: snr, num_hit (as the
  * driver's arrays), optional positions/snrs [D][GSMCAL_MAX_HITS] and counts [D] (NULL to skip). */

@@ -7,7 +7,7 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode BCCH_decode CW_check total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
+ *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode BCCH_decode CW_check IQ_imbalance total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
  *            gsmcal_band_power gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
@@ -374,6 +374,25 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     plhs[0] = mxCreateDoubleMatrix(n - 1, 1, mxREAL);
     chk(gsmcal_CW_check(ctx(), s, (long)n, REAL_PTR(plhs[0]), &pr), "CW_check");
     if (nlhs > 1) plhs[1] = scalar(pr);
+
+#elif defined(GSMCAL_FN_IQ_imbalance)
+    /* [gain, phase_deg, irr_db, row] = IQ_imbalance(s)     the I/Q imbalance check of one complex vector (raw2iq's output, r_correct):
+     * gain ratio, quadrature skew in degrees, image rejection in dB and the whole 1 x GSMCAL_IQ_COLS row (columns: GSMCAL_Q_*).
+     * No .m file of the reference exists for it (its TODO item 4.5); the line it prints comes from the library's report. */
+    mwSize n = 0, k;
+    const double* s;
+    double row[GSMCAL_IQ_COLS];
+    if (nrhs < 1 || mxGetNumberOfElements(prhs[0]) < 1) mexErrMsgIdAndTxt("gsmcal:args", "usage: gain = IQ_imbalance(s) with at least one sample");
+    s = cplx_in(prhs[0], &n);
+    chk(gsmcal_IQ_imbalance(ctx(), s, (long)n, row), "IQ_imbalance");
+    say();
+    plhs[0] = scalar(row[GSMCAL_Q_GAIN]);
+    if (nlhs > 1) plhs[1] = scalar(row[GSMCAL_Q_PHASE_DEG]);
+    if (nlhs > 2) plhs[2] = scalar(row[GSMCAL_Q_IRR_DB]);
+    if (nlhs > 3) {
+        plhs[3] = mxCreateDoubleMatrix(1, GSMCAL_IQ_COLS, mxREAL);
+        for (k = 0; k < GSMCAL_IQ_COLS; ++k) REAL_PTR(plhs[3])[k] = row[k];
+    }
 
 #elif defined(GSMCAL_FN_total_ppm_calculation)
     /* ppm_out = total_ppm_calculation(ppm_in) */

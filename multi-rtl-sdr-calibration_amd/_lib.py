@@ -21,6 +21,10 @@ CW_MAX_EVENTS = 16
 CW_COLS = 5 + 2 * CW_MAX_EVENTS    # one row of cw_check_batch: phase_rotate, count, max |r|, n of the maximum, status, (n, r_n) pairs
 CW_TILE = 2048                     # ratios per workgroup of the CW check (GSMCAL_CW_TILE)
 CW_OK, CW_SHORT, CW_ZERO = 0, 1, 2
+IQ_COLS = 22                       # one row of iq_imbalance_batch (api.IQ_FIELDS names the columns)
+IQ_TILE = 16384                    # samples per workgroup of the I/Q check (GSMCAL_IQ_TILE)
+IQ_MAX_N = 1 << 23                 # samples per capture up to which the exact 64-bit moments hold (GSMCAL_IQ_MAX_N)
+IQ_OK, IQ_SHORT, IQ_FLAT = 0, 1, 2
 DEMOD_COLS = 4 + 3 * MAX_HITS      # one row of fcch_demod_batch: num_fcch, mean_freq, carrier_ppm, status, freq[], snr[], max_idx[]
 MAX_BCCH = 4 * MAX_HITS            # BCCH bursts per stream bcch_demod_batch evaluates (GSMCAL_MAX_BCCH)
 BCCH_COLS = 6 + 4 * MAX_BCCH       # one row of bcch_demod_batch: six scalars (api.BCCH_FIELDS), then idx[], peak[], runner_up[], phase[]
@@ -113,6 +117,10 @@ SIGNATURES = {
     "gsmcal_cw_check_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, C.c_double, c_double_p, c_double_p, C.c_long]),
     "gsmcal_cw_check_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_void_p, C.c_void_p,
                                             C.c_long]),
+    "gsmcal_IQ_imbalance": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_double_p]),
+    "gsmcal_iq_imbalance_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p]),
+    "gsmcal_iq_imbalance_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p]),
+    "gsmcal_iq_correct": (C.c_int, [C.c_void_p, c_double_p, C.c_long, C.c_int, c_double_p, c_double_p, c_double_p]),
     "gsmcal_fcch_scan_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, c_double_p,
                                          c_double_p, c_double_p, c_double_p, c_int_p]),
     "gsmcal_fcch_scan_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, c_double_p, C.c_int,

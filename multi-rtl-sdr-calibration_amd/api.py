@@ -18,7 +18,8 @@ sentinel returns (scalar -1.0 / inf, pos_info = [[-1, -1]]) so that tests read l
     [idx,r,carrier_ppm] = BCCH_demod(s,pos_info,normal_training_sequence,ov,carrier_freq)     BCCH_demod.m:5 (a dict)
     ppm_out = total_ppm_calculation(ppm_in)
 and, without a counterpart in the reference (its SCH_demod.m returns nothing, its BCCH_demod.m stops at the training sequence index):
-SCH_decode(s,pos_info,sch_training_sequence,ov) and BCCH_decode(s,pos_info,tsc,ov).
+SCH_decode(s,pos_info,sch_training_sequence,ov) and BCCH_decode(s,pos_info,tsc,ov); and IQ_imbalance(s) / iq_correct(s,gain,sin_phase)
+for the I/Q imbalance its TODO item 4.5 asks about.
 
 Everything computes on the GPU through the C ABI; there is no CPU fallback.
 """
@@ -31,7 +32,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -696,6 +697,67 @@ def cw_check_batch_dev(d_raw, d, n, thr, d_summary, d_r=None, r_stride=0, ctx=No
     ctx = ctx or default_context()
     ctx.check(ctx.lib.gsmcal_cw_check_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), float(thr), C.c_void_p(d_summary),
                                                 C.c_void_p(d_r) if d_r else None, int(r_stride)), "cw_check_batch_dev")
+
+
+# columns of a row of iq_imbalance_batch[_dev] / IQ_imbalance, in order (GSMCAL_Q_*)
+IQ_FIELDS = ("n", "S_I", "S_Q", "S_II", "S_QQ", "S_IQ", "min_I", "max_I", "min_Q", "max_Q", "clip_I", "clip_Q", "dc_I", "dc_Q",
+             "var_I", "var_Q", "gain", "sin_phase", "phase_deg", "irr_db", "level_dbfs", "status")
+_IQ_INT_FIELDS = ("n", "clip_I", "clip_Q", "status")
+
+
+def iq_rows(table):
+    """(D, IQ_COLS) table of iq_imbalance_batch[_dev] / one row of IQ_imbalance -> one dict per capture keyed by IQ_FIELDS: n and
+    status as ints, the clip counts as ints or None where they are NaN (the complex form), everything else as floats."""
+    rows = []
+    for t in np.asarray(table, dtype=np.float64).reshape(-1, IQ_COLS):
+        row = {k: float(v) for k, v in zip(IQ_FIELDS, t)}
+        for k in _IQ_INT_FIELDS:
+            row[k] = None if np.isnan(row[k]) else int(row[k])
+        rows.append(row)
+    return rows
+
+
+def iq_imbalance_batch(raw, ctx=None):
+    """raw: (D, 2N) uint8 -> the (D, IQ_COLS) table of the I/Q imbalance and clipping check (IQ_FIELDS / iq_rows name its columns):
+    the exact byte sums, min, max and clip count per rail, DC, variance, gain ratio, quadrature skew, image rejection, level."""
+    ctx = ctx or default_context()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    if raw.ndim != 2 or raw.shape[1] % 2:
+        raise ValueError("raw must be (D, 2N) bytes")
+    d, two_n = raw.shape
+    out = np.empty((d, IQ_COLS))
+    ctx.check(ctx.lib.gsmcal_iq_imbalance_batch(ctx.h, raw.ctypes.data_as(_lib.c_u8_p), d, two_n // 2, _dp(out)), "iq_imbalance_batch")
+    return out
+
+
+def iq_imbalance_batch_dev(d_raw, d, n, d_table, ctx=None):
+    """Device-pointer form of iq_imbalance_batch: only enqueues on the context's stream (ctx.sync() before reading).  d_raw: [d][2n]
+    bytes, 2-byte aligned; d_table: [d][IQ_COLS] doubles in device or pinned host memory."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.gsmcal_iq_imbalance_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), C.c_void_p(d_table)), "iq_imbalance_batch_dev")
+
+
+def IQ_imbalance(s, ctx=None):
+    """The I/Q check of one complex stream s (N,) (raw2iq's output, r_correct) -> one (IQ_COLS,) row, the clip columns NaN."""
+    ctx = ctx or default_context()
+    buf, n, _ = _cplx_in(np.asarray(s).ravel())
+    row = np.empty(IQ_COLS)
+    ctx.check(ctx.lib.gsmcal_IQ_imbalance(ctx.h, _dp(buf.view(np.float64)), n, _dp(row)), "IQ_imbalance")
+    _say(ctx)
+    return row
+
+
+def iq_correct(s, gain, sin_phase, ctx=None):
+    """Removes a measured imbalance: s complex (N,) or (N, D) (one stream per column, as the per-function entry points take them),
+    gain and sin_phase scalars or (D,) from the streams' rows -> the same shape with Q replaced by (Q/g - I*s)/sqrt(1 - s*s)."""
+    ctx = ctx or default_context()
+    s = np.asarray(s)
+    buf, n, d = _cplx_in(s)
+    g = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.float64).ravel(), (d,)))
+    sp = np.ascontiguousarray(np.broadcast_to(np.asarray(sin_phase, dtype=np.float64).ravel(), (d,)))
+    out = np.empty_like(buf)
+    ctx.check(ctx.lib.gsmcal_iq_correct(ctx.h, _dp(buf.view(np.float64)), n, d, _dp(g), _dp(sp), _dp(out.view(np.float64))), "iq_correct")
+    return out[0] if s.ndim == 1 else np.ascontiguousarray(out.T)
 
 
 def _opt(p):

@@ -1337,6 +1337,110 @@ int gsmcal_CW_check(gsmcal_ctx* c, const double* s, long len, double* r, double*
     return 0;
 }
 
+// ---- I/Q imbalance and clipping check (the reference's TODO item 4.5; kernels_iqcheck.h) ---------------------------------------------
+// Passes: k_iq_moments (one record per capture and tile), k_iq_finish (the whole row).  `arr` != nullptr: one complex array instead
+// of raw bytes (gsmcal_IQ_imbalance).
+static const auto k_iq_moments_raw = &k_iq_moments<true>;
+static const auto k_iq_moments_arr = &k_iq_moments<false>;
+static const auto k_iq_finish_raw = &k_iq_finish<true>;
+static const auto k_iq_finish_arr = &k_iq_finish<false>;
+static_assert(IQ_TILE == GSMCAL_IQ_TILE && IQ_COLS == GSMCAL_IQ_COLS && IQ_N_MAX == GSMCAL_IQ_MAX_N && IQ_ST_SHORT == GSMCAL_IQ_SHORT &&
+              IQ_ST_FLAT == GSMCAL_IQ_FLAT && GSMCAL_Q_STATUS == IQ_COLS - 1, "kernels_iqcheck.h and include/gsmcal.h disagree");
+
+static int iq_enqueue(gsmcal_ctx* c, const uint8_t* d_raw, const cplx* arr, int d, long n, double* d_table) {
+    c->cur = &c->lanes[0];                              // the context's stream; the lane's buffers are not touched
+    const long nblk = (n + IQ_TILE - 1) / IQ_TILE;      // n <= 2^23: at most 512
+    const size_t rec = arr ? sizeof(IqPart<false>) : sizeof(IqPart<true>);
+    RET_IF(ensure(c, c->iq_part, (size_t)d * nblk * rec));
+    if (arr) {
+        IqPart<false>* part = (IqPart<false>*)c->iq_part.p;
+        LAUNCH(c, k_iq_moments_arr, dim3((unsigned)nblk, d), dim3(256), 0, (const uint8_t*)nullptr, 0L, arr, n, n, part);
+        LAUNCH(c, k_iq_finish_arr, dim3((d + 3) / 4), dim3(256), 0, (const IqPart<false>*)part, (int)nblk, d, n, d_table);
+    } else {
+        IqPart<true>* part = (IqPart<true>*)c->iq_part.p;
+        for_capture_chunks(d, [&](long lo, int S) {
+            LAUNCH(c, k_iq_moments_raw, dim3((unsigned)nblk, S), dim3(256), 0, d_raw + (size_t)lo * 2 * n, 2 * n, (const cplx*)nullptr, 0L, n,
+                   part + lo * nblk);
+        });
+        LAUNCH(c, k_iq_finish_raw, dim3((d + 3) / 4), dim3(256), 0, (const IqPart<true>*)part, (int)nblk, d, n, d_table);
+    }
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+static int iq_args_ok(gsmcal_ctx* c, const void* raw, int d, long n, const void* table) {
+    if (!c) return GSMCAL_E_ARG;
+    const char* why = nullptr;
+    if (!raw || !table) why = "iq_imbalance: raw and table must not be NULL";
+    else if (d < 1) why = "iq_imbalance: d must be at least 1";
+    else if (n < 1) why = "iq_imbalance: n must be at least 1";
+    if (why) { c->err = why; return GSMCAL_E_ARG; }
+    if (n > GSMCAL_IQ_MAX_N) { c->err = "iq_imbalance: n above 2^23 (the exact 64-bit moments would overflow)"; return GSMCAL_E_UNSUPPORTED; }
+    return 0;
+}
+
+int gsmcal_iq_imbalance_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n, double* d_table) {
+    RET_IF(iq_args_ok(c, d_raw, d, n, d_table));
+    if ((uintptr_t)d_raw & 1) { c->err = "iq_imbalance: d_raw must be 2-byte aligned"; return GSMCAL_E_ARG; }
+    ENTER(c);
+    return iq_enqueue(c, d_raw, nullptr, d, n, d_table);
+}
+
+int gsmcal_iq_imbalance_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, double* table) {
+    RET_IF(iq_args_ok(c, raw, d, n, table));
+    ENTER(c);
+    const Stage io[] = {STAGE(stage_raw, (size_t)2 * n * d, raw, nullptr, 0),
+                        STAGE(stage_out, (size_t)d * GSMCAL_IQ_COLS * sizeof(double), nullptr, table, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(iq_enqueue(c, (const uint8_t*)c->stage_raw.p, nullptr, d, n, (double*)c->stage_out.p));
+    return stage_down(c, io);
+}
+
+int gsmcal_IQ_imbalance(gsmcal_ctx* c, const double* s, long len, double* table_row) {
+    if (!c) return GSMCAL_E_ARG;
+    if (!s || !table_row || len < 1) { c->err = "IQ_imbalance: s and table_row must not be NULL and len must be at least 1"; return GSMCAL_E_ARG; }
+    if (len > GSMCAL_IQ_MAX_N) { c->err = "IQ_imbalance: len above 2^23"; return GSMCAL_E_UNSUPPORTED; }
+    ENTER(c);
+    c->report.clear();
+    const Stage io[] = {STAGE(iq_in, (size_t)len * sizeof(cplx), s, nullptr, 0),
+                        STAGE(stage_out, GSMCAL_IQ_COLS * sizeof(double), nullptr, table_row, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(iq_enqueue(c, nullptr, (const cplx*)c->iq_in.p, 1, len, (double*)c->stage_out.p));
+    RET_IF(stage_down(c, io));
+    c->report = report_iq_imbalance(table_row);
+    return 0;
+}
+
+int gsmcal_iq_correct(gsmcal_ctx* c, const double* s, long len, int d, const double* gain, const double* sin_phase, double* out) {
+    if (!c) return GSMCAL_E_ARG;
+    const char* why = nullptr;
+    if (!s || !gain || !sin_phase || !out) why = "iq_correct: no pointer may be NULL";
+    else if (d < 1 || len < 1 || (size_t)d * (size_t)len > ((size_t)1 << 36)) why = "iq_correct: d and len must be at least 1 and d*len at most 2^36";
+    else {
+        const size_t bytes = (size_t)d * len * sizeof(cplx);
+        const uintptr_t a = (uintptr_t)s, b = (uintptr_t)out;
+        if (a != b && a < b + bytes && b < a + bytes) why = "iq_correct: out may equal s or lie apart from it, not overlap it";
+        for (int i = 0; i < d && !why; ++i) {
+            if (!std::isfinite(gain[i]) || !(gain[i] > 0.0)) why = "iq_correct: every gain must be finite and > 0";
+            else if (!(fabs(sin_phase[i]) < 1.0)) why = "iq_correct: every |sin_phase| must be below 1";
+        }
+    }
+    if (why) { c->err = why; return GSMCAL_E_ARG; }
+    ENTER(c);
+    c->cur = &c->lanes[0];
+    std::vector<double> par((size_t)2 * d);
+    for (int i = 0; i < d; ++i) { par[2 * i] = gain[i]; par[2 * i + 1] = sin_phase[i]; }
+    RET_IF(upload_if_changed(c, c->iq_par, c->h_iq_par, par.data(), par.size(), "I/Q correction parameters"));
+    const Stage io[] = {STAGE(iq_in, (size_t)d * len * sizeof(cplx), s, out, 0)};
+    RET_IF(stage_up(c, io));
+    for_capture_chunks(d, [&](long lo, int S) {
+        LAUNCH(c, k_iq_correct, dim3((unsigned)((len + 1023) / 1024), S), dim3(256), 0, (cplx*)c->iq_in.p + (size_t)lo * len, len,
+               (const double*)c->iq_par.p + 2 * lo);
+    });
+    CHECK_LAUNCH(c);
+    return stage_down(c, io);
+}
+
 int gsmcal_fcch_scan_batch_dev(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n, const double* coef, int ntaps,
                                double* d_snr_numhit, double* d_positions, double* d_pos_snr, int* d_counts) {
     if (!c || !d_raw || !coef || !d_snr_numhit || d < 1 || n < 1 || ntaps < 1) return GSMCAL_E_ARG;

@@ -177,4 +177,13 @@ std::string report_bcch_decode(const double* row, const gsmcal_si_info& si) {
     return r + buf;
 }
 
+// gsmcal_IQ_imbalance (the project's own line).  row: one row of the I/Q table (GSMCAL_Q_*).
+std::string report_iq_imbalance(const double* row) {
+    const int status = (int)row[GSMCAL_Q_STATUS];
+    if (status == GSMCAL_IQ_SHORT) return "I/Q imbalance undefined: fewer than two samples.\n";
+    if (status == GSMCAL_IQ_FLAT) return "I/Q imbalance undefined: constant rail.\n";
+    return "I/Q gain " + rep_num2str(row[GSMCAL_Q_GAIN]) + " phase " + rep_num2str(row[GSMCAL_Q_PHASE_DEG]) + " deg image rejection " +
+           rep_num2str(row[GSMCAL_Q_IRR_DB]) + " dB DC " + rep_num2str(row + GSMCAL_Q_DC_I, 2) + "\n";
+}
+
 }  // namespace

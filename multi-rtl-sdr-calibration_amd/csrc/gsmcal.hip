@@ -33,6 +33,7 @@
 #include "kernels_spectrum.h"
 #include "kernels_subband.h"
 #include "kernels_cwcheck.h"
+#include "kernels_iqcheck.h"
 #include "state.h"
 
 #define GSMCAL_VERSION "gsmcal-mi355x 0.1 (gfx950)"

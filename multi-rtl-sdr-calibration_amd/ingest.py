@@ -197,3 +197,27 @@ def check_sample_loss(ring, slot, d, n, thr, ctx=None):
     finally:
         ctx.lib.gsmcal_dev_free(ctx.h, d_out)
     return api.cw_rows(out)
+
+
+def check_front_end(ring, slot, d, n, ctx=None):
+    """The I/Q imbalance and clipping check on a ring slot that has been submitted: DC, gain ratio, quadrature skew, image
+    rejection, level and the count of bytes at the ADC's rails of the slot's d captures of n samples each (dongle-major bytes, as
+    capture_all fills them) on the device copy, returned as api.iq_rows -- one dict per dongle.  The slot is acquired and
+    released here; the call returns when the rows are on the host."""
+    from . import api
+    ctx = ctx or ring.ctx
+    if 2 * int(n) * int(d) > ring.bytes:
+        raise ValueError("the slot holds fewer than d captures of n samples")
+    out = np.empty((int(d), api.IQ_COLS))
+    d_out = C.c_void_p()
+    ctx.check(ctx.lib.gsmcal_dev_alloc(ctx.h, out.nbytes, C.byref(d_out)), "gsmcal_dev_alloc")
+    try:
+        d_raw = ring.acquire(slot)
+        try:
+            api.iq_imbalance_batch_dev(d_raw, d, n, d_out.value, ctx=ctx)
+            ctx.check(ctx.lib.gsmcal_memcpy_d2h(ctx.h, out.ctypes.data_as(C.c_void_p), d_out, out.nbytes), "gsmcal_memcpy_d2h")
+        finally:
+            ring.release(slot)
+    finally:
+        ctx.lib.gsmcal_dev_free(ctx.h, d_out)
+    return api.iq_rows(out)

@@ -436,9 +436,18 @@ def ideal_waveform(num_frames, start_frame, rng, bcch=True, tsc=0, bsic=None, fn
     return x
 
 
+def _iq_impair(y, iq_gain, iq_phase_deg):
+    """The front end's I/Q imbalance on a complex waveform: I = x_I, Q = g*(x_Q cos(phi) + x_I sin(phi)) (either argument left at
+    None: g = 1 / phi = 0)."""
+    g = 1.0 if iq_gain is None else float(iq_gain)
+    phi = 0.0 if iq_phase_deg is None else math.radians(float(iq_phase_deg))
+    return y.real + 1j * (g * (y.imag * math.cos(phi) + y.real * math.sin(phi)))
+
+
 def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
                 sampling_ppm=None, carrier_ppm=None, snr_db=None, carrier_freq=957.4e6,
-                start_frame=None, frac_start=None, tx_key=None, tsc=0, bsic=None, fn0=None, si=None):
+                start_frame=None, frac_start=None, tx_key=None, tsc=0, bsic=None, fn0=None, si=None,
+                iq_gain=None, iq_phase_deg=None):
     """One capture: returns (raw uint8 interleaved I,Q of length 2*num_frames*10000, truth dict).
     tx_key: dongles given the same key receive the SAME transmission (payload, multiframe phase, start instant) through
     their own clocks, carrier offsets and noise -- what gsm_sync_demod.m's inter-dongle phase plot (:151-158) looks at.
@@ -447,7 +456,9 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     needs start_frame given with fn0 mod 51 == start_frame.  Left at None the SCH payload stays random and the capture is
     byte-identical to what it always was.
     si: the system information the BCCH blocks carry (ideal_waveform; si3_octets / si4_octets build one); None leaves their
-    payload random and the capture byte-identical likewise."""
+    payload random and the capture byte-identical likewise.
+    iq_gain / iq_phase_deg: the front end's gain ratio g and quadrature skew phi (_iq_impair), applied to the noisy waveform before
+    the DC and the rounding; with both left at None nothing is applied and the capture is byte-identical likewise."""
     rng = np.random.Generator(np.random.Philox(key=[int(seed), (int(dongle) << 20) ^ int(arfcn)]))
     eps_s = rng.uniform(-80.0, 80.0) if sampling_ppm is None else float(sampling_ppm)
     eps_c = rng.uniform(-40.0, 40.0) if carrier_ppm is None else float(carrier_ppm)
@@ -479,6 +490,8 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     amp = 70.0
     sigma = amp * 10.0 ** (-snr / 20.0) / math.sqrt(2.0)
     y = amp * y + sigma * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    if iq_gain is not None or iq_phase_deg is not None:
+        y = _iq_impair(y, iq_gain, iq_phase_deg)
     dc = 127.4 + rng.uniform(-1.0, 1.0, 2)
     raw = np.empty(2 * n, dtype=np.float64)
     raw[0::2] = y.real + dc[0]
@@ -489,14 +502,16 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     payload = _sch_payload_args(sf, bsic, fn0) if bcch else None
     truth["bsic"], truth["fn0"] = payload if payload is not None else (None, None)
     truth["si"] = _si_args(si) if bcch else None
+    truth["iq_gain"], truth["iq_phase_deg"] = iq_gain, iq_phase_deg
     return raw, truth
 
 
-def make_cw(n, step=0.7, amp=100.0, dc=(127.4, 127.6), noise=0.5, drops=(), seed=DEFAULT_SEED):
+def make_cw(n, step=0.7, amp=100.0, dc=(127.4, 127.6), noise=0.5, drops=(), seed=DEFAULT_SEED, iq_gain=None, iq_phase_deg=None):
     """A CW capture as check_CW_samples_loss_tcp.m records one from a signal generator: the tone amp*exp(1i*(step*t + phi)) plus
     white Gaussian noise (standard deviation `noise` per component) plus DC, rounded and clipped to bytes; returns the 2n
     interleaved uint8 I,Q bytes.  drops = [(pos, k), ...] removes k samples of the source after output index pos (0-based), so
-    CW_check's spike of k*step (mod 2 pi) lands at n = pos + 1 (1-based)."""
+    CW_check's spike of k*step (mod 2 pi) lands at n = pos + 1 (1-based).  iq_gain / iq_phase_deg: the front end's I/Q imbalance
+    (_iq_impair) on the noisy tone before the DC and the rounding; both None: nothing is applied, the bytes are what they always were."""
     rng = np.random.Generator(np.random.Philox(key=[int(seed), 0x4357 ^ int(n)]))
     gap = np.zeros(n, dtype=np.int64)
     for pos, k in drops:
@@ -506,6 +521,8 @@ def make_cw(n, step=0.7, amp=100.0, dc=(127.4, 127.6), noise=0.5, drops=(), seed
     t = np.arange(n, dtype=np.float64) + np.cumsum(gap)
     y = amp * np.exp(1j * (step * t + rng.uniform(0, 2 * math.pi)))
     y = y + noise * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    if iq_gain is not None or iq_phase_deg is not None:
+        y = _iq_impair(y, iq_gain, iq_phase_deg)
     raw = np.empty(2 * n, dtype=np.float64)
     raw[0::2] = y.real + dc[0]
     raw[1::2] = y.imag + dc[1]
