@@ -1895,6 +1895,17 @@ __host__ inline size_t fc_lds_bytes(int nshift, int nfft) {
 // and the same switches cost the 1 024-stream step 1.3 %.)
 #define FC_PRIO(P0, P1, P2) if (gridDim.x * gridDim.y <= 768u) { const unsigned rnd_ = (blockIdx.y * gridDim.x + blockIdx.x) >> 8; if (rnd_ == 0) __builtin_amdgcn_s_setprio(P0); else if (rnd_ == 1) __builtin_amdgcn_s_setprio(P1); else __builtin_amdgcn_s_setprio(P2); }
 #define FC_PF 8   /* slide steps whose samples are fetched from LDS ahead of the arithmetic */
+// Development build: a stamp taken by lane 0 of wave `wv` (DEV_STAMP is thread 0's): 12 / 13 = the E / C wave has finished its
+// scan, 14 = wave 0 has finished its slides -- all three in front of the join that stamp 6 follows.
+#ifdef GSMCAL_DEVTIMING
+#define FC_ROLE_STAMP(wv, i)                                                                                          \
+    do {                                                                                                              \
+        if (DEV_STAMP_ON(KID_CERT, i) && g_stamps && wave == (wv) && lane == 0 && blockIdx.y * gridDim.x + blockIdx.x < DEV_STAMP_BLOCKS) \
+            g_stamps[((size_t)KID_CERT * DEV_STAMP_BLOCKS + blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = wall_clock64();           \
+    } while (0)
+#else
+#define FC_ROLE_STAMP(wv, i) do { } while (0)
+#endif
 // OV > 0: the reference geometry as compile-time constants (128*OV+1 shifts, 148*OV-point windows, NTAPS filter taps);
 // OV = 0: from the arguments.
 template <int OV, int NTAPS>
@@ -2169,8 +2180,65 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
     __syncthreads();                                      // S and the tables are dead: E and sumS take their place
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 4);
     FC_PRIO(0, 1, 2)                                      // E(t), slides, certificate: youngest first
-    // ---- E(t): E(0) by a block reduction, then a block scan of g[q] = |x[q+nfft]|^2 - |x[q]|^2 ----
-    {
+    // ---- E(t) and C(t) need nothing but the window.  Role split (block-uniform): where at least two waves hold no slide
+    // lane (the reference geometry: 128 slide lanes in 256 threads), the slide waves go straight on and two of the others
+    // form the two scans meanwhile, each on its own -- no barrier and no exchange before the join in front of the block
+    // reduction.  (Before: all four waves scanned together, then waves 2 and 3 sat out the slides.)  Only the association
+    // of the fp64 sums differs (~1e-13 relative in E and C, far inside the certificate's margins); P*, t*, k* are untouched.
+    const int nslide = (FC_NB * nchunk + 63) >> 6;        // waves that hold slide lanes
+    const bool split = nwave - nslide >= 2;
+    if (split) {
+        DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 5);
+        if (wave == nslide || wave == nslide + 1) {       // (wave-uniform) the E wave and the C wave
+            const bool we = wave == nslide;
+            // a contiguous range of shifts per lane, an inclusive wave scan of the lane totals, a second pass with the running values
+            const int per = OV > 0 ? 2 * OV : (nstep + 63) >> 6;
+            const int i0 = lane * per < nstep ? lane * per : nstep, i1 = i0 + per < nstep ? i0 + per : nstep;
+            auto term = [&](int q) -> double {
+                const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
+                if (we) return (a1.x * a1.x + a1.y * a1.y) - (b1.x * b1.x + b1.y * b1.y);
+                // |d_q| in fp32, scaled up by 1 + 2^-20: see the block scan below
+                const double dr = a1.x - b1.x, di = a1.y - b1.y;
+                return (double)(__fsqrt_rn((float)(dr * dr + di * di)) * 1.00000095367431640625f);
+            };
+            double run = 0.0;
+            if (we) {                                     // E(0), in every lane
+                for (int i = lane; i < nfft; i += 64) { const cplx v = xs[FC_XP(i)]; run += v.x * v.x + v.y * v.y; }
+                for (int off = 32; off > 0; off >>= 1) run += __shfl_down(run, off, 64);
+                run = __shfl(run, 0, 64);
+            }
+            double g[OV > 0 ? 2 * OV : 1];                // reference geometry: the range's terms stay in registers for the second pass
+            double loc = 0.0;
+            if (OV > 0) {
+#pragma unroll
+                for (int u = 0; u < 2 * OV; ++u) { g[u] = term(i0 + u); loc += g[u]; }   // (nstep = 64 * per: every range is whole)
+            } else {
+                for (int q = i0; q < i1; ++q) loc += term(q);
+            }
+            double inc = loc;
+            for (int off = 1; off < 64; off <<= 1) {
+                const double o = __shfl_up(inc, off, 64);
+                if (lane >= off) inc += o;
+            }
+            const double exc = __shfl_up(inc, 1, 64);
+            if (lane > 0) run += exc;
+            if (OV > 0) {
+#pragma unroll
+                for (int u = 0; u < 2 * OV; ++u) {
+                    if (we) Et[i0 + u] = run; else Cs[FC_XP(i0 + u)] = (float)run;
+                    run += g[u];
+                }
+            } else {
+                for (int q = i0; q < i1; ++q) {
+                    if (we) Et[q] = run; else Cs[FC_XP(q)] = (float)run;
+                    run += term(q);
+                }
+            }
+            if (i1 == nstep && i0 < nstep) { if (we) Et[nstep] = run; else Cs[FC_XP(nstep)] = (float)run; }
+            FC_ROLE_STAMP(wave, we ? 12 : 13);
+        }
+    } else {
+        // E(0) by a block reduction, then a block scan of g[q] = |x[q+nfft]|^2 - |x[q]|^2
         double e0 = 0.0;
         for (int i = tid; i < nfft; i += nthr) { const cplx v = xs[FC_XP(i)]; e0 += v.x * v.x + v.y * v.y; }
         for (int off = 32; off > 0; off >>= 1) e0 += __shfl_down(e0, off, 64);
@@ -2205,8 +2273,8 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
             rund += (double)(__fsqrt_rn((float)(dr * dr + di * di)) * 1.00000095367431640625f);
         }
         if (i1 == nstep && i0 < nstep) { Et[nstep] = run; Cs[FC_XP(nstep)] = (float)rund; }
+        DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 5);
     }
-    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 5);
     // ---- slides: lane (c, j) walks chunk c of bin k; the 8 lanes of a group share the shift ----
     double best = -1.0;
     int bt = 0x7fffffff;
@@ -2242,6 +2310,7 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
             for (int u = 0; u < FC_PF; ++u) sumS[FC_XP(t0 + q0 + u + 1)] = ps[u];
         }
     }
+    FC_ROLE_STAMP(0, 14);
     int bk = k;
     for (int off = 32; off > 0; off >>= 1) {
         const double op = __shfl_down(best, off, 64);
@@ -2249,7 +2318,7 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
         const int ok = __shfl_down(bk, off, 64);
         if (op > best || (op == best && (ot < bt || (ot == bt && ok < bk)))) { best = op; bt = ot; bk = ok; }
     }
-    __syncthreads();                                      // red_p was E(0) until here
+    __syncthreads();                                      // the join of the roles (without the split: red_p was E(0) until here)
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 6);
     if (lane == 0) { red_p[wave] = best; red_t[wave] = bt; red_k[wave] = bk; }
     __syncthreads();
