@@ -53,6 +53,7 @@ enum {
     GSMCAL_S_BCCH_TSC_MIXED = 13, /* BCCH_demod.m:103-105: the first four BCCH bursts disagree     */
     GSMCAL_S_SCH_NO_DECODE = 14,  /* gsmcal_SCH_decode: fewer than two SCH bursts decode consistently */
     GSMCAL_S_BCCH_NO_DECODE = 15, /* gsmcal_BCCH_decode: no BCCH block passes the Fire code's check   */
+    GSMCAL_S_PAIR_FEW = 16,       /* gsmcal_pair_coherence: fewer than two bursts of the pair are used */
     /* < 0: failures */
     GSMCAL_E_ARG = -1,
     GSMCAL_E_HIP = -2,
@@ -72,6 +73,8 @@ enum {
 #define GSMCAL_SI_COLS (4 + 7 * GSMCAL_MAX_HITS)       /* one row of gsmcal_bcch_decode_batch[_dev]: 172 doubles */
 #define GSMCAL_BLOCK_OCTETS 23                         /* octets of one BCCH block (GSMCAL_SI_OCTETS of gsmcal_si.h) */
 #define GSMCAL_BLOCK_CODED 456                         /* coded bits of one BCCH block */
+#define GSMCAL_MAX_PAIR_BURSTS (GSMCAL_MAX_HITS + GSMCAL_MAX_BCCH)   /* type-1 and type-2 rows gsmcal_pair_coherence_batch evaluates: 120 */
+#define GSMCAL_PAIR_COLS (16 + 6 * GSMCAL_MAX_PAIR_BURSTS)           /* one row of gsmcal_pair_coherence_batch[_dev]: 736 doubles */
 
 /* columns of one row of the calibration table (doubles; this row is what ranks all-gather) */
 enum {
@@ -145,6 +148,30 @@ enum {
     GSMCAL_I_MEAN_SLOPE = 4 + 5 * GSMCAL_MAX_HITS,  /* [GSMCAL_MAX_HITS] mean phase slope of the four bursts, rad/symbol       */
     GSMCAL_I_AMP = 4 + 6 * GSMCAL_MAX_HITS          /* [GSMCAL_MAX_HITS] mean of the four bursts' |h| / 26                     */
 };
+
+/* columns of one row of the pair_coherence table (doubles) */
+#define GSMCAL_P_STATUS 0               /* 0, GSMCAL_S_POST_NO_POS, GSMCAL_S_PAIR_FEW, GSMCAL_E_CAPACITY                         */
+#define GSMCAL_P_NUM_BURSTS 1           /* type-1 and type-2 rows of a's pos_info (0 at GSMCAL_S_POST_NO_POS)                    */
+#define GSMCAL_P_NUM_EVAL 2             /* bursts whose two windows lie inside the streams                                       */
+#define GSMCAL_P_NUM_USED 3             /* evaluated, not at the edge of the lag range, coherence >= min_coherence               */
+#define GSMCAL_P_NUM_ADJACENT 4         /* steps between consecutive used bursts at most 1.5 frames apart                        */
+#define GSMCAL_P_LAG0 5                 /* the pair's lag0, as given                                                             */
+#define GSMCAL_P_DELAY0 6               /* delay of b against a at the first used burst, samples (the fitted line at t = 0)      */
+#define GSMCAL_P_REL_SAMPLING_PPM 7     /* 1e6 * slope of that line                                                              */
+#define GSMCAL_P_DELAY_RMS 8            /* rms of the delays about the line, samples                                             */
+#define GSMCAL_P_REL_CARRIER_HZ 9       /* carrier of b against a: burst_carrier_hz refined by the adjacent phase steps          */
+#define GSMCAL_P_BURST_CARRIER_HZ 10    /* mean of freq[] over the used bursts                                                   */
+#define GSMCAL_P_PHASE0 11              /* phase of b against a at the centre of the first used burst, rad                       */
+#define GSMCAL_P_PHASE_RMS 12           /* rms of the used bursts' phases about phase0 + 2 pi rel_carrier_hz t / fs, rad         */
+#define GSMCAL_P_MEAN_COHERENCE 13      /* mean of coherence[] over the used bursts                                              */
+#define GSMCAL_P_MIN_COHERENCE_SEEN 14  /* ... and the smallest                                                                  */
+#define GSMCAL_P_MAX_LAG 15             /* M, as used                                                                            */
+#define GSMCAL_P_POS 16                                     /* [GSMCAL_MAX_PAIR_BURSTS] the burst's row of a's table, 1-based    */
+#define GSMCAL_P_DELAY (16 + GSMCAL_MAX_PAIR_BURSTS)        /* [..] lag0 + m* + the parabola's offset, samples                  */
+#define GSMCAL_P_PHASE (16 + 2 * GSMCAL_MAX_PAIR_BURSTS)    /* [..] phase of b against a at the burst's centre, rad             */
+#define GSMCAL_P_FREQ (16 + 3 * GSMCAL_MAX_PAIR_BURSTS)     /* [..] segment-to-segment phase step as a frequency, Hz            */
+#define GSMCAL_P_COH (16 + 4 * GSMCAL_MAX_PAIR_BURSTS)      /* [..] sum |c_k| / sqrt(sum Ea sum Eb), <= 1                       */
+#define GSMCAL_P_EDGE (16 + 5 * GSMCAL_MAX_PAIR_BURSTS)     /* [..] 1: the maximum sits at -M or +M (delay .. coherence NaN); 0 */
 
 /* ---- algorithm thresholds (the constants the reference hard-codes inside its functions) ---------- */
 /* Defaults = the reference's literals.  gsmcal_set_params() takes effect from the next call on (calls in flight finish with the
@@ -454,6 +481,31 @@ int gsmcal_SCH_decode(gsmcal_ctx* ctx, const double* s, long len, const double* 
 int gsmcal_BCCH_decode(gsmcal_ctx* ctx, const double* s, long len, const double* pos_info, int rows, int ld, int tsc,
                        int oversampling_ratio, unsigned char* octets, double* table_row, double* soft, gsmcal_si_info* first);
 
+/* pair_coherence(s_a, s_b, pos_info_a, ov, lag0, max_lag, min_coherence) -- the project's own function: the
+ * reference names the goal, dongles that "work together coherently", and has no code for it beyond a difference of integer burst
+ * positions (gsm_sync_demod.m:149-158).  How far apart two corrected streams are in time, to a fraction of a sample, and in carrier
+ * phase; how coherent they are; how fast they still drift.  ov 2, 4 or 8 (anything else GSMCAL_E_UNSUPPORTED); lag0: the expected
+ * offset of b's content against a's, samples; max_lag M, 1 <= M <= 4*ov (0 selects 2*ov); min_coherence in [0, 1].
+ * With L = 148*ov, Ls = 37*ov, fs = (1625e3/6)*ov, per type-1 or type-2 row of a's pos_info, in table order (1-based start pos,
+ * p = round(pos) - 1; FCCH rows are left out, a tone has no delay):
+ *   evaluated iff 0 <= p, p + L <= len_a, 0 <= p + lag0 - M and p + lag0 + M + L <= len_b (otherwise every column NaN, no error);
+ *   c[m][k] = sum_{n<Ls} b[p + lag0 + m + k*Ls + n] conj(a[p + k*Ls + n]) for m = -M..M, k = 0..3, Ea[k] and Eb[m][k] the energies
+ *   of the same samples;  y[m] = sum_k |c[m][k]|^2, m* its first maximum;  m* = -M or +M: edge = 1, the burst is not used;
+ *   delay = lag0 + m* + 0.5 (y[m*-1] - y[m*+1]) / (y[m*-1] - 2 y[m*] + y[m*+1]);
+ *   theta = arg sum_{k<3} c[m*][k+1] conj(c[m*][k]), freq = theta fs / (2 pi Ls) (unambiguous to +-fs/(2 Ls) = 3.66 kHz);
+ *   phase = arg sum_k c[m*][k] exp(-j theta (k - 1.5));  coherence = sum_k |c[m*][k]| / sqrt(sum Ea sum Eb[m*]) (NaN at 0 / 0).
+ * Per pair, over the used bursts (evaluated, not edge, coherence >= min_coherence), t = p - p of the first used burst: delay0,
+ * rel_sampling_ppm and delay_rms from the least-squares line of delay on t; burst_carrier_hz = mean freq; rel_carrier_hz refines it
+ * by the phase steps between consecutive used bursts at most 1875*ov samples apart (with none it equals burst_carrier_hz); phase0
+ * and phase_rms of the phases rotated back by rel_carrier_hz.  Fewer than two used bursts: GSMCAL_S_PAIR_FEW, the summaries NaN.
+ * Either stream empty or a pos_info all -1: GSMCAL_S_POST_NO_POS.  More than GSMCAL_MAX_PAIR_BURSTS rows: GSMCAL_E_CAPACITY.
+ * table_row (required): GSMCAL_PAIR_COLS doubles (GSMCAL_P_*), the row gsmcal_pair_coherence_batch writes for the pair.  corr (may
+ * be NULL): [GSMCAL_MAX_PAIR_BURSTS][2M+1][4] complex, c[m][k], NaN for bursts not evaluated.  gsmcal_last_call_report then returns
+ * the summary lines.  Returns the status. */
+int gsmcal_pair_coherence(gsmcal_ctx* ctx, const double* s_a, long len_a, const double* s_b, long len_b, const double* pos_info,
+                          int rows, int ld, int oversampling_ratio, int lag0, int max_lag, double min_coherence, double* table_row,
+                          double* corr);
+
 /* ppm_out = total_ppm_calculation(ppm_in)                           total_ppm_calculation.m:5-21
  * (pure host arithmetic; no context needed) */
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out);
@@ -694,6 +746,22 @@ int gsmcal_bcch_decode_batch(gsmcal_ctx* ctx, const double* r, long stride, cons
 int gsmcal_bcch_decode_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
                                  int d, int oversampling_ratio, const int* tsc, double* d_out, unsigned char* d_octets,
                                  double* d_soft);
+
+/* pair_coherence for P pairs of D streams, on the same inputs as gsmcal_sch_decode_batch[_dev].  pairs (host): [P][2] stream indices
+ * (a, b), each in [0, D): anything else GSMCAL_E_ARG, decided before anything is enqueued; lag0 (host): [P].  The bursts of a pair are
+ * the rows of a's table.  out: [P][GSMCAL_PAIR_COLS], row = {status, num_bursts, num_eval, num_used, num_adjacent, lag0, delay0,
+ * rel_sampling_ppm, delay_rms, rel_carrier_hz, burst_carrier_hz, phase0, phase_rms, mean_coherence, min_coherence_seen, max_lag,
+ * pos[], delay[], phase[], freq[], coherence[], edge[]} (GSMCAL_P_*), as gsmcal_pair_coherence defines them; per-row outcomes go in
+ * the status column.  corr (NULL to skip): [P][GSMCAL_MAX_PAIR_BURSTS][2M+1][4] complex.  A row is bit-identical alone, at any
+ * position of a batch of any size, from call to call, and equal to what gsmcal_pair_coherence returns.  _dev: device pointers (pairs
+ * and lag0 stay host arrays), only enqueues on the context's stream; the lanes and every answer about the calibrate / scan call
+ * before stay untouched. */
+int gsmcal_pair_coherence_batch(gsmcal_ctx* ctx, const double* r, long stride, const long* r_len, const double* pos_info, int d,
+                                int oversampling_ratio, const int* pairs, const int* lag0, int num_pairs, int max_lag,
+                                double min_coherence, double* out, double* corr);
+int gsmcal_pair_coherence_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
+                                    int d, int oversampling_ratio, const int* pairs, const int* lag0, int num_pairs, int max_lag,
+                                    double min_coherence, double* d_out, double* d_corr);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,

@@ -7,7 +7,7 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode BCCH_decode CW_check IQ_imbalance total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
+ *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode BCCH_decode CW_check IQ_imbalance pair_coherence total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
  *            gsmcal_band_power gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
@@ -393,6 +393,37 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         plhs[3] = mxCreateDoubleMatrix(1, GSMCAL_IQ_COLS, mxREAL);
         for (k = 0; k < GSMCAL_IQ_COLS; ++k) REAL_PTR(plhs[3])[k] = row[k];
     }
+
+#elif defined(GSMCAL_FN_pair_coherence)
+    /* [delay0, rel_carrier_hz, phase0, mean_coherence, rel_sampling_ppm, row] = pair_coherence(s_a, s_b, pos_info_a, ov, lag0, max_lag,
+     * min_coherence): the project's own function (include/gsmcal.h), no .m file of the reference exists for it.  The delay of b
+     * against a in samples, their carrier difference in Hz and phase in rad at the first used burst, the mean coherence, the drift of
+     * the delay in ppm (NaN when fewer than two bursts are used or pos_info == -1) and the whole 1 x GSMCAL_PAIR_COLS row (columns:
+     * GSMCAL_P_*).  lag0 defaults to 0, max_lag to 2*ov, min_coherence to 0.5.  Prints the report lines. */
+    mwSize na = 0, nb = 0, k;
+    const double *sa, *sb;
+    int rows, rc;
+    double* row;
+    if (nrhs < 4) mexErrMsgIdAndTxt("gsmcal:args", "usage: [delay0, rel_carrier_hz, phase0, mean_coherence, rel_sampling_ppm, row] = pair_coherence(s_a, s_b, pos_info_a, ov, lag0, max_lag, min_coherence)");
+    sa = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &na) : NULL;
+    sb = mxGetNumberOfElements(prhs[1]) > 1 ? cplx_in(prhs[1], &nb) : NULL;
+    rows = (int)mxGetM(prhs[2]);
+    row = (double*)mxCalloc(GSMCAL_PAIR_COLS, sizeof(double));
+    rc = gsmcal_pair_coherence(ctx(), sa, (long)na, sb, (long)nb, REAL_PTR(prhs[2]), rows, rows, (int)mxGetScalar(prhs[3]),
+                               nrhs > 4 ? (int)mxGetScalar(prhs[4]) : 0, nrhs > 5 ? (int)mxGetScalar(prhs[5]) : 0,
+                               nrhs > 6 ? mxGetScalar(prhs[6]) : 0.5, row, NULL);
+    chk(rc, "pair_coherence");
+    say();
+    plhs[0] = scalar(row[GSMCAL_P_DELAY0]);
+    if (nlhs > 1) plhs[1] = scalar(row[GSMCAL_P_REL_CARRIER_HZ]);
+    if (nlhs > 2) plhs[2] = scalar(row[GSMCAL_P_PHASE0]);
+    if (nlhs > 3) plhs[3] = scalar(row[GSMCAL_P_MEAN_COHERENCE]);
+    if (nlhs > 4) plhs[4] = scalar(row[GSMCAL_P_REL_SAMPLING_PPM]);
+    if (nlhs > 5) {
+        plhs[5] = mxCreateDoubleMatrix(1, GSMCAL_PAIR_COLS, mxREAL);
+        for (k = 0; k < GSMCAL_PAIR_COLS; ++k) REAL_PTR(plhs[5])[k] = row[k];
+    }
+    mxFree(row);
 
 #elif defined(GSMCAL_FN_total_ppm_calculation)
     /* ppm_out = total_ppm_calculation(ppm_in) */

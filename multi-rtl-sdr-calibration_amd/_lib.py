@@ -34,6 +34,9 @@ S_SCH_NO_DECODE = 14
 SI_COLS = 4 + 7 * MAX_HITS         # one row of bcch_decode_batch: four scalars (api.SI_FIELDS), then ok[], pos[], corrected[], ts_err[], steal[], mean_slope[], amp[]
 S_BCCH_NO_DECODE = 15
 BLOCK_OCTETS, BLOCK_CODED = 23, 456  # octets and coded bits of one BCCH block
+MAX_PAIR_BURSTS = MAX_HITS + MAX_BCCH   # type-1 and type-2 rows per stream pair_coherence_batch evaluates (GSMCAL_MAX_PAIR_BURSTS)
+PAIR_COLS = 16 + 6 * MAX_PAIR_BURSTS    # one row of pair_coherence_batch: sixteen scalars (api.PAIR_FIELDS), then pos[], delay[], phase[], freq[], coherence[], edge[]
+S_PAIR_FEW = 16
 HYPERFRAME = 2715648               # TDMA frames per GSM hyperframe: frame numbers wrap here
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
@@ -100,6 +103,12 @@ SIGNATURES = {
                                            c_double_p, c_u8_p, c_double_p]),
     "gsmcal_bcch_decode_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsmcal_pair_coherence": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_double_p, C.c_long, c_double_p, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_double, c_double_p, c_double_p]),
+    "gsmcal_pair_coherence_batch": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_long_p, c_double_p, C.c_int, C.c_int, c_int_p,
+                                              c_int_p, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p]),
+    "gsmcal_pair_coherence_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p,
+                                                  c_int_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "gsmcal_total_ppm_calculation": (C.c_int, [c_double_p, C.c_int, c_double_p]),
     "gsmcal_frontend_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                         c_double_p]),

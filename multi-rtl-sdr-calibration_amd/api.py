@@ -18,7 +18,8 @@ sentinel returns (scalar -1.0 / inf, pos_info = [[-1, -1]]) so that tests read l
     [idx,r,carrier_ppm] = BCCH_demod(s,pos_info,normal_training_sequence,ov,carrier_freq)     BCCH_demod.m:5 (a dict)
     ppm_out = total_ppm_calculation(ppm_in)
 and, without a counterpart in the reference (its SCH_demod.m returns nothing, its BCCH_demod.m stops at the training sequence index):
-SCH_decode(s,pos_info,sch_training_sequence,ov) and BCCH_decode(s,pos_info,tsc,ov); and IQ_imbalance(s) / iq_correct(s,gain,sin_phase)
+SCH_decode(s,pos_info,sch_training_sequence,ov) and BCCH_decode(s,pos_info,tsc,ov); pair_coherence(s_a,s_b,pos_info_a,ov,lag0)
+for the goal its README names, dongles that work together coherently; and IQ_imbalance(s) / iq_correct(s,gain,sin_phase)
 for the I/Q imbalance its TODO item 4.5 asks about.
 
 Everything computes on the GPU through the C ABI; there is no CPU fallback.
@@ -32,7 +33,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, PAIR_COLS, MAX_PAIR_BURSTS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -970,6 +971,109 @@ def bcch_decode_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_rati
                                                    int(d), int(oversampling_ratio), codes.ctypes.data_as(_lib.c_int_p),
                                                    C.c_void_p(d_out), C.c_void_p(d_octets), _opt(d_soft)),
               "bcch_decode_batch_dev")
+
+
+PAIR_FIELDS = ("status", "num_bursts", "num_eval", "num_used", "num_adjacent", "lag0", "delay0", "rel_sampling_ppm", "delay_rms",
+               "rel_carrier_hz", "burst_carrier_hz", "phase0", "phase_rms", "mean_coherence", "min_coherence_seen", "max_lag")   # columns 0..15
+PAIR_BURST_FIELDS = ("pos", "delay", "phase", "freq", "coherence", "edge")
+
+
+def pair_rows(table):
+    """(P, PAIR_COLS) table of pair_coherence_batch[_dev] -> dict of its columns (pos, delay, phase, freq, coherence, edge:
+    (P, MAX_PAIR_BURSTS), NaN for unused entries and for bursts that were not evaluated)."""
+    return _table_rows(table, PAIR_COLS, PAIR_FIELDS, PAIR_BURST_FIELDS, MAX_PAIR_BURSTS)
+
+
+def pair_lag0(sch_table_or_rows, pairs, oversampling_ratio):
+    """The expected offset of b's content against a's for every pair (a, b), from an SCH_decode table (or sch_rows' dict):
+    round(alignment[b] - alignment[a]) of sch_alignment -> (P,) int32.  Raises ValueError where a stream of a pair has no
+    alignment (its SCH bursts did not decode)."""
+    al = sch_alignment(sch_table_or_rows, oversampling_ratio)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    diff = al[pr[:, 1]] - al[pr[:, 0]]
+    if np.isnan(diff).any():
+        raise ValueError("pair_lag0: a stream of a pair has no SCH alignment")
+    return (np.sign(diff) * np.floor(np.abs(diff) + 0.5)).astype(np.int32)
+
+
+def _pairs_in(pairs, lag0, d):
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    lg = np.asarray(lag0, dtype=np.int32).ravel()
+    lg = np.ascontiguousarray(np.broadcast_to(lg, (len(pr),)) if lg.size == 1 else lg)
+    if len(pr) < 1 or len(lg) != len(pr):
+        raise ValueError("pairs must be (P, 2) stream indices with one lag0 per pair")
+    return pr, lg, len(pr)
+
+
+def _max_lag_in(max_lag, oversampling_ratio):
+    return 2 * int(oversampling_ratio) if max_lag is None else int(max_lag)
+
+
+def pair_coherence(s_a, s_b, pos_info, oversampling_ratio, lag0=0, max_lag=None, min_coherence=0.5, ctx=None, want_corr=False):
+    """pair_coherence(s_a, s_b, pos_info_a, ov, lag0) -- the project's own function (include/gsmcal.h): the
+    delay of stream b against stream a to a fraction of a sample, their carrier phase and frequency difference, their coherence
+    and the drift of the delay, measured on the SCH and BCCH bursts of a's pos_info.  lag0: the expected offset of b's content
+    against a's (pair_lag0); max_lag M in 1..4*ov (default 2*ov); ov 2, 4 or 8.  Returns None when pos_info is all -1, otherwise a
+    dict: the PAIR_FIELDS as scalars (`status` 0, or 16 = fewer than two used bursts), per burst `pos`, `delay`, `phase`, `freq`,
+    `coherence`, `edge` (NaN for a burst that was not evaluated), with want_corr `corr` (num_bursts, 2M+1, 4) complex; `row` is the
+    (PAIR_COLS,) table row pair_coherence_batch holds for this pair."""
+    ctx = ctx or default_context()
+    ba, na = _r_in(s_a)
+    bb, nb = _r_in(s_b)
+    pi, rows, pic = _pos_info_in(pos_info)
+    m = _max_lag_in(max_lag, oversampling_ratio)
+    row = np.full(PAIR_COLS, np.nan)
+    corr = np.empty((MAX_PAIR_BURSTS, 2 * max(m, 0) + 1, 4), dtype=np.complex128) if want_corr else None
+    rc = ctx.check(ctx.lib.gsmcal_pair_coherence(ctx.h, _dp(ba) if ba is not None else None, na, _dp(bb) if bb is not None else None, nb,
+                                                 _dp(pic), rows, rows, int(oversampling_ratio), int(lag0), m, float(min_coherence),
+                                                 _dp(row), _dp(corr) if want_corr else None), "pair_coherence")
+    _say(ctx)
+    if rc == _lib.S_POST_NO_POS:
+        return None
+    t = pair_rows(row)
+    k = min(int(t["num_bursts"][0]), MAX_PAIR_BURSTS) if rc >= 0 else 0
+    out = {name: (int(t[name][0]) if name in ("status", "num_bursts", "num_eval", "num_used", "num_adjacent", "lag0", "max_lag")
+                  else float(t[name][0])) for name in PAIR_FIELDS}
+    for name in PAIR_BURST_FIELDS:
+        out[name] = t[name][0, :k].copy()
+    out["row"] = row
+    if want_corr:
+        out["corr"] = corr[:k].copy()
+    return out
+
+
+def pair_coherence_batch(r_correct, r_len, pos_info_raw, oversampling_ratio, pairs, lag0, max_lag=None, min_coherence=0.5, ctx=None,
+                         want_corr=False):
+    """pair_coherence for P pairs of D streams, on what calibrate_batch(..., want_r=True) returns (as sch_decode_batch).  pairs:
+    (P, 2) stream indices (a, b); the bursts of a pair are the rows of a's table.  lag0: one int or one per pair (pair_lag0).
+    Returns the (P, PAIR_COLS) table (pair_rows names its columns; per-row outcomes are in its status column) -- or, with
+    want_corr, a dict: "table", "corr" (P, MAX_PAIR_BURSTS, 2M+1, 4) complex, NaN where no burst was evaluated."""
+    ctx = ctx or default_context()
+    r, d, stride, rl, pi = _post_batch_in(r_correct, r_len, pos_info_raw)
+    pr, lg, npairs = _pairs_in(pairs, lag0, d)
+    m = _max_lag_in(max_lag, oversampling_ratio)
+    out = np.empty((npairs, PAIR_COLS))
+    corr = np.empty((npairs, MAX_PAIR_BURSTS, 2 * max(m, 0) + 1, 4), dtype=np.complex128) if want_corr else None
+    ctx.check(ctx.lib.gsmcal_pair_coherence_batch(ctx.h, _dp(r), stride, rl.ctypes.data_as(_lib.c_long_p), _dp(pi), d,
+                                                  int(oversampling_ratio), pr.ctypes.data_as(_lib.c_int_p),
+                                                  lg.ctypes.data_as(_lib.c_int_p), npairs, m, float(min_coherence), _dp(out),
+                                                  _dp(corr) if want_corr else None), "pair_coherence_batch")
+    if not want_corr:
+        return out
+    return {"table": out, "corr": corr}
+
+
+def pair_coherence_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_ratio, pairs, lag0, d_out, max_lag=None,
+                             min_coherence=0.5, d_corr=None, ctx=None):
+    """Device-pointer form of pair_coherence_batch: only enqueues on the context's stream, e.g. directly behind calibrate_batch_dev on
+    its d_r_correct / d_r_len / d_pos_info (ctx.sync() before reading).  pairs, lag0: host arrays.  d_out: [P][PAIR_COLS] doubles;
+    optional d_corr: [P][MAX_PAIR_BURSTS][2M+1][4] complex.  Device or pinned host memory."""
+    ctx = ctx or default_context()
+    pr, lg, npairs = _pairs_in(pairs, lag0, int(d))
+    ctx.check(ctx.lib.gsmcal_pair_coherence_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), C.c_void_p(d_pos_info),
+                                                      int(d), int(oversampling_ratio), pr.ctypes.data_as(_lib.c_int_p),
+                                                      lg.ctypes.data_as(_lib.c_int_p), npairs, _max_lag_in(max_lag, oversampling_ratio),
+                                                      float(min_coherence), C.c_void_p(d_out), _opt(d_corr)), "pair_coherence_batch_dev")
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

@@ -1048,6 +1048,88 @@ int gsmcal_BCCH_decode(gsmcal_ctx* c, const double* s, long len, const double* p
     return status;
 }
 
+// ---- pair_coherence: delay, phase and drift between two corrected streams -------------------------------
+// k_pair_xcorr (one workgroup per burst slot and pair, one wave per segment) + k_pair_finish (one wave per pair), in pc_part.
+static int pair_coherence_args(gsmcal_ctx* c, int d, int ov, const int* pairs, const int* lag0, int P, int* max_lag, double min_coh) {
+    if (!pairs || !lag0 || P < 1) return GSMCAL_E_ARG;
+    if (ov != 2 && ov != 4 && ov != 8) { c->err = "pair_coherence: oversampling ratios 2, 4 and 8 only"; return GSMCAL_E_UNSUPPORTED; }
+    if (*max_lag == 0) *max_lag = 2 * ov;
+    if (*max_lag < 1 || *max_lag > 4 * ov) { c->err = "pair_coherence: max_lag must be 1 .. 4*oversampling_ratio"; return GSMCAL_E_ARG; }
+    if (!(min_coh >= 0.0 && min_coh <= 1.0)) { c->err = "pair_coherence: min_coherence must be in [0, 1]"; return GSMCAL_E_ARG; }
+    for (int i = 0; i < 2 * P; ++i)
+        if (pairs[i] < 0 || pairs[i] >= d) { c->err = "pair_coherence: a pair names a stream outside the batch"; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+int gsmcal_pair_coherence_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info, int d,
+                                    int ov, const int* pairs, const int* lag0, int P, int max_lag, double min_coh, double* d_out,
+                                    double* d_corr) {
+    if (!post_args_ok(c, d_r, d_r_len, d_pos_info, d_out, d, stride)) return GSMCAL_E_ARG;
+    RET_IF(pair_coherence_args(c, d, ov, pairs, lag0, P, &max_lag, min_coh));
+    ENTER_ON_CTX_STREAM(c);
+    std::vector<int> rec((size_t)3 * P);
+    for (int i = 0; i < P; ++i) { rec[3 * i] = pairs[2 * i]; rec[3 * i + 1] = pairs[2 * i + 1]; rec[3 * i + 2] = lag0[i]; }
+    RET_IF(upload_if_changed(c, c->pc_pairs, c->h_pc_pairs, rec.data(), rec.size(), "pair_coherence pairs"));
+    RET_IF(ensure(c, c->pc_part, (size_t)P * PX_SLOTS * PX_PART * sizeof(double)));
+    const int* d_pairs = (const int*)c->pc_pairs.p;
+    double* part = (double*)c->pc_part.p;
+    const size_t lds = px_lds_bytes(ov, max_lag), nl = (size_t)2 * max_lag + 1;
+    for_capture_chunks(P, [&](long lo, int S) {
+        LAUNCH(c, k_pair_xcorr, dim3(PX_SLOTS, S), dim3(PX_THREADS), lds, (const cplx*)d_r, stride, d_r_len, d_pos_info, ov, max_lag,
+               d_pairs + (size_t)lo * 3, part + (size_t)lo * PX_SLOTS * PX_PART,
+               d_corr ? (cplx*)d_corr + (size_t)lo * PX_SLOTS * nl * PX_K : nullptr);
+    });
+    LAUNCH(c, k_pair_finish, dim3(P), dim3(64), 0, d_r_len, stride, d_pos_info, ov, max_lag, min_coh, d_pairs, (const double*)part, d_out);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_pair_coherence_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, const double* pos_info, int d, int ov,
+                                const int* pairs, const int* lag0, int P, int max_lag, double min_coh, double* out, double* corr) {
+    if (!post_args_ok(c, r, r_len, pos_info, out, d, stride)) return GSMCAL_E_ARG;
+    RET_IF(pair_coherence_args(c, d, ov, pairs, lag0, P, &max_lag, min_coh));
+    ENTER(c);
+    const Stage io[] = {POST_STAGES_IN,
+                        STAGE(pc_out, (size_t)P * GSMCAL_PAIR_COLS * sizeof(double), nullptr, out, 0),
+                        STAGE(pc_corr, corr ? (size_t)P * PX_SLOTS * (2 * max_lag + 1) * PX_K * sizeof(cplx) : 0, nullptr, corr, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_pair_coherence_batch_dev(c, POST_STAGED_IN, d, ov, pairs, lag0, P, max_lag, min_coh, (double*)c->pc_out.p,
+                                           corr ? (double*)c->pc_corr.p : nullptr));
+    return stage_down(c, io);
+}
+
+int gsmcal_pair_coherence(gsmcal_ctx* c, const double* s_a, long len_a, const double* s_b, long len_b, const double* pos_info, int rows,
+                          int ld, int ov, int lag0, int max_lag, double min_coh, double* table_row, double* corr) {
+    if (!c || !pos_info || !table_row || rows < 1 || ld < rows) return GSMCAL_E_ARG;
+    const int pair[2] = {0, 1};
+    RET_IF(pair_coherence_args(c, 2, ov, pair, &lag0, 1, &max_lag, min_coh));
+    ENTER(c);
+    c->report.clear();
+    if (pos_info_all_m1(pos_info, rows, ld)) {                  // nothing to read: the batch form's row for such a pair
+        std::fill(table_row, table_row + GSMCAL_PAIR_COLS, NAN);
+        table_row[GSMCAL_P_NUM_BURSTS] = table_row[GSMCAL_P_NUM_EVAL] = table_row[GSMCAL_P_NUM_USED] = table_row[GSMCAL_P_NUM_ADJACENT] = 0.0;
+        table_row[GSMCAL_P_LAG0] = (double)lag0;
+        table_row[GSMCAL_P_MAX_LAG] = (double)max_lag;
+        table_row[GSMCAL_P_STATUS] = GSMCAL_S_POST_NO_POS;
+        if (corr) std::fill(corr, corr + (size_t)PX_SLOTS * (2 * max_lag + 1) * PX_K * 2, NAN);
+        return GSMCAL_S_POST_NO_POS;
+    }
+    if (!s_a || !s_b || len_a < 1 || len_b < 1) return GSMCAL_E_ARG;
+    if (rows > MAXROWS) return GSMCAL_E_CAPACITY;
+    const long stride = std::max(len_a, len_b);                 // the two streams as one batch: a is stream 0, b stream 1 with no table
+    std::vector<double> r((size_t)2 * stride * 2, 0.0);
+    memcpy(r.data(), s_a, (size_t)len_a * sizeof(cplx));
+    memcpy(r.data() + (size_t)stride * 2, s_b, (size_t)len_b * sizeof(cplx));
+    const long r_len[2] = {len_a, len_b};
+    std::vector<double> pi = pos_info_padded(pos_info, rows, ld);
+    pi.resize((size_t)2 * 2 * MAXROWS, -1.0);
+    RET_IF(gsmcal_pair_coherence_batch(c, r.data(), stride, r_len, pi.data(), 2, ov, pair, &lag0, 1, max_lag, min_coh, table_row, corr));
+    const int status = (int)table_row[GSMCAL_P_STATUS];
+    if (status < 0) return status;
+    c->report = report_pair_coherence(table_row);
+    return status;
+}
+
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out) {
     if (!ppm_in || !ppm_out || n < 1) return GSMCAL_E_ARG;

@@ -186,4 +186,20 @@ std::string report_iq_imbalance(const double* row) {
            rep_num2str(row[GSMCAL_Q_IRR_DB]) + " dB DC " + rep_num2str(row + GSMCAL_Q_DC_I, 2) + "\n";
 }
 
+// gsmcal_pair_coherence (the project's own lines).  row: one row of the pair_coherence table (GSMCAL_P_*), status 0 or
+// GSMCAL_S_PAIR_FEW.
+std::string report_pair_coherence(const double* row) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "pair bursts %d evaluated %d used %d adjacent %d\n", (int)row[GSMCAL_P_NUM_BURSTS], (int)row[GSMCAL_P_NUM_EVAL],
+             (int)row[GSMCAL_P_NUM_USED], (int)row[GSMCAL_P_NUM_ADJACENT]);
+    std::string r = buf;
+    if ((int)row[GSMCAL_P_STATUS] != 0) return r + "Fewer than two bursts to compare the streams on.\n";
+    r += "pair delay " + rep_num2str(row[GSMCAL_P_DELAY0]) + " samples drift " + rep_num2str(row[GSMCAL_P_REL_SAMPLING_PPM]) + " ppm rms " +
+         rep_num2str(row[GSMCAL_P_DELAY_RMS]) + "\n";
+    r += "pair carrier " + rep_num2str(row[GSMCAL_P_REL_CARRIER_HZ]) + " Hz phase " + rep_num2str(row[GSMCAL_P_PHASE0]) + " rad rms " +
+         rep_num2str(row[GSMCAL_P_PHASE_RMS]) + "\n";
+    r += "pair coherence mean " + rep_num2str(row[GSMCAL_P_MEAN_COHERENCE]) + " min " + rep_num2str(row[GSMCAL_P_MIN_COHERENCE_SEEN]) + "\n";
+    return r;
+}
+
 }  // namespace

@@ -73,10 +73,14 @@ struct CtxBufs {
     // I/Q imbalance check (gsmcal_IQ_imbalance, gsmcal_iq_imbalance_batch*, gsmcal_iq_correct).  iq_part: one record per (capture,
     // tile); iq_in: the complex streams of the host forms; iq_par: {gain, sin_phase} per stream of gsmcal_iq_correct
     DevBuf iq_part, iq_in, iq_par;
+    // pair_coherence (gsmcal_pair_coherence, gsmcal_pair_coherence_batch*): {a, b, lag0} per pair, the per-burst records, and the host
+    // wrapper's staging of the table and the correlations (its inputs go through fd_in / fd_len / fd_pos)
+    DevBuf pc_pairs, pc_part, pc_out, pc_corr;
     ALL_BUFS(CtxBufs, &coef, &ts, &cf, &table, &snrhit, &arr_in, &arr_out, &posinfo, &rlen, &misc, &tw, &csum_head, &tw_sch, &stage_raw,
              &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &bc_ts, &bc_corr, &bc_flag, &bc_out,
              &bc_corr_out, &bc_r, &bc_rlen, &sd_part, &sd_out, &sd_soft, &sd_u, &bd_part, &bd_tsc, &bd_out, &bd_oct, &bd_soft, &sb_taps, &sb_idx,
-             &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r, &iq_part, &iq_in, &iq_par)
+             &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r, &iq_part, &iq_in, &iq_par, &pc_pairs, &pc_part,
+             &pc_out, &pc_corr)
 };
 
 struct gsmcal_ctx : CtxBufs {
@@ -188,7 +192,7 @@ struct gsmcal_ctx : CtxBufs {
     std::vector<double> h_coef, h_ts, h_cf;   // host copies: upload only when changed
     // host copies of the add-on caches (upload_if_changed); h_sb_coef / h_sb_w: what the rows in sb_taps were built from
     std::vector<double> h_bp_coef, h_fd_cf, h_bc_ts, h_sb_coef, h_sb_w, h_sb_rows, h_iq_par;
-    std::vector<int> h_sb_idx, h_bd_tsc;
+    std::vector<int> h_sb_idx, h_bd_tsc, h_pc_pairs;
     int fd_tw_n = 0;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream

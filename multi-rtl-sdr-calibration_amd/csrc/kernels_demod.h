@@ -148,6 +148,9 @@ template <int T>
 struct PosType {                                 // pos_info(i, 2) == T: 0 FCCH, 1 SCH, 2 BCCH
     __device__ bool operator()(int i, const double* pi) const { return pi[MAXROWS + i] == (double)T; }
 };
+struct PosBurst {                                // a burst with content to correlate: SCH or BCCH (an FCCH tone has no delay)
+    __device__ bool operator()(int i, const double* pi) const { return pi[MAXROWS + i] == 1.0 || pi[MAXROWS + i] == 2.0; }
+};
 struct PosBlock {                                // a BCCH block: type 1, and type 2 in the four rows behind it
     __device__ bool operator()(int i, const double* pi) const {
         bool isb = i + 4 < MAXROWS && pi[MAXROWS + i] == 1.0;

@@ -451,6 +451,8 @@ def make_stream(dongle=0, arfcn=0, num_frames=102, seed=DEFAULT_SEED, bcch=True,
     """One capture: returns (raw uint8 interleaved I,Q of length 2*num_frames*10000, truth dict).
     tx_key: dongles given the same key receive the SAME transmission (payload, multiframe phase, start instant) through
     their own clocks, carrier offsets and noise -- what gsm_sync_demod.m's inter-dongle phase plot (:151-158) looks at.
+    With tx_key, a start_frame or frac_start left at None is drawn from the transmission's generator BEFORE the payload: two
+    dongles share the payload only when both leave the argument at None or both give it (pair_coherence needs the same payload).
     tsc: the cell's training sequence code (0..7), planted in every normal burst.
     bsic / fn0: the SCH payload (ideal_waveform): the cell's BSIC and the GSM frame number of the waveform's first frame, which
     needs start_frame given with fn0 mod 51 == start_frame.  Left at None the SCH payload stays random and the capture is
