@@ -76,7 +76,7 @@ def as_out(tab, pos, rl, rc):
     if rc is not None:
         r = rc.cpu().numpy()
         r = r[..., 0] + 1j * r[..., 1]
-    return {"table": table, "pos_info": rows, "r_len": rl.cpu().numpy(), "r_correct": r}
+    return {"table": table, "pos_info": rows, "pos_info_raw": p, "r_len": rl.cpu().numpy(), "r_correct": r}
 
 
 def run_dev(g, raw, coef, ts, env=None, calls=1, depth=1, with_r=True, profile=False):
