@@ -54,6 +54,7 @@ enum {
     GSMCAL_S_SCH_NO_DECODE = 14,  /* gsmcal_SCH_decode: fewer than two SCH bursts decode consistently */
     GSMCAL_S_BCCH_NO_DECODE = 15, /* gsmcal_BCCH_decode: no BCCH block passes the Fire code's check   */
     GSMCAL_S_PAIR_FEW = 16,       /* gsmcal_pair_coherence: fewer than two bursts of the pair are used */
+    GSMCAL_S_ALIGN_SKIPPED = 17,  /* gsmcal_pair_align: a value of the member's parameter row is not finite */
     /* < 0: failures */
     GSMCAL_E_ARG = -1,
     GSMCAL_E_HIP = -2,
@@ -75,6 +76,10 @@ enum {
 #define GSMCAL_BLOCK_CODED 456                         /* coded bits of one BCCH block */
 #define GSMCAL_MAX_PAIR_BURSTS (GSMCAL_MAX_HITS + GSMCAL_MAX_BCCH)   /* type-1 and type-2 rows gsmcal_pair_coherence_batch evaluates: 120 */
 #define GSMCAL_PAIR_COLS (16 + 6 * GSMCAL_MAX_PAIR_BURSTS)           /* one row of gsmcal_pair_coherence_batch[_dev]: 736 doubles */
+#define GSMCAL_MAX_ALIGN_MEMBERS 64                    /* members of one gsmcal_pair_align_batch[_dev] call */
+#define GSMCAL_ALIGN_PARAMS 6                          /* one member's row: delay, slope_ppm, carrier_hz, phase, anchor, weight */
+#define GSMCAL_ALIGN_INFO_COLS 4                       /* one row of the info table of gsmcal_pair_align_batch[_dev] */
+#define GSMCAL_ALIGN_TAPS 16                           /* taps of the interpolator, k = -7 .. 8 */
 
 /* columns of one row of the calibration table (doubles; this row is what ranks all-gather) */
 enum {
@@ -172,6 +177,19 @@ enum {
 #define GSMCAL_P_FREQ (16 + 3 * GSMCAL_MAX_PAIR_BURSTS)     /* [..] segment-to-segment phase step as a frequency, Hz            */
 #define GSMCAL_P_COH (16 + 4 * GSMCAL_MAX_PAIR_BURSTS)      /* [..] sum |c_k| / sqrt(sum Ea sum Eb), <= 1                       */
 #define GSMCAL_P_EDGE (16 + 5 * GSMCAL_MAX_PAIR_BURSTS)     /* [..] 1: the maximum sits at -M or +M (delay .. coherence NaN); 0 */
+
+/* columns of one member's parameter row of pair_align (doubles) */
+#define GSMCAL_A_DELAY 0                /* position of output sample `anchor` in the member's stream minus anchor, samples        */
+#define GSMCAL_A_SLOPE_PPM 1            /* 1e6 * how much faster than the output index the position advances, |.| <= 1000          */
+#define GSMCAL_A_CARRIER_HZ 2           /* carrier to take out, Hz of the OUTPUT time base                                         */
+#define GSMCAL_A_PHASE 3                /* carrier phase to take out at output sample `anchor`, rad                                */
+#define GSMCAL_A_ANCHOR 4               /* output index the drift and the carrier are counted from                                 */
+#define GSMCAL_A_WEIGHT 5               /* the member's weight in the sum                                                          */
+/* columns of the info table of pair_align (doubles): rows 0 .. G-1 the members, row G the sum */
+#define GSMCAL_AI_STATUS 0              /* member: 0, GSMCAL_S_POST_NO_POS, GSMCAL_S_ALIGN_SKIPPED      sum: members with status 0  */
+#define GSMCAL_AI_FIRST_VALID 1         /* member: first valid output index (0 with none)               sum: the largest of them    */
+#define GSMCAL_AI_END_VALID 2           /* member: one past the last valid output index (0 with none)   sum: the smallest, >= first */
+#define GSMCAL_AI_NUM_VALID 3           /* member: end_valid - first_valid                              sum: sum of the used weights */
 
 /* ---- algorithm thresholds (the constants the reference hard-codes inside its functions) ---------- */
 /* Defaults = the reference's literals.  gsmcal_set_params() takes effect from the next call on (calls in flight finish with the
@@ -506,6 +524,37 @@ int gsmcal_pair_coherence(gsmcal_ctx* ctx, const double* s_a, long len_a, const 
                           int rows, int ld, int oversampling_ratio, int lag0, int max_lag, double min_coherence, double* table_row,
                           double* corr);
 
+/* pair_align(s, ov, params_row, out_len) -- the project's own function: what pair_coherence measures, this
+ * acts on.  One stream is resampled onto another dongle's time base by a fractional delay that may drift, and a carrier is taken out.
+ * ov 2, 4 or 8 (anything else GSMCAL_E_UNSUPPORTED), fs = (1625e3/6)*ov; params_row: GSMCAL_ALIGN_PARAMS doubles {delay, slope_ppm,
+ * carrier_hz, phase, anchor, weight} (GSMCAL_A_*), |slope_ppm| <= 1000 (beyond: GSMCAL_E_ARG); out_len >= 1.  For n = 0 .. out_len-1,
+ * in fp64, every operation rounded on its own:
+ *   x = (n + delay) + (slope_ppm*1e-6)*(n - anchor),  base = floor(x),  mu = x - base;
+ *   valid iff 0 <= base - 7 and base + 8 < len (decided before a sample is read);
+ *   out[n] = exp(-j (phase + (2 pi carrier_hz / fs) (n - anchor))) sum_{k=-7..8} h(k - mu) s[base + k] where valid, exactly 0 + 0j
+ *   where not;  h(u) = sinc(u) (0.42 + 0.5 cos(2 pi u/16) + 0.08 cos(4 pi u/16)), sinc(u) = sin(pi u)/(pi u), h(0) = 1 exactly.
+ * The window is zero at |u| = 8, so h is continuous: a floor() that lands on the other side of an integer x changes a sample by
+ * rounding only.  x increases with n, so the valid samples are one interval [first_valid, end_valid).
+ * info_row (required): GSMCAL_ALIGN_INFO_COLS doubles {status, first_valid, end_valid, num_valid} (GSMCAL_AI_*), 0 0 0 with no
+ * valid sample.  status (also the return value): 0; GSMCAL_S_POST_NO_POS: len < 1 (s may then be NULL); GSMCAL_S_ALIGN_SKIPPED: a
+ * value of params_row is not finite -- out is all zero in both cases.  out: out_len complex; it must not overlap s.
+ * gsmcal_last_call_report then returns the member's line. */
+int gsmcal_pair_align(gsmcal_ctx* ctx, const double* s, long len, int oversampling_ratio, const double* params_row, long out_len,
+                      double* out, double* info_row);
+
+/* One row of the pair_coherence table -> the parameter row that aligns stream b of that pair onto stream a (pure host arithmetic; no
+ * context needed).  pair_row: GSMCAL_PAIR_COLS doubles; min_coherence: the threshold the row was made with (the row does not carry
+ * it; it decides which burst is the first USED one: pos not NaN, edge 0, coherence >= min_coherence); weight: copied.  With
+ * L = 148*ov, s = 1e-6 rel_sampling_ppm, p0 = round(pos) - 1 of the first used burst:
+ *   anchor = p0 + (L-1)/2;  delay = delay0 + s (L-1)/2;  slope_ppm = rel_sampling_ppm;  carrier_hz = rel_carrier_hz (1 + s);
+ *   phase = phase0
+ * (pair_coherence's phase is that of b against a at the burst's centre IN b's INDEX, its delay0 sits at the burst's START: at output
+ * index n the position in b is n + delay0 + s (n - p0), and the carrier seen there, rel_carrier_hz per second of a's samples counted
+ * in b's index, turns (1 + s) times as fast per output sample).  A row whose status is not 0, or without a used burst: every value
+ * NaN but the weight (gsmcal_pair_align_batch then skips the member); returns GSMCAL_S_ALIGN_SKIPPED then, otherwise 0.  The
+ * reference stream itself is the row {0, 0, 0, 0, 0, weight}. */
+int gsmcal_pair_align_params(const double* pair_row, int oversampling_ratio, double min_coherence, double weight, double* params_row);
+
 /* ppm_out = total_ppm_calculation(ppm_in)                           total_ppm_calculation.m:5-21
  * (pure host arithmetic; no context needed) */
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out);
@@ -762,6 +811,29 @@ int gsmcal_pair_coherence_batch(gsmcal_ctx* ctx, const double* r, long stride, c
 int gsmcal_pair_coherence_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, const double* d_pos_info,
                                     int d, int oversampling_ratio, const int* pairs, const int* lag0, int num_pairs, int max_lag,
                                     double min_coherence, double* d_out, double* d_corr);
+
+/* pair_align for G members of D streams, (r, stride, r_len) as gsmcal_sch_decode_batch[_dev] takes them, and their weighted sum.
+ * members (host): [G] stream indices, each in [0, D); params (host): [G][GSMCAL_ALIGN_PARAMS], rows as gsmcal_pair_align defines
+ * them; 1 <= G <= GSMCAL_MAX_ALIGN_MEMBERS; a stream may be named more than once.  len of a member = min(r_len, stride) of its stream.
+ * aligned (may be NULL): [G][out_len] complex, row g = gsmcal_pair_align of member g.  combined (may be NULL, not both):
+ * [out_len] complex, combined[n] = sum_g weight_g aligned_g[n] in list order over the members valid at n (0 with none).
+ * info (required): [G + 1][GSMCAL_ALIGN_INFO_COLS]: member rows {status, first_valid, end_valid, num_valid}, then the sum's
+ * {members_used, combined_first, combined_end, sum of the used members' weights}: [combined_first, combined_end) is where every
+ * member with status 0 is valid (empty: end = first).  Per-member outcomes go in the status column and the call succeeds: a member
+ * with len < 1 (GSMCAL_S_POST_NO_POS) or with a value in its row that is not finite (GSMCAL_S_ALIGN_SKIPPED: the NaN summaries of a
+ * failed pair_coherence row pass straight through gsmcal_pair_align_params) has an all-zero aligned row and is left out of the sum.
+ * Decided before anything is enqueued: GSMCAL_E_ARG for a stream index outside [0, D), G outside 1 .. 64, out_len < 1,
+ * |slope_ppm| > 1000, both outputs NULL; GSMCAL_E_UNSUPPORTED for ov not in {2, 4, 8}.  An output that overlaps r is not supported.
+ * An aligned row is the same bits alone, at any place of any list, with or without `combined`, from call to call and from
+ * gsmcal_pair_align; combined is the same bits from call to call and between the two forms.  The host form leaves the report lines
+ * (one per member, one for the sum) with gsmcal_last_call_report.  _dev: device pointers (members and params stay host arrays), only
+ * enqueues on the context's stream; the lanes and every answer about the calibrate / scan call before stay untouched. */
+int gsmcal_pair_align_batch(gsmcal_ctx* ctx, const double* r, long stride, const long* r_len, int d, int oversampling_ratio,
+                            const int* members, const double* params, int G, long out_len, double* aligned, double* combined,
+                            double* info);
+int gsmcal_pair_align_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, int d, int oversampling_ratio,
+                                const int* members, const double* params, int G, long out_len, double* d_aligned, double* d_combined,
+                                double* d_info);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,

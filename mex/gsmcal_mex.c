@@ -7,7 +7,7 @@
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
  *            FCCH_coarse_position FCCH_fine_correction SCH_corr_rate_correction \
- *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode BCCH_decode CW_check IQ_imbalance pair_coherence total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
+ *            carrier_correct_post_SCH FCCH_demod BCCH_demod SCH_decode BCCH_decode CW_check IQ_imbalance pair_coherence pair_align total_ppm_calculation gsmcal_calibrate gsmcal_fcch_scan \
  *            gsmcal_band_power gsmcal_subband_power; do
  *     mex -R2018a -DGSMCAL_FN_$f -output $f mex/gsmcal_mex.c -Iinclude -Lmulti-rtl-sdr-calibration_amd/lib -lgsmcal
  *   done
@@ -424,6 +424,32 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (k = 0; k < GSMCAL_PAIR_COLS; ++k) REAL_PTR(plhs[5])[k] = row[k];
     }
     mxFree(row);
+
+#elif defined(GSMCAL_FN_pair_align)
+    /* [out, info] = pair_align(s, ov, params, out_len): the project's own function (include/gsmcal.h), no .m file of the reference
+     * exists for it.  s resampled at (n + delay) + 1e-6 slope_ppm (n - anchor) and turned by exp(-j (phase + 2 pi carrier_hz
+     * (n - anchor) / fs)), n = 0 .. out_len-1; params = [delay slope_ppm carrier_hz phase anchor weight] (the weight is not used
+     * here); out_len defaults to numel(s).  out: out_len x 1 complex, 0 where a tap would fall outside s; info = [status
+     * first_valid end_valid num_valid] (0-based, end exclusive).  Prints the report line. */
+    mwSize n = 0, k;
+    const double* s;
+    double info[GSMCAL_ALIGN_INFO_COLS];
+    double* out;
+    long out_len;
+    if (nrhs < 3 || mxGetNumberOfElements(prhs[2]) != GSMCAL_ALIGN_PARAMS)
+        mexErrMsgIdAndTxt("gsmcal:args", "usage: [out, info] = pair_align(s, ov, [delay slope_ppm carrier_hz phase anchor weight], out_len)");
+    s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    out_len = nrhs > 3 ? (long)mxGetScalar(prhs[3]) : (long)n;
+    if (out_len < 1) mexErrMsgIdAndTxt("gsmcal:args", "pair_align: out_len must be at least 1");
+    out = (double*)mxCalloc(2 * (size_t)out_len, sizeof(double));
+    chk(gsmcal_pair_align(ctx(), s, (long)n, (int)mxGetScalar(prhs[1]), REAL_PTR(prhs[2]), out_len, out, info), "pair_align");
+    say();
+    plhs[0] = cplx_col(out, (mwSize)out_len);
+    mxFree(out);
+    if (nlhs > 1) {
+        plhs[1] = mxCreateDoubleMatrix(1, GSMCAL_ALIGN_INFO_COLS, mxREAL);
+        for (k = 0; k < GSMCAL_ALIGN_INFO_COLS; ++k) REAL_PTR(plhs[1])[k] = info[k];
+    }
 
 #elif defined(GSMCAL_FN_total_ppm_calculation)
     /* ppm_out = total_ppm_calculation(ppm_in) */

@@ -37,6 +37,9 @@ BLOCK_OCTETS, BLOCK_CODED = 23, 456  # octets and coded bits of one BCCH block
 MAX_PAIR_BURSTS = MAX_HITS + MAX_BCCH   # type-1 and type-2 rows per stream pair_coherence_batch evaluates (GSMCAL_MAX_PAIR_BURSTS)
 PAIR_COLS = 16 + 6 * MAX_PAIR_BURSTS    # one row of pair_coherence_batch: sixteen scalars (api.PAIR_FIELDS), then pos[], delay[], phase[], freq[], coherence[], edge[]
 S_PAIR_FEW = 16
+MAX_ALIGN_MEMBERS = 64                  # members of one pair_align_batch call (GSMCAL_MAX_ALIGN_MEMBERS)
+ALIGN_PARAMS, ALIGN_INFO_COLS = 6, 4    # one member's parameter row (api.ALIGN_PARAM_FIELDS); one row of the info table (api.ALIGN_INFO_FIELDS)
+S_ALIGN_SKIPPED = 17
 HYPERFRAME = 2715648               # TDMA frames per GSM hyperframe: frame numbers wrap here
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
@@ -109,6 +112,12 @@ SIGNATURES = {
                                               c_int_p, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p]),
     "gsmcal_pair_coherence_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_int_p,
                                                   c_int_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "gsmcal_pair_align": (C.c_int, [C.c_void_p, c_double_p, C.c_long, C.c_int, c_double_p, C.c_long, c_double_p, c_double_p]),
+    "gsmcal_pair_align_params": (C.c_int, [c_double_p, C.c_int, C.c_double, C.c_double, c_double_p]),
+    "gsmcal_pair_align_batch": (C.c_int, [C.c_void_p, c_double_p, C.c_long, c_long_p, C.c_int, C.c_int, c_int_p, c_double_p, C.c_int,
+                                          C.c_long, c_double_p, c_double_p, c_double_p]),
+    "gsmcal_pair_align_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, C.c_int,
+                                              C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsmcal_total_ppm_calculation": (C.c_int, [c_double_p, C.c_int, c_double_p]),
     "gsmcal_frontend_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                         c_double_p]),

@@ -19,7 +19,8 @@ sentinel returns (scalar -1.0 / inf, pos_info = [[-1, -1]]) so that tests read l
     ppm_out = total_ppm_calculation(ppm_in)
 and, without a counterpart in the reference (its SCH_demod.m returns nothing, its BCCH_demod.m stops at the training sequence index):
 SCH_decode(s,pos_info,sch_training_sequence,ov) and BCCH_decode(s,pos_info,tsc,ov); pair_coherence(s_a,s_b,pos_info_a,ov,lag0)
-for the goal its README names, dongles that work together coherently; and IQ_imbalance(s) / iq_correct(s,gain,sin_phase)
+and pair_align(s,ov,params,out_len) / coherent_combine(...) for the goal its README names, dongles that work together coherently
+(measure how far apart two streams are; put them on one time base and add them up); and IQ_imbalance(s) / iq_correct(s,gain,sin_phase)
 for the I/Q imbalance its TODO item 4.5 asks about.
 
 Everything computes on the GPU through the C ABI; there is no CPU fallback.
@@ -33,7 +34,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, PAIR_COLS, MAX_PAIR_BURSTS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, PAIR_COLS, MAX_PAIR_BURSTS, ALIGN_PARAMS, ALIGN_INFO_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -1074,6 +1075,138 @@ def pair_coherence_batch_dev(d_r, stride, d_r_len, d_pos_info, d, oversampling_r
                                                       int(d), int(oversampling_ratio), pr.ctypes.data_as(_lib.c_int_p),
                                                       lg.ctypes.data_as(_lib.c_int_p), npairs, _max_lag_in(max_lag, oversampling_ratio),
                                                       float(min_coherence), C.c_void_p(d_out), _opt(d_corr)), "pair_coherence_batch_dev")
+
+
+ALIGN_PARAM_FIELDS = ("delay", "slope_ppm", "carrier_hz", "phase", "anchor", "weight")        # one member's row of pair_align_batch
+ALIGN_INFO_FIELDS = ("status", "first_valid", "end_valid", "num_valid")                     # one member's row of the info table
+ALIGN_SUM_FIELDS = ("members_used", "combined_first", "combined_end", "weight_sum")          # ... and its last row, for the sum
+
+
+def align_rows(info):
+    """(G + 1, ALIGN_INFO_COLS) info table of pair_align_batch[_dev] -> dict: the ALIGN_INFO_FIELDS as (G,) columns of the members
+    (status 0, 10 = the stream is empty, 17 = a parameter is not finite; [first_valid, end_valid) the output samples every tap of
+    which lies inside the stream) and the ALIGN_SUM_FIELDS as scalars of the sum ([combined_first, combined_end): where every member
+    with status 0 is valid)."""
+    t = np.asarray(info, dtype=np.float64).reshape(-1, ALIGN_INFO_COLS)
+    out = {k: t[:-1, i] for i, k in enumerate(ALIGN_INFO_FIELDS)}
+    out.update({k: (float(t[-1, i]) if k == "weight_sum" else int(t[-1, i])) for i, k in enumerate(ALIGN_SUM_FIELDS)})
+    return out
+
+
+def pair_align_params(pair_table, oversampling_ratio, weights=None, min_coherence=0.5):
+    """Rows of a pair_coherence table (pairs (a, b)) -> (P, ALIGN_PARAMS) parameter rows {delay, slope_ppm, carrier_hz, phase, anchor,
+    weight} that put stream b of each pair on stream a's time base and take its carrier out (gsmcal_pair_align_params; pure host
+    arithmetic, no context).  With L = 148 ov, s = 1e-6 rel_sampling_ppm and p0 = round(pos) - 1 of the first USED burst:
+        anchor = p0 + (L-1)/2,  delay = delay0 + s (L-1)/2,  slope_ppm = rel_sampling_ppm,
+        carrier_hz = rel_carrier_hz (1 + s),  phase = phase0.
+    Why: pair_coherence fits delay(t) = delay0 + s t with t counted from the START of the first used burst, so output sample n of
+    a's time base sits at n + delay0 + s (n - p0) in b -- which is (n + delay) + s (n - anchor) with the two values above.  Its
+    phase0 is the phase of b against a at that burst's CENTRE, the sample p0 + (L-1)/2 of a: the anchor.  Its rel_carrier_hz is
+    measured per sample of a as the burst is walked in b's index, and one output sample advances b's index by 1 + s: the carrier to
+    take out per output sample is (1 + s) times as large.
+    A burst is used when its pos is not NaN, its edge is 0 and its coherence >= min_coherence: the row does not carry the threshold
+    pair_coherence was run with, so it is an argument here (default 0.5, pair_coherence's own default) -- pass the same value.
+    weights: one per row (default 1 / (P + 1): equal gain for the P members and the reference stream, whose own row is
+    {0, 0, 0, 0, 0, w}).  A row whose status is not 0 gives NaN parameters; pair_align_batch then skips that member."""
+    lib = _lib.load()
+    tab = np.ascontiguousarray(np.asarray(pair_table, dtype=np.float64).reshape(-1, PAIR_COLS))
+    w = np.full(len(tab), 1.0 / (len(tab) + 1)) if weights is None else np.broadcast_to(np.asarray(weights, dtype=np.float64), (len(tab),))
+    out = np.empty((len(tab), ALIGN_PARAMS))
+    for i in range(len(tab)):
+        rc = lib.gsmcal_pair_align_params(_dp(tab[i]), int(oversampling_ratio), float(min_coherence), float(w[i]), _dp(out[i]))
+        if rc < 0:
+            raise GsmcalError(f"pair_align_params failed with {rc}")
+    return out
+
+
+def _members_in(members, params):
+    mb = np.ascontiguousarray(np.asarray(members, dtype=np.int32).ravel())
+    pr = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1, ALIGN_PARAMS))
+    if len(mb) != len(pr):
+        raise ValueError("one parameter row per member")
+    return mb, pr, len(mb)
+
+
+def pair_align(s, oversampling_ratio, params_row, out_len=None, ctx=None):
+    """pair_align(s, ov, params_row, out_len) -- the project's own function (include/gsmcal.h): stream s
+    resampled at x(n) = (n + delay) + 1e-6 slope_ppm (n - anchor) by a 16-tap Blackman-windowed sinc and turned by
+    exp(-j (phase + 2 pi carrier_hz (n - anchor) / fs)), n = 0 .. out_len-1 (default len(s)); samples a tap of which would fall
+    outside s are exactly 0.  ov 2, 4 or 8; |slope_ppm| <= 1000.  Returns (out, info): out (out_len,) complex, info a dict of the
+    ALIGN_INFO_FIELDS (status 0, 10 for an empty s, 17 for a parameter that is not finite)."""
+    ctx = ctx or default_context()
+    buf, n = _r_in(s)
+    out_len = n if out_len is None else int(out_len)
+    pr = np.ascontiguousarray(np.asarray(params_row, dtype=np.float64).ravel())
+    if len(pr) != ALIGN_PARAMS:
+        raise ValueError("params_row: delay, slope_ppm, carrier_hz, phase, anchor, weight")
+    out = np.empty(max(out_len, 0), dtype=np.complex128)
+    info = np.empty(ALIGN_INFO_COLS)
+    ctx.check(ctx.lib.gsmcal_pair_align(ctx.h, _dp(buf) if buf is not None else None, n, int(oversampling_ratio), _dp(pr), out_len,
+                                        _dp(out), _dp(info)), "pair_align")
+    _say(ctx)
+    return out, {k: int(info[i]) for i, k in enumerate(ALIGN_INFO_FIELDS)}
+
+
+def pair_align_batch(r_correct, r_len, oversampling_ratio, members, params, out_len=None, ctx=None, want_aligned=True, want_combined=True):
+    """pair_align for G members of D streams (r_correct, r_len as calibrate_batch(..., want_r=True) returns them) and their weighted
+    sum.  members: (G,) stream indices; params: (G, ALIGN_PARAMS) rows (pair_align_params; the reference stream is {0, 0, 0, 0, 0, w});
+    out_len defaults to the streams' row length.  Returns a dict: "aligned" (G, out_len) complex (with want_aligned), "combined"
+    (out_len,) complex = sum_g weight_g aligned_g in list order over the members valid at each sample (with want_combined), "info"
+    the (G + 1, ALIGN_INFO_COLS) table (align_rows names its columns; per-member outcomes are in its status column)."""
+    ctx = ctx or default_context()
+    r = np.ascontiguousarray(np.atleast_2d(np.asarray(r_correct, dtype=np.complex128)))
+    d, stride = r.shape
+    rl = np.ascontiguousarray(np.asarray(r_len, dtype=np.int64).ravel())
+    if len(rl) != d:
+        raise ValueError("r_len must have one entry per stream")
+    mb, pr, g = _members_in(members, params)
+    out_len = stride if out_len is None else int(out_len)
+    al = np.empty((g, max(out_len, 0)), dtype=np.complex128) if want_aligned else None
+    cb = np.empty(max(out_len, 0), dtype=np.complex128) if want_combined else None
+    info = np.empty((g + 1, ALIGN_INFO_COLS))
+    ctx.check(ctx.lib.gsmcal_pair_align_batch(ctx.h, _dp(r), stride, rl.ctypes.data_as(_lib.c_long_p), d, int(oversampling_ratio),
+                                              mb.ctypes.data_as(_lib.c_int_p), _dp(pr), g, out_len, _dp(al) if want_aligned else None,
+                                              _dp(cb) if want_combined else None, _dp(info)), "pair_align_batch")
+    out = {"info": info}
+    if want_aligned:
+        out["aligned"] = al
+    if want_combined:
+        out["combined"] = cb
+    return out
+
+
+def pair_align_batch_dev(d_r, stride, d_r_len, d, oversampling_ratio, members, params, out_len, d_info, d_aligned=None, d_combined=None,
+                         ctx=None):
+    """Device-pointer form of pair_align_batch: only enqueues on the context's stream (ctx.sync() before reading).  members, params:
+    host arrays.  d_info: [G + 1][ALIGN_INFO_COLS] doubles; d_aligned: [G][out_len] complex and d_combined: [out_len] complex, either
+    may be left out, not both; neither may overlap d_r.  Device or pinned host memory."""
+    ctx = ctx or default_context()
+    mb, pr, g = _members_in(members, params)
+    ctx.check(ctx.lib.gsmcal_pair_align_batch_dev(ctx.h, C.c_void_p(d_r), int(stride), C.c_void_p(d_r_len), int(d), int(oversampling_ratio),
+                                                  mb.ctypes.data_as(_lib.c_int_p), _dp(pr), g, int(out_len), _opt(d_aligned), _opt(d_combined),
+                                                  C.c_void_p(d_info)), "pair_align_batch_dev")
+
+
+def coherent_combine(r_correct, r_len, pos_info_raw, oversampling_ratio, sch_table, ref=0, members=None, max_lag=None, min_coherence=0.5,
+                     want_aligned=False, ctx=None):
+    """One stream out of several calibrated dongles on one cell: pair_lag0 -> pair_coherence_batch for the pairs (ref, m) ->
+    pair_align_params -> pair_align_batch, on what calibrate_batch(..., want_r=True) and sch_decode_batch returned.  members: the
+    streams to put on ref's time base (default: every other stream).  The sum has equal weights 1 / (1 + len(members)) and ref
+    itself as its first member; a member whose pair row has a status other than 0 is skipped (info says so).  Returns a dict:
+    "combined" (N,) complex, "info" (align_rows names its columns; row 0 is ref), "pair_table" (len(members), PAIR_COLS), "params"
+    (1 + len(members), ALIGN_PARAMS), "members" (ref first), with want_aligned "aligned" (1 + len(members), N).  The combined stream
+    has the shape the demod family takes: SCH_decode and the others read it with ref's pos_info."""
+    ctx = ctx or default_context()
+    r, d, stride, rl, pi = _post_batch_in(r_correct, r_len, pos_info_raw)
+    ms = [m for m in range(d) if m != ref] if members is None else [int(m) for m in members]
+    pairs = [(int(ref), m) for m in ms]
+    lag0 = pair_lag0(sch_table, pairs, oversampling_ratio)
+    table = pair_coherence_batch(r, rl, pi, oversampling_ratio, pairs, lag0, max_lag, min_coherence, ctx=ctx)
+    w = 1.0 / (1 + len(ms))
+    params = np.vstack([[0.0, 0.0, 0.0, 0.0, 0.0, w], pair_align_params(table, oversampling_ratio, w, min_coherence)])
+    out = pair_align_batch(r, rl, oversampling_ratio, [int(ref)] + ms, params, ctx=ctx, want_aligned=want_aligned)
+    out.update({"pair_table": table, "params": params, "members": np.array([int(ref)] + ms)})
+    return out
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

@@ -1130,6 +1130,97 @@ int gsmcal_pair_coherence(gsmcal_ctx* c, const double* s_a, long len_a, const do
     return status;
 }
 
+// ---- pair_align: streams onto one dongle's time base, their carrier taken out, and their sum ------------------
+// k_pair_align (one workgroup per tile of PA_TILE output samples; the members in list order when the sum is asked for, one member
+// per grid row otherwise) + k_pair_align_info (one wave: the members' valid intervals and the sum's row).
+static int pair_align_args(gsmcal_ctx* c, int d, int ov, const int* members, const double* params, int G, long out_len, const void* aligned,
+                           const void* combined) {
+    if (!members || !params || (!aligned && !combined)) return GSMCAL_E_ARG;
+    if (ov != 2 && ov != 4 && ov != 8) { c->err = "pair_align: oversampling ratios 2, 4 and 8 only"; return GSMCAL_E_UNSUPPORTED; }
+    if (G < 1 || G > GSMCAL_MAX_ALIGN_MEMBERS) { c->err = "pair_align: 1 .. 64 members"; return GSMCAL_E_ARG; }
+    if (out_len < 1) { c->err = "pair_align: out_len must be at least 1"; return GSMCAL_E_ARG; }
+    for (int g = 0; g < G; ++g) {
+        if (members[g] < 0 || members[g] >= d) { c->err = "pair_align: a member names a stream outside the batch"; return GSMCAL_E_ARG; }
+        if (fabs(params[(size_t)g * GSMCAL_ALIGN_PARAMS + GSMCAL_A_SLOPE_PPM]) > 1000.0) {       // (NaN passes: the member is skipped)
+            c->err = "pair_align: |slope_ppm| must be at most 1000";
+            return GSMCAL_E_ARG;
+        }
+    }
+    return 0;
+}
+
+int gsmcal_pair_align_batch_dev(gsmcal_ctx* c, const double* d_r, long stride, const long* d_r_len, int d, int ov, const int* members,
+                                const double* params, int G, long out_len, double* d_aligned, double* d_combined, double* d_info) {
+    if (!c || !d_r || !d_r_len || !d_info || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    RET_IF(pair_align_args(c, d, ov, members, params, G, out_len, d_aligned, d_combined));
+    ENTER_ON_CTX_STREAM(c);
+    RET_IF(upload_if_changed(c, c->pa_members, c->h_pa_members, members, (size_t)G, "pair_align members"));
+    RET_IF(upload_if_changed(c, c->pa_params, c->h_pa_params, params, (size_t)G * GSMCAL_ALIGN_PARAMS, "pair_align params"));
+    const int* d_members = (const int*)c->pa_members.p;
+    const double* d_params = (const double*)c->pa_params.p;
+    const long tiles = (out_len + PA_TILE - 1) / PA_TILE, per_launch = 1L << 30;                   // (grid.x holds 2^31 - 1)
+    for (long t = 0; t < tiles; t += per_launch)
+        LAUNCH(c, k_pair_align, dim3((unsigned)std::min(per_launch, tiles - t), d_combined ? 1 : G), dim3(PA_TILE), 0, (const cplx*)d_r, stride,
+               d_r_len, ov, d_members, d_params, G, out_len, t * PA_TILE, (cplx*)d_aligned, (cplx*)d_combined);
+    LAUNCH(c, k_pair_align_info, dim3(1), dim3(64), 0, d_r_len, stride, ov, d_members, d_params, G, out_len, d_info);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_pair_align_batch(gsmcal_ctx* c, const double* r, long stride, const long* r_len, int d, int ov, const int* members,
+                            const double* params, int G, long out_len, double* aligned, double* combined, double* info) {
+    if (!c || !r || !r_len || !info || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    RET_IF(pair_align_args(c, d, ov, members, params, G, out_len, aligned, combined));
+    ENTER(c);
+    c->report.clear();
+    const size_t row = (size_t)out_len * sizeof(cplx);
+    const Stage io[] = {STAGE(fd_in, (size_t)d * stride * sizeof(cplx), r, nullptr, 0),
+                        STAGE(fd_len, (size_t)d * sizeof(long), r_len, nullptr, 0),
+                        STAGE(pa_aligned, aligned ? (size_t)G * row : 0, nullptr, aligned, 0),
+                        STAGE(pa_combined, combined ? row : 0, nullptr, combined, 0),
+                        STAGE(pa_info, (size_t)(G + 1) * GSMCAL_ALIGN_INFO_COLS * sizeof(double), nullptr, info, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_pair_align_batch_dev(c, (const double*)c->fd_in.p, stride, (const long*)c->fd_len.p, d, ov, members, params, G, out_len,
+                                       aligned ? (double*)c->pa_aligned.p : nullptr, combined ? (double*)c->pa_combined.p : nullptr,
+                                       (double*)c->pa_info.p));
+    RET_IF(stage_down(c, io));
+    c->report = report_pair_align(members, info, G, combined != nullptr);
+    return 0;
+}
+
+int gsmcal_pair_align(gsmcal_ctx* c, const double* s, long len, int ov, const double* params_row, long out_len, double* out,
+                      double* info_row) {
+    if (!c || !params_row || !out || !info_row || (len >= 1 && !s)) return GSMCAL_E_ARG;
+    const int member = 0;
+    const double none[2] = {0.0, 0.0};                           // an empty stream: one sample that is never read
+    const long stride = len >= 1 ? len : 1;
+    double info[2 * GSMCAL_ALIGN_INFO_COLS];
+    RET_IF(gsmcal_pair_align_batch(c, len >= 1 ? s : none, stride, &len, 1, ov, &member, params_row, 1, out_len, out, nullptr, info));
+    std::copy(info, info + GSMCAL_ALIGN_INFO_COLS, info_row);
+    return (int)info[GSMCAL_AI_STATUS];
+}
+
+int gsmcal_pair_align_params(const double* pair_row, int ov, double min_coh, double weight, double* params_row) {
+    if (!pair_row || !params_row || (ov != 2 && ov != 4 && ov != 8)) return GSMCAL_E_ARG;
+    std::fill(params_row, params_row + GSMCAL_ALIGN_PARAMS, NAN);
+    params_row[GSMCAL_A_WEIGHT] = weight;
+    if (!(pair_row[GSMCAL_P_STATUS] == 0.0)) return GSMCAL_S_ALIGN_SKIPPED;
+    int first = -1;
+    for (int j = 0; j < GSMCAL_MAX_PAIR_BURSTS && first < 0; ++j)
+        if (pair_row[GSMCAL_P_POS + j] == pair_row[GSMCAL_P_POS + j] && pair_row[GSMCAL_P_EDGE + j] == 0.0 &&
+            pair_row[GSMCAL_P_COH + j] >= min_coh)
+            first = j;
+    if (first < 0) return GSMCAL_S_ALIGN_SKIPPED;
+    const double p0 = round(pair_row[GSMCAL_P_POS + first]) - 1.0, half = (148.0 * ov - 1.0) / 2.0;
+    const double ppm = pair_row[GSMCAL_P_REL_SAMPLING_PPM], s = 1e-6 * ppm;
+    params_row[GSMCAL_A_ANCHOR] = p0 + half;
+    params_row[GSMCAL_A_DELAY] = pair_row[GSMCAL_P_DELAY0] + s * half;
+    params_row[GSMCAL_A_SLOPE_PPM] = ppm;
+    params_row[GSMCAL_A_CARRIER_HZ] = pair_row[GSMCAL_P_REL_CARRIER_HZ] * (1.0 + s);
+    params_row[GSMCAL_A_PHASE] = pair_row[GSMCAL_P_PHASE0];
+    return 0;
+}
+
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out) {
     if (!ppm_in || !ppm_out || n < 1) return GSMCAL_E_ARG;

@@ -202,4 +202,24 @@ std::string report_pair_coherence(const double* row) {
     return r;
 }
 
+// gsmcal_pair_align / gsmcal_pair_align_batch (the project's own lines).  info: [G + 1][GSMCAL_ALIGN_INFO_COLS]; one line per member
+// (status, valid interval), one for the sum.
+std::string report_pair_align(const int* members, const double* info, int G, bool with_sum) {
+    char buf[200];
+    std::string r;
+    for (int g = 0; g < G; ++g) {
+        const double* o = info + (size_t)g * GSMCAL_ALIGN_INFO_COLS;
+        snprintf(buf, sizeof buf, "align member %d stream %d status %d valid [%ld, %ld) %ld samples\n", g, members[g], (int)o[GSMCAL_AI_STATUS],
+                 (long)o[GSMCAL_AI_FIRST_VALID], (long)o[GSMCAL_AI_END_VALID], (long)o[GSMCAL_AI_NUM_VALID]);
+        r += buf;
+    }
+    if (with_sum) {
+        const double* o = info + (size_t)G * GSMCAL_ALIGN_INFO_COLS;
+        snprintf(buf, sizeof buf, "align sum of %d members valid [%ld, %ld) weights ", (int)o[GSMCAL_AI_STATUS], (long)o[GSMCAL_AI_FIRST_VALID],
+                 (long)o[GSMCAL_AI_END_VALID]);
+        r += buf + rep_num2str(o[GSMCAL_AI_NUM_VALID]) + "\n";
+    }
+    return r;
+}
+
 }  // namespace

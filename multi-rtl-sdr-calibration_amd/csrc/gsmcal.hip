@@ -35,6 +35,7 @@
 #include "kernels_cwcheck.h"
 #include "kernels_iqcheck.h"
 #include "kernels_pair.h"
+#include "kernels_align.h"
 #include "state.h"
 
 #define GSMCAL_VERSION "gsmcal-mi355x 0.1 (gfx950)"
