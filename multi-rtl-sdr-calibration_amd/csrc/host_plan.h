@@ -665,16 +665,16 @@ int run_fine(gsmcal_ctx* c, int S, const Source& src, int lvl, const Geom& g, in
     if (!setup_done) LAUNCH(c, k_step<STEP_FINE_SETUP>, dim3(S), dim3(64), 0, st, sa, lvl, 0);
     // raw sources at level 0: the certificate kernel builds the windows itself when a staging pass fits its free LDS
     const int fc_thr = fc_threads(g.fine_nshift);
-    const size_t clds = (fc_lds_bytes(g.fine_nshift, g.nfft) + 15) & ~(size_t)15;
+    const FcCarve fcv = fc_carve(g.fine_nshift, g.nfft);
+    const size_t clds = fcv.launch;
     const bool cert_ok = c->prescreen && c->certify && fc_thr <= 512 && clds <= 159 * 1024 &&
                          (g.fine_nshift - 1) % FS_CHUNK == 0 && g.nfft % 148 == 0 && g.nfft >= 2 * FC_NB;
     FusedGather fg;
     memset(&fg, 0, sizeof(fg));
     if (cert_ok && src.kind == SRC_RAW && lvl == 0 && c->fuse_fine_gather) {
-        const size_t avail = clds - (size_t)FC_XP(g.fine_wlen) * sizeof(cplx) - 16;
         for (int np = 2; np <= 8; ++np) {
             const int per = ((g.fine_wlen + np - 1) / np + 3) & ~3;
-            if ((per + src.ntaps + 14) / 8 + 1 <= fc_thr && fc_stage_bytes(per, src.ntaps) <= avail) {
+            if ((per + src.ntaps + 14) / 8 + 1 <= fc_thr && fc_stage_bytes(per, src.ntaps) <= fcv.stage) {
                 fg.raw = src.raw; fg.raw_stride = src.raw_stride; fg.coef = src.coef; fg.win_out = win;
                 fg.ntaps = src.ntaps; fg.per = per;
                 fg.sym47 = src.ntaps == 47 && (int)c->h_coef.size() == 47 && taps_symmetric(c->h_coef.data(), 47) ? 1 : 0;

@@ -1842,7 +1842,8 @@ __device__ __forceinline__ void fine_verify_body(const StreamState* __restrict__
 // Anchors by a two-level regrouping of the DFT sum (exact algebra, fp64): with B = gcd(64, nfft),
 //   S_k(m) = sum_{b<B} x[B*m+b] W^(k*b),   X_k(64c) = sum_{a<nfft/B} W^(k*B*a) * S_k(64c/B + a),   W = exp(-2 pi i/nfft)
 // i.e. nfft/B + (wlen/B)*B/nchunk MACs per anchor instead of nfft.
-// LDS: window | S partials (later E[nstep+1]) | twiddle tables (later the fp32 group sums).
+// The body below is its phases (fc_window_raw .. fc_emit) between its barriers; the dynamic LDS they share is laid out by
+// fc_carve(), for the kernel and the host alike.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float fc_group8_sum(float v) {     // sum over the 8 lanes of a bin group, in every lane
     int t;
@@ -1855,7 +1856,7 @@ __device__ __forceinline__ float fc_group8_sum(float v) {     // sum over the 8 
     return v;
 }
 
-__host__ __device__ inline int fc_gcd64(int n) { int b = 64; while (n % b) b >>= 1; return b; }
+__host__ __device__ constexpr int fc_gcd64(int n) { int b = 64; while (n % b) b >>= 1; return b; }
 // threads of k_fine_cert: 8 per chunk, at least 256.  (320 would save the nearly empty third round of the level-1 phase --
 // 69 blocks handed out 32 at a time -- but five-wave workgroups no longer sit three to a CU: measured 77 us against 59.)
 __host__ __device__ constexpr int fc_threads(int nshift) {
@@ -1879,12 +1880,55 @@ __host__ inline size_t fc_stage_bytes(int per, int ntaps) {
     const int span8 = per + ntaps + 8;
     return (size_t)(span8 + span8 / 4 + 1) * sizeof(cplx) + (size_t)fir_taps_padded(ntaps) * sizeof(double);
 }
-__host__ inline size_t fc_lds_bytes(int nshift, int nfft) {
-    const int nstep = nshift - 1, wlen = nstep + nfft, B = fc_gcd64(nfft);
-    size_t r1 = (size_t)FC_NB * (wlen / B) * sizeof(cplx), e1 = (size_t)(nstep + 2) * sizeof(double);
-    size_t r2 = (size_t)FC_NB * (B + 2 + nfft / B) * sizeof(cplx), e2 = (size_t)2 * (size_t)(FC_XP(nstep + 2) + 1) * sizeof(float) + 16 * sizeof(double);
-    return (size_t)FC_XP(wlen) * sizeof(cplx) + (r1 > e1 ? r1 : e1) + (r2 > e2 ? r2 : e2);
+
+// k_fine_cert's geometry and its dynamic LDS, written down once: the kernel's pointers, the size of the launch and run_fine()'s
+// fit test of a staging pass all come from here.  Byte offsets from the base of the dynamic LDS:
+//   xs    the window, FC_XP(wlen) samples
+//   reg1  Sp[FC_NB][nM], the S partials (level 1 -> level 2); from the E/C scans on Et[t], t = 0..nstep
+//   reg2  tw1[FC_NB][ld1] = W^(k_j b) and tw2[nA][FC_NB] = W^(k_j B a) (twiddles -> level 2); from the slides on sumS[t] (the sum
+//         over S of P(t,k), later s(t)) and Cs[t] (C(t) = sum_{q<t} |d_q|, the slack of the recurrence), FC_XP(nstep + 2) floats
+//         each, and behind them the 2 x 8 scan partials sh_scan / sh_scan2 (block scan, certificate)
+// Before the tone estimate regions 1 and 2 are free: the bin choice keeps its 148-point spectrum at reg1, and a window built from
+// the raw bytes stages its passes there (`stage` bytes: what is left of the launch behind the window, less 16).
+struct FcCarve {
+    int nstep, wlen, B, nA, nM, nchunk, ld1;
+    size_t xs, reg1, reg2;
+    size_t Sp, Et, tw1, tw2, sumS, Cs, sh_scan, sh_scan2;
+    size_t total, launch, stage;     // bytes used | dynamic LDS of the launch (whole 16 bytes) | room of a staging pass
+};
+__host__ __device__ constexpr FcCarve fc_carve(int nshift, int nfft) {
+    FcCarve c{};
+    c.nstep = nshift - 1; c.wlen = c.nstep + nfft;
+    c.B = fc_gcd64(nfft); c.nA = nfft / c.B; c.nM = c.wlen / c.B; c.nchunk = c.nstep / FS_CHUNK;
+    c.ld1 = c.B + 2;                                      // plane stride of tw1: spreads the 8 bins over the banks
+    const int xp = FC_XP(c.nstep + 2);
+    const size_t r1 = (size_t)FC_NB * c.nM * sizeof(cplx), e1 = (size_t)(c.nstep + 2) * sizeof(double);
+    const size_t r2 = (size_t)FC_NB * (c.B + 2 + nfft / c.B) * sizeof(cplx), e2 = (size_t)2 * (size_t)(xp + 1) * sizeof(float) + 16 * sizeof(double);
+    c.xs = 0;
+    c.reg1 = (size_t)FC_XP(c.wlen) * sizeof(cplx);
+    c.reg2 = c.reg1 + (r1 > e1 ? r1 : e1);
+    c.Sp = c.Et = c.reg1;
+    c.tw1 = c.reg2;
+    c.tw2 = c.tw1 + (size_t)(FC_NB * c.ld1) * sizeof(cplx);
+    c.sumS = c.reg2;
+    c.Cs = c.sumS + (size_t)xp * sizeof(float);
+    c.sh_scan = c.Cs + (size_t)(xp + (xp & 1)) * sizeof(float);
+    c.sh_scan2 = c.sh_scan + 8 * sizeof(double);
+    c.total = c.reg2 + (r2 > e2 ? r2 : e2);
+    c.launch = (c.total + 15) & ~(size_t)15;
+    c.stage = c.launch - c.reg1 - 16;
+    return c;
 }
+static_assert(fc_carve(1025, 1184).total == 53520, "reference geometry: with the 144 bytes of static LDS, 100 bytes under the 53 760-byte line (three workgroups per CU)");
+// a pointer into the carve (every phase forms its pointers from the one base)
+template <typename T>
+__device__ __forceinline__ T* fc_at(size_t off) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    return (T*)(smem + off);
+}
+struct FcThread { int tid, lane, wave, nthr, nwave; };
+// static LDS: the block reduction's slots (red_p: E(0) of the block scan before that), the certified range [a, b] and the lowest bin of S
+struct alignas(16) FcShared { double red_p[8]; int red_t[8], red_k[8]; int a, b, lo; };
 
 // Issue priority of this wave by the dispatch round of its workgroup (0..255 / 256..511 / 512..: first, second, third on its
 // CU).  The SIMDs issue oldest wave first: left alone, the first workgroup of a CU finishes at ~35 us, the third at 55, alone on
@@ -1900,236 +1944,170 @@ __host__ inline size_t fc_lds_bytes(int nshift, int nfft) {
 #ifdef GSMCAL_DEVTIMING
 #define FC_ROLE_STAMP(wv, i)                                                                                          \
     do {                                                                                                              \
-        if (DEV_STAMP_ON(KID_CERT, i) && g_stamps && wave == (wv) && lane == 0 && blockIdx.y * gridDim.x + blockIdx.x < DEV_STAMP_BLOCKS) \
+        if (DEV_STAMP_ON(KID_CERT, i) && g_stamps && th.wave == (wv) && th.lane == 0 && blockIdx.y * gridDim.x + blockIdx.x < DEV_STAMP_BLOCKS) \
             g_stamps[((size_t)KID_CERT * DEV_STAMP_BLOCKS + blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = wall_clock64();           \
     } while (0)
 #else
 #define FC_ROLE_STAMP(wv, i) do { } while (0)
 #endif
-// OV > 0: the reference geometry as compile-time constants (128*OV+1 shifts, 148*OV-point windows, NTAPS filter taps);
-// OV = 0: from the arguments.
+
+// ---- k_fine_cert's phases, in the order the kernel runs them.  The barriers between them are the kernel's. ----
+
+// raw chunk `tid` of a pass over [first, first + span) (8 samples, 16-byte aligned); samples outside the stream read as 0
+__device__ __forceinline__ uint4 fc_raw_chunk(const unsigned short* base, long n0, long ao, long first, int span, int tid, long& first_al) {
+    first_al = raw_first_al(first, ao);
+    const long g0 = first_al + 8L * tid;
+    return g0 < first + span ? ffast_chunk(base, g0, n0) : make_uint4(0, 0, 0, 0);
+}
+// The window straight from the raw bytes (raw2iq.m:6-8 + filter(coef,1,.), gather_core's level 0 with the same
+// order of operations), in passes of fg.per outputs staged through regions 1/2 (free until the tone estimate):
+// the window never makes the trip through HBM before the first use, and the k_gather launch in front of this
+// kernel is gone.  It is still written out for k_fine_chunk / k_fine_verify.  (Stamps 8 .. 11 and the A/B build's store sit
+// between the passes' own barriers, in here.)
+// st: the stream's state, base: its raw samples, ws: the window's first sample, wout: where the window goes in HBM
 template <int OV, int NTAPS>
-__global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict__ sts,
-                                                   const cplx* __restrict__ win, long win_stream_stride,
-                                                   long win_stride, int nshift_rt, int nfft_rt,
-                                                   const cplx* __restrict__ tw_g, FineCert* __restrict__ cert, int H,
-                                                   int* __restrict__ items, int* __restrict__ n_items, FusedGather fg_in) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int nshift = OV > 0 ? 128 * OV + 1 : nshift_rt, nfft = OV > 0 ? 148 * OV : nfft_rt;
-    FusedGather fg = fg_in;
-    if (OV > 0) fg.ntaps = NTAPS;
-    const int nstep = nshift - 1, wlen = nstep + nfft;
-    const int B = fc_gcd64(nfft), nA = nfft / B, nM = wlen / B, nchunk = nstep / FS_CHUNK;
-    const int nthr = blockDim.x;                          // >= 8 * nchunk, whole waves (as a compile-time constant: 1.2 us SLOWER)
-    cplx* xs = (cplx*)smem;                               // window
-    const size_t r1 = (size_t)FC_NB * nM * sizeof(cplx), e1 = (size_t)(nstep + 2) * sizeof(double);
-    cplx* Sp = xs + FC_XP(wlen);                          // S partials [j][m]
-    double* Et = (double*)Sp;                             // ... later E[t], t = 0..nstep
-    unsigned char* reg2 = (unsigned char*)Sp + (r1 > e1 ? r1 : e1);
-    const int ld1 = B + 2;                                // plane stride of tw1: spreads the 8 bins over the banks
-    cplx* tw1 = (cplx*)reg2;                              // [j][b]  W^(k_j b)
-    cplx* tw2 = tw1 + FC_NB * ld1;                        // [a][j]  W^(k_j B a)
-    float* sumS = (float*)reg2;                           // ... later sum over S of P(t,k), t = 0..nstep
-    float* Cs = sumS + FC_XP(nstep + 2);                  // ... and C(t) = sum_{q<t} |d_q|, the slack of the recurrence
-    double* sh_scan = (double*)(Cs + FC_XP(nstep + 2) + (FC_XP(nstep + 2) & 1));   // 2 x 8 scan partials behind them (same phases)
-    double* sh_scan2 = sh_scan + 8;
-    __shared__ double red_p[8];
-    __shared__ int red_t[8], red_k[8];
-    __shared__ int sh_a, sh_b, sh_lo;
-    const int s = blockIdx.y, w = blockIdx.x;
-    if (w >= sts[s].n_win) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
-    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 0);
-    FC_PRIO(0, 1, 2)                                      // window build: youngest workgroup of the CU first (see FC_PRIO)
-    if (fg.raw) {
-        // The window straight from the raw bytes (raw2iq.m:6-8 + filter(coef,1,.), gather_core's level 0 with the same
-        // order of operations), in passes of fg.per outputs staged through regions 1/2 (free until the tone estimate):
-        // the window never makes the trip through HBM before the first use, and the k_gather launch in front of this
-        // kernel is gone.  It is still written out for k_fine_chunk / k_fine_verify.
-        const StreamState* st = sts + s;
-        const long n0 = st->n0, ws = st->win_start[w];
-        const double mr = st->mean_re, mi = st->mean_im;
-        const int ntp = fg.ntaps, per = fg.per;
-        cplx* xq = (cplx*)Sp;
-        double* c_s = (double*)(xq + xs_pad(per + ntp + 8) + 1);
-        const unsigned short* base = (const unsigned short*)(fg.raw + (size_t)s * fg.raw_stride);
-        cplx* wout = fg.win_out + (size_t)s * win_stream_stride + (size_t)w * win_stride;
-        fir_stage_taps(c_s, fg.coef, ntp, tid, nthr);
-        const bool sym47 = OV > 0 && NTAPS == 47 && fg.sym47 != 0;      // (block-uniform)
-        double cf[24];                                                // the 24 distinct taps (uniform addresses: scalar loads)
-        if (OV > 0 && NTAPS == 47) {
+__device__ __forceinline__ void fc_window_raw(const FcCarve& cv, const FcThread& th, const FusedGather& fg, const StreamState* st,
+                                              const unsigned short* base, long ws, cplx* wout) {
+    const int tid = th.tid, nthr = th.nthr, wlen = cv.wlen;
+    cplx* xs = fc_at<cplx>(cv.xs);
+    const long n0 = st->n0;
+    const double mr = st->mean_re, mi = st->mean_im;
+    const int ntp = fg.ntaps, per = fg.per;
+    cplx* xq = fc_at<cplx>(cv.reg1);
+    double* c_s = (double*)(xq + xs_pad(per + ntp + 8) + 1);
+    fir_stage_taps(c_s, fg.coef, ntp, tid, nthr);
+    const bool sym47 = OV > 0 && NTAPS == 47 && fg.sym47 != 0;      // (block-uniform)
+    double cf[24];                                                // the 24 distinct taps (uniform addresses: scalar loads)
+    if (OV > 0 && NTAPS == 47) {
 #pragma unroll
-            for (int k = 0; k < 24; ++k) cf[k] = fg.coef[k];
+        for (int k = 0; k < 24; ++k) cf[k] = fg.coef[k];
+    }
+    // the raw chunk is fetched one pass ahead so the loads overlap the FIR of the previous one; what read as 0 outside the stream
+    // is zeroed again after the mean is subtracted
+    const long ao = raw_align_off(base);
+    long first_al;
+    uint4 pre = fc_raw_chunk(base, n0, ao, ws - (ntp - 1), (per < wlen ? per : wlen) + ntp - 1, tid, first_al);
+    for (int o0 = 0; o0 < wlen; o0 += per) {
+        const int cnt = wlen - o0 < per ? wlen - o0 : per;
+        const long first = ws + o0 - (ntp - 1);
+        const int span = cnt + ntp - 1;
+        raw_chunk_to_lds(xq, pre, tid, (int)(first - first_al), first, span, span + 8, n0, mr, mi);   // entries span .. span+7 are 0
+        __syncthreads();
+        if (o0 == 0) DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 8);
+        if (o0 + per < wlen) {
+            const int ncnt = wlen - (o0 + per) < per ? wlen - (o0 + per) : per;
+            pre = fc_raw_chunk(base, n0, ao, first + per, ncnt + ntp - 1, tid, first_al);
         }
-        // raw chunk `tid` of a pass (8 samples, 16-byte aligned), fetched one pass ahead so the loads overlap the FIR of
-        // the previous one; samples outside the stream read as 0 and are zeroed again after the mean is subtracted
-        const long ao = (long)(((uintptr_t)base >> 1) & 7);
-        auto raw_chunk = [&](long first, int span, long& first_al) -> uint4 {
-            long m = (first + ao) % 8;
-            if (m < 0) m += 8;
-            first_al = first - m;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            const long g0 = first_al + 8L * tid;
-            if (g0 < first + span) {
-                if (g0 >= 0 && g0 + 8 <= n0) {
-                    v = *(const uint4*)(base + g0);
-                } else {
-                    unsigned short t[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) t[i] = (g0 + i >= 0 && g0 + i < n0) ? base[g0 + i] : (unsigned short)0;
-                    v.x = t[0] | ((unsigned)t[1] << 16); v.y = t[2] | ((unsigned)t[3] << 16);
-                    v.z = t[4] | ((unsigned)t[5] << 16); v.w = t[6] | ((unsigned)t[7] << 16);
-                }
-            }
-            return v;
-        };
-        long first_al;
-        uint4 pre = raw_chunk(ws - (ntp - 1), (per < wlen ? per : wlen) + ntp - 1, first_al);
-        for (int o0 = 0; o0 < wlen; o0 += per) {
-            const int cnt = wlen - o0 < per ? wlen - o0 : per;
-            const long first = ws + o0 - (ntp - 1);
-            const int span = cnt + ntp - 1;
-            {   // raw2iq.m:6-8 from the registers: staged sample i = 8*tid + u - (first - first_al); entries span .. span+7 are 0
-                const int i_base = 8 * tid - (int)(first - first_al);
-                const unsigned wv[4] = {pre.x, pre.y, pre.z, pre.w};
-                const long g_base = first + i_base;
-                if (i_base >= 0 && i_base + 8 <= span && g_base >= 0 && g_base + 8 <= n0) {
-                    // the usual chunk: all eight samples inside the span and the stream -- no per-sample tests, and two
-                    // 16-byte-aligned groups of four padded slots (i_base is a multiple of 8 here only when first is aligned, so
-                    // the stores stay per sample; the tests were most of this loop)
-                    // (xs_pad(i_base + u) = xs_pad(i_base) + u + ((r + u) >> 2), r = i_base & 3 the same in every lane: one lane
-                    // address plus scalar offsets, as in k_stream_tile_s47)
-                    const int r = __builtin_amdgcn_readfirstlane(i_base & 3);
-                    cplx* xp = xq + xs_pad(i_base);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const unsigned q = wv[u >> 1] >> (16 * (u & 1));
-                        xp[u + ((r + u) >> 2)] = make_double2((double)(q & 0xFFu) - mr, (double)((q >> 8) & 0xFFu) - mi);
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int i = i_base + u;
-                        const long g = first + i;
-                        const unsigned q = (wv[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
-                        cplx v = make_double2(0.0, 0.0);
-                        if (i < span && g >= 0 && g < n0) v = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
-                        if (i >= 0 && i < span + 8) xq[xs_pad(i)] = v;
-                    }
-                }
-            }
-            __syncthreads();
-            if (o0 == 0) DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 8);
-            if (o0 + per < wlen) {
-                const int ncnt = wlen - (o0 + per) < per ? wlen - (o0 + per) : per;
-                pre = raw_chunk(first + per, ncnt + ntp - 1, first_al);
-            }
-            for (int i0 = 4 * tid; i0 < cnt; i0 += 4 * nthr) {
-                cplx y0, y1, y2, y3;              // gather_core's loop: every accumulator takes its taps oldest first
-                if (OV > 0 && NTAPS == 47 && sym47) {   // same sums, bit for bit: 50 LDS reads per four outputs instead of 72
-                    cplx y[4];
-                    fir4_sym47(xq, cf, i0, y);
-                    y0 = y[0]; y1 = y[1]; y2 = y[2]; y3 = y[3];
-                } else if (ntp == 47) fir4_lds<47>(xq, c_s, i0, ntp, &y0, &y1, &y2, &y3);
-                else fir4_lds<0>(xq, c_s, i0, ntp, &y0, &y1, &y2, &y3);
-                const int o = o0 + i0;
+        for (int i0 = 4 * tid; i0 < cnt; i0 += 4 * nthr) {
+            cplx y0, y1, y2, y3;              // gather_core's loop: every accumulator takes its taps oldest first
+            if (OV > 0 && NTAPS == 47 && sym47) {   // same sums, bit for bit: 50 LDS reads per four outputs instead of 72
+                cplx y[4];
+                fir4_sym47(xq, cf, i0, y);
+                y0 = y[0]; y1 = y[1]; y2 = y[2]; y3 = y[3];
+            } else if (ntp == 47) fir4_lds<47>(xq, c_s, i0, ntp, &y0, &y1, &y2, &y3);
+            else fir4_lds<0>(xq, c_s, i0, ntp, &y0, &y1, &y2, &y3);
+            const int o = o0 + i0;
 #ifdef GSMCAL_AB_LAZY_WIN      /* A/B build of tools/ab_traffic.sh only: the window goes out at the end, and only if the certificate left chunks open */
-                xs[FC_XP(o)] = y0;
-                if (i0 + 1 < cnt) xs[FC_XP(o + 1)] = y1;
-                if (i0 + 2 < cnt) xs[FC_XP(o + 2)] = y2;
-                if (i0 + 3 < cnt) xs[FC_XP(o + 3)] = y3;
+            xs[FC_XP(o)] = y0;
+            if (i0 + 1 < cnt) xs[FC_XP(o + 1)] = y1;
+            if (i0 + 2 < cnt) xs[FC_XP(o + 2)] = y2;
+            if (i0 + 3 < cnt) xs[FC_XP(o + 3)] = y3;
 #else
-                xs[FC_XP(o)] = y0; wout[o] = y0;
-                if (i0 + 1 < cnt) { xs[FC_XP(o + 1)] = y1; wout[o + 1] = y1; }
-                if (i0 + 2 < cnt) { xs[FC_XP(o + 2)] = y2; wout[o + 2] = y2; }
-                if (i0 + 3 < cnt) { xs[FC_XP(o + 3)] = y3; wout[o + 3] = y3; }
+            xs[FC_XP(o)] = y0; wout[o] = y0;
+            if (i0 + 1 < cnt) { xs[FC_XP(o + 1)] = y1; wout[o + 1] = y1; }
+            if (i0 + 2 < cnt) { xs[FC_XP(o + 2)] = y2; wout[o + 2] = y2; }
+            if (i0 + 3 < cnt) { xs[FC_XP(o + 3)] = y3; wout[o + 3] = y3; }
 #endif
-            }
-            __syncthreads();
-            DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 9 + (o0 > 0) + (o0 > per));
         }
-        if (tid == 0) { sh_a = 0; sh_b = nstep; }
         __syncthreads();
-    } else {
-        const cplx* x = win + (size_t)s * win_stream_stride + (size_t)w * win_stride;
-        for (int i = tid; i < wlen; i += nthr) xs[FC_XP(i)] = x[i];
-        if (tid == 0) { sh_a = 0; sh_b = nstep; }
-        __syncthreads();
+        DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 9 + (o0 > 0) + (o0 > per));
     }
-    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 1);
-    FC_PRIO(2, 1, 0)                                      // choice of S and the anchors: oldest first
-    // ---- S: the tone's bin from a 148-point spectrum of the window's middle nfft samples summed in groups of
-    // ov (nfft = 148*ov, so the two frequency grids coincide; the channel filter keeps the signal inside the
-    // decimated band).  Only the choice of S depends on this estimate, never the result: a poor choice just
-    // certifies less.
-    {
-        const int D = nfft / 148, n0 = nstep / 2;
-        cplx* yd = Sp;                                    // region 1 is free until level 1
-        cplx* t148 = Sp + 148;
-        double* pw = (double*)(Sp + 296);
-        for (int m = tid; m < 148; m += nthr) {
-            double sr = 0.0, si = 0.0;
-            for (int i = 0; i < D; ++i) { const cplx v = xs[FC_XP(n0 + D * m + i)]; sr += v.x; si += v.y; }
-            yd[m] = make_double2(sr, si);
-            t148[m] = tw_g[D * m];
-        }
-        __syncthreads();
-        // 148 = 4 x 37: Y[k1 + 37 k2] = sum_{n2<4} W148^(n2 (k1+37 k2)) * sum_{n1<37} y[4 n1 + n2] W37^(n1 k1)
-        cplx* A = (cplx*)(pw + 148);                      // [n2][k1], 148 entries
-        for (int o = tid; o < 148; o += nthr) {
-            const int n2 = o / 37, k1 = o - n2 * 37;
-            double ar = 0.0, ai = 0.0;
-            int idx = 0;
+}
+
+// ... or read from `win`, where a k_gather launch left it
+__device__ __forceinline__ void fc_window_load(const FcCarve& cv, const FcThread& th, const cplx* x) {
+    const int tid = th.tid, nthr = th.nthr, wlen = cv.wlen;
+    cplx* xs = fc_at<cplx>(cv.xs);
+    for (int i = tid; i < wlen; i += nthr) xs[FC_XP(i)] = x[i];
+}
+
+// ---- S: the tone's bin from a 148-point spectrum of the window's middle nfft samples summed in groups of
+// ov (nfft = 148*ov, so the two frequency grids coincide; the channel filter keeps the signal inside the
+// decimated band).  Only the choice of S depends on this estimate, never the result: a poor choice just
+// certifies less.  Returns the lowest bin of S in every thread (its last barrier publishes it).
+__device__ __forceinline__ int fc_choose_bins(const FcCarve& cv, const FcThread& th, int nfft, const cplx* tw_g, FcShared& sh) {
+    const int tid = th.tid, lane = th.lane, wave = th.wave, nthr = th.nthr, nstep = cv.nstep;
+    cplx* xs = fc_at<cplx>(cv.xs);
+    cplx* Sp = fc_at<cplx>(cv.Sp);
+    const int D = nfft / 148, n0 = nstep / 2;
+    cplx* yd = Sp;                                    // region 1 is free until level 1
+    cplx* t148 = Sp + 148;
+    double* pw = (double*)(Sp + 296);
+    for (int m = tid; m < 148; m += nthr) {
+        double sr = 0.0, si = 0.0;
+        for (int i = 0; i < D; ++i) { const cplx v = xs[FC_XP(n0 + D * m + i)]; sr += v.x; si += v.y; }
+        yd[m] = make_double2(sr, si);
+        t148[m] = tw_g[D * m];
+    }
+    __syncthreads();
+    // 148 = 4 x 37: Y[k1 + 37 k2] = sum_{n2<4} W148^(n2 (k1+37 k2)) * sum_{n1<37} y[4 n1 + n2] W37^(n1 k1)
+    cplx* A = (cplx*)(pw + 148);                      // [n2][k1], 148 entries
+    for (int o = tid; o < 148; o += nthr) {
+        const int n2 = o / 37, k1 = o - n2 * 37;
+        double ar = 0.0, ai = 0.0;
+        int idx = 0;
 #pragma unroll 4
-            for (int n1 = 0; n1 < 37; ++n1) {
-                const cplx v = yd[4 * n1 + n2], t = t148[idx];   // W37^m = W148^(4m)
-                ar = fma(v.x, t.x, fma(-v.y, t.y, ar));
-                ai = fma(v.x, t.y, fma(v.y, t.x, ai));
-                idx += 4 * k1;
-                idx = idx >= 148 ? idx - 148 : idx;
-            }
-            A[o] = make_double2(ar, ai);
+        for (int n1 = 0; n1 < 37; ++n1) {
+            const cplx v = yd[4 * n1 + n2], t = t148[idx];   // W37^m = W148^(4m)
+            ar = fma(v.x, t.x, fma(-v.y, t.y, ar));
+            ai = fma(v.x, t.y, fma(v.y, t.x, ai));
+            idx += 4 * k1;
+            idx = idx >= 148 ? idx - 148 : idx;
         }
-        __syncthreads();
-        for (int q = tid; q < 148; q += nthr) {
-            const int k1 = q % 37;
-            double ar = 0.0, ai = 0.0;
-            int idx = 0;
-#pragma unroll
-            for (int n2 = 0; n2 < 4; ++n2) {
-                const cplx v = A[n2 * 37 + k1], t = t148[idx];
-                ar = fma(v.x, t.x, fma(-v.y, t.y, ar));
-                ai = fma(v.x, t.y, fma(v.y, t.x, ai));
-                idx += q;
-                idx = idx >= 148 ? idx - 148 : idx;
-            }
-            pw[q] = ar * ar + ai * ai;
-        }
-        __syncthreads();
-        if (wave == 0) {
-            double bp = -1.0;
-            int bq = 0;
-            for (int q = lane; q < 148; q += 64)
-                if (pw[q] > bp) { bp = pw[q]; bq = q; }
-            for (int off = 32; off > 0; off >>= 1) {
-                const double op = __shfl_down(bp, off, 64);
-                const int oq = __shfl_down(bq, off, 64);
-                if (op > bp || (op == bp && oq < bq)) { bp = op; bq = oq; }
-            }
-            if (lane == 0) {
-                const bool up = pw[(bq + 1) % 148] > pw[(bq + 147) % 148];
-                const int kpk = bq < 74 ? bq : nfft - 148 + bq;
-                sh_lo = kpk - (up ? FC_NB / 2 - 1 : FC_NB / 2);   // bins lo .. lo+FC_NB-1 (mod nfft), leaning to the stronger side
-            }
-        }
-        __syncthreads();
+        A[o] = make_double2(ar, ai);
     }
-    const int lo = sh_lo;
-    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 2);
-    const int j = tid & (FC_NB - 1), c = tid / FC_NB;
-    const bool act = c < nchunk;                          // lanes beyond the last chunk only help with the shared phases
-    const int k = ((lo + j) % nfft + nfft) % nfft;
-    for (int i = tid; i < FC_NB * (B + nA); i += nthr) {  // twiddle tables of the FC_NB bins
+    __syncthreads();
+    for (int q = tid; q < 148; q += nthr) {
+        const int k1 = q % 37;
+        double ar = 0.0, ai = 0.0;
+        int idx = 0;
+#pragma unroll
+        for (int n2 = 0; n2 < 4; ++n2) {
+            const cplx v = A[n2 * 37 + k1], t = t148[idx];
+            ar = fma(v.x, t.x, fma(-v.y, t.y, ar));
+            ai = fma(v.x, t.y, fma(v.y, t.x, ai));
+            idx += q;
+            idx = idx >= 148 ? idx - 148 : idx;
+        }
+        pw[q] = ar * ar + ai * ai;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        double bp = -1.0;
+        int bq = 0;
+        for (int q = lane; q < 148; q += 64)
+            if (pw[q] > bp) { bp = pw[q]; bq = q; }
+        for (int off = 32; off > 0; off >>= 1) {
+            const double op = __shfl_down(bp, off, 64);
+            const int oq = __shfl_down(bq, off, 64);
+            if (op > bp || (op == bp && oq < bq)) { bp = op; bq = oq; }
+        }
+        if (lane == 0) {
+            const bool up = pw[(bq + 1) % 148] > pw[(bq + 147) % 148];
+            const int kpk = bq < 74 ? bq : nfft - 148 + bq;
+            sh.lo = kpk - (up ? FC_NB / 2 - 1 : FC_NB / 2);   // bins lo .. lo+FC_NB-1 (mod nfft), leaning to the stronger side
+        }
+    }
+    __syncthreads();
+    return sh.lo;
+}
+
+// twiddle tables of the FC_NB bins
+__device__ __forceinline__ void fc_twiddles(const FcCarve& cv, const FcThread& th, int nfft, int lo, const cplx* tw_g) {
+    const int tid = th.tid, nthr = th.nthr, B = cv.B, nA = cv.nA, ld1 = cv.ld1;
+    cplx* tw1 = fc_at<cplx>(cv.tw1);                      // [j][b]  W^(k_j b)
+    cplx* tw2 = fc_at<cplx>(cv.tw2);                      // [a][j]  W^(k_j B a)
+    for (int i = tid; i < FC_NB * (B + nA); i += nthr) {
         if (i < FC_NB * B) {
             const int jj = i / B, q = i - jj * B;
             const int kk = ((lo + jj) % nfft + nfft) % nfft;
@@ -2141,9 +2119,15 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
             tw2[q * FC_NB + jj] = tw_g[(((kk * B) % nfft) * q) % nfft];
         }
     }
-    __syncthreads();
-    // ---- level 1: S_k(m) for all nM blocks of the window.  Lane (c, j) starts its block at sample c mod B so
-    // that the groups of a wave read different LDS banks (the 8 lanes of a group share the sample: broadcast).
+}
+
+// ---- level 1: S_k(m) for all nM blocks of the window.  Lane (c, j) starts its block at sample c mod B so
+// that the groups of a wave read different LDS banks (the 8 lanes of a group share the sample: broadcast).
+__device__ __forceinline__ void fc_level1(const FcCarve& cv, const FcThread& th, int j, int c) {
+    const int nthr = th.nthr, B = cv.B, nM = cv.nM, ld1 = cv.ld1;
+    cplx* xs = fc_at<cplx>(cv.xs);
+    cplx* Sp = fc_at<cplx>(cv.Sp);
+    cplx* tw1 = fc_at<cplx>(cv.tw1);
     for (int m = c; m < nM; m += nthr / FC_NB) {
         const int xb0 = B * m;
         // B divides 128, so the block's B samples sit contiguously behind FC_XP(xb0); sample and twiddle share one running byte
@@ -2163,20 +2147,274 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
         }
         Sp[j * nM + m] = make_double2(ar, ai);
     }
-    __syncthreads();
-    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 3);
-    // ---- level 2: anchor X_k(64c) ----
-    double xr = 0.0, xi = 0.0;
-    if (act) {
-        const cplx* sb = Sp + j * nM + (FS_CHUNK / B) * c;
-        const cplx* tb = tw2 + j;
+}
+
+// ---- level 2: anchor X_k(64c) of lane (c, j) ----
+__device__ __forceinline__ void fc_level2_anchor(const FcCarve& cv, int j, int c, double& xr, double& xi) {
+    const int nA = cv.nA, nM = cv.nM, B = cv.B;
+    const cplx* sb = fc_at<cplx>(cv.Sp) + j * nM + (FS_CHUNK / B) * c;
+    const cplx* tb = fc_at<cplx>(cv.tw2) + j;
 #pragma unroll 4
-        for (int a = 0; a < nA; ++a) {
-            const cplx v = sb[a], t = tb[a * FC_NB];
-            xr = fma(v.x, t.x, fma(-v.y, t.y, xr));
-            xi = fma(v.x, t.y, fma(v.y, t.x, xi));
+    for (int a = 0; a < nA; ++a) {
+        const cplx v = sb[a], t = tb[a * FC_NB];
+        xr = fma(v.x, t.x, fma(-v.y, t.y, xr));
+        xi = fma(v.x, t.y, fma(v.y, t.x, xi));
+    }
+}
+
+// ---- E(t) and C(t): the two terms of step q, from a1 = x[q+nfft] and b1 = x[q] ----
+// g[q] = |x[q+nfft]|^2 - |x[q]|^2, the step of the window's energy
+__device__ __forceinline__ double fc_energy_term(const cplx& a1, const cplx& b1) {
+    return (a1.x * a1.x + a1.y * a1.y) - (b1.x * b1.x + b1.y * b1.y);
+}
+// |d_q| in fp32 (v_sqrt_f32 is one instruction, the fp64 square root a dozen): C(t) only has to be an UPPER bound of
+// the slack, each term is scaled up by 1 + 2^-20 > the rounding of the fp32 conversion and square root (< 2^-22)
+__device__ __forceinline__ double fc_slack_term(const cplx& a1, const cplx& b1) {
+    const double dr = a1.x - b1.x, di = a1.y - b1.y;
+    return (double)(__fsqrt_rn((float)(dr * dr + di * di)) * 1.00000095367431640625f);
+}
+
+// Role-split form: this wave alone forms E(t) (we) or C(t), t = 0..nstep.
+// a contiguous range of shifts per lane, an inclusive wave scan of the lane totals, a second pass with the running values
+template <int OV>
+__device__ __forceinline__ void fc_scan_role(const FcCarve& cv, const FcThread& th, int nfft, bool we) {
+    const int lane = th.lane, nstep = cv.nstep;
+    cplx* xs = fc_at<cplx>(cv.xs);
+    double* Et = fc_at<double>(cv.Et);
+    float* Cs = fc_at<float>(cv.Cs);
+    const int per = OV > 0 ? 2 * OV : (nstep + 63) >> 6;
+    const int i0 = lane * per < nstep ? lane * per : nstep, i1 = i0 + per < nstep ? i0 + per : nstep;
+    auto term = [&](int q) -> double {
+        const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
+        if (we) return fc_energy_term(a1, b1);
+        return fc_slack_term(a1, b1);
+    };
+    double run = 0.0;
+    if (we) {                                     // E(0), in every lane
+        for (int i = lane; i < nfft; i += 64) { const cplx v = xs[FC_XP(i)]; run += v.x * v.x + v.y * v.y; }
+        for (int off = 32; off > 0; off >>= 1) run += __shfl_down(run, off, 64);
+        run = __shfl(run, 0, 64);
+    }
+    double g[OV > 0 ? 2 * OV : 1];                // reference geometry: the range's terms stay in registers for the second pass
+    double loc = 0.0;
+    if (OV > 0) {
+#pragma unroll
+        for (int u = 0; u < 2 * OV; ++u) { g[u] = term(i0 + u); loc += g[u]; }   // (nstep = 64 * per: every range is whole)
+    } else {
+        for (int q = i0; q < i1; ++q) loc += term(q);
+    }
+    double inc = loc;
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    const double exc = __shfl_up(inc, 1, 64);
+    if (lane > 0) run += exc;
+    if (OV > 0) {
+#pragma unroll
+        for (int u = 0; u < 2 * OV; ++u) {
+            if (we) Et[i0 + u] = run; else Cs[FC_XP(i0 + u)] = (float)run;
+            run += g[u];
+        }
+    } else {
+        for (int q = i0; q < i1; ++q) {
+            if (we) Et[q] = run; else Cs[FC_XP(q)] = (float)run;
+            run += term(q);
         }
     }
+    if (i1 == nstep && i0 < nstep) { if (we) Et[nstep] = run; else Cs[FC_XP(nstep)] = (float)run; }
+}
+
+// Block form: E(0) by a block reduction, then a block scan of both terms (one barrier in the middle)
+__device__ __forceinline__ void fc_scan_block(const FcCarve& cv, const FcThread& th, int nfft, FcShared& sh) {
+    const int tid = th.tid, lane = th.lane, wave = th.wave, nthr = th.nthr, nwave = th.nwave, nstep = cv.nstep;
+    cplx* xs = fc_at<cplx>(cv.xs);
+    double* Et = fc_at<double>(cv.Et);
+    float* Cs = fc_at<float>(cv.Cs);
+    double* sh_scan = fc_at<double>(cv.sh_scan);
+    double* sh_scan2 = fc_at<double>(cv.sh_scan2);
+    double e0 = 0.0;
+    for (int i = tid; i < nfft; i += nthr) { const cplx v = xs[FC_XP(i)]; e0 += v.x * v.x + v.y * v.y; }
+    for (int off = 32; off > 0; off >>= 1) e0 += __shfl_down(e0, off, 64);
+    if (lane == 0) sh.red_p[wave] = e0;
+    const int per = (nstep + nthr - 1) / nthr;
+    const int i0 = tid * per < nstep ? tid * per : nstep, i1 = i0 + per < nstep ? i0 + per : nstep;
+    double loc = 0.0, locd = 0.0;
+    for (int q = i0; q < i1; ++q) {
+        const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
+        loc += fc_energy_term(a1, b1);
+        locd += fc_slack_term(a1, b1);
+    }
+    double inc = loc, incd = locd;                    // inclusive scans across the wave
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(inc, off, 64), od = __shfl_up(incd, off, 64);
+        if (lane >= off) { inc += o; incd += od; }
+    }
+    if (lane == 63) { sh_scan[wave] = inc; sh_scan2[wave] = incd; }
+    __syncthreads();
+    double run = inc - loc, rund = incd - locd;
+    for (int i = 0; i < wave; ++i) { run += sh_scan[i]; rund += sh_scan2[i]; }
+    for (int i = 0; i < nwave; ++i) run += sh.red_p[i];  // + E(0)
+    for (int q = i0; q < i1; ++q) {
+        Et[q] = run;
+        Cs[FC_XP(q)] = (float)rund;
+        const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
+        run += fc_energy_term(a1, b1);
+        rund += fc_slack_term(a1, b1);
+    }
+    if (i1 == nstep && i0 < nstep) { Et[nstep] = run; Cs[FC_XP(nstep)] = (float)rund; }
+}
+
+// ---- (P*, t*, k*): the first maximum of the wave, in lane 0 ...
+__device__ __forceinline__ void fc_wave_best(double& best, int& bt, int& bk) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const double op = __shfl_down(best, off, 64);
+        const int ot = __shfl_down(bt, off, 64);
+        const int ok = __shfl_down(bk, off, 64);
+        if (op > best || (op == best && (ot < bt || (ot == bt && ok < bk)))) { best = op; bt = ot; bk = ok; }
+    }
+}
+// ... and of the block, in every thread (one barrier)
+__device__ __forceinline__ void fc_block_best(const FcThread& th, FcShared& sh, double& best, int& bt, int& bk) {
+    if (th.lane == 0) { sh.red_p[th.wave] = best; sh.red_t[th.wave] = bt; sh.red_k[th.wave] = bk; }
+    __syncthreads();
+    best = sh.red_p[0]; bt = sh.red_t[0]; bk = sh.red_k[0];
+    for (int i = 1; i < th.nwave; ++i)
+        if (sh.red_p[i] > best || (sh.red_p[i] == best && (sh.red_t[i] < bt || (sh.red_t[i] == bt && sh.red_k[i] < bk)))) {
+            best = sh.red_p[i]; bt = sh.red_t[i]; bk = sh.red_k[i];
+        }
+}
+
+// ---- certificate per shift.  Two bounds on every bin outside S:
+//   Parseval at the shift itself:            |X_k(t)| <= s(t) = sqrt(R(t))
+//   the recurrence from any other shift t':  |X_k(t)| <= s(t') + |C(t) - C(t')|   (each step adds at most |d_q|)
+// so U(t) = min( C(t) + min_{t'<=t}(s(t') - C(t')),  -C(t) + min_{t'>=t}(s(t') + C(t')) ) and shift t is certified
+// when U(t) < sqrt(P*).  fp32 group sums: each of the 8 terms and 7 additions errs by <= 2^-24 relative, all
+// terms are <= N*E(t), so |sumS - exact| < 2e-6 * N*E(t); the margins cover that, the fp32 storage of s and C
+// and the fp64 rounding of E and P.  Narrows sh.a / sh.b to the certified range around t* = bt (two barriers).
+__device__ __forceinline__ void fc_certificate(const FcCarve& cv, const FcThread& th, int nfft, FcShared& sh, double best, int bt) {
+    const int tid = th.tid, lane = th.lane, wave = th.wave, nthr = th.nthr, nwave = th.nwave, nstep = cv.nstep;
+    double* Et = fc_at<double>(cv.Et);
+    float* sumS = fc_at<float>(cv.sumS);
+    float* Cs = fc_at<float>(cv.Cs);
+    double* sh_scan = fc_at<double>(cv.sh_scan);
+    double* sh_scan2 = fc_at<double>(cv.sh_scan2);
+    const double INF = __longlong_as_double(0x7ff0000000000000LL);
+    const double sb = best > 0.0 ? sqrt(best) * (1.0 - 1e-9) : -1.0;
+    const int per = (nstep + nthr) / nthr;            // >= ceil((nstep+1)/nthr)
+    const int u0 = tid * per < nstep + 1 ? tid * per : nstep + 1, u1 = u0 + per < nstep + 1 ? u0 + per : nstep + 1;
+    double mf = INF, mb = INF;
+    for (int t = u0; t < u1; ++t) {
+        const double NE = (double)nfft * Et[t];
+        const float ss = sumS[FC_XP(t)];
+        const double R = NE - (double)ss + 4e-6 * NE;
+        // (fp32 square root: s(t) is stored in fp32 anyway; the 1e-6 margin covers both roundings, < 2^-22 together)
+        float sf = ss <= 3.0e38f ? __fsqrt_rn((float)(R > 0.0 ? R : 0.0)) * 1.000001f : __int_as_float(0x7f800000);   // (an overflowed fp32 sum bounds nothing)
+        if (!(sf >= 0.0f)) sf = __int_as_float(0x7f800000);                  // NaN input
+        sumS[FC_XP(t)] = sf;                          // own range only: s(t) replaces the group sum
+        const double ct = (double)Cs[FC_XP(t)];
+        mf = fmin(mf, (double)sf - ct);
+        mb = fmin(mb, (double)sf + ct);
+    }
+    double pf = mf, pb = mb;                          // inclusive prefix-min / suffix-min across the wave
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(pf, off, 64), ob = __shfl_down(pb, off, 64);
+        if (lane >= off) pf = fmin(pf, o);
+        if (lane + off < 64) pb = fmin(pb, ob);
+    }
+    __syncthreads();                                  // sh_scan / sh_scan2 are free again
+    if (lane == 63) sh_scan[wave] = pf;
+    if (lane == 0) sh_scan2[wave] = pb;
+    double ef = __shfl_up(pf, 1, 64), eb = __shfl_down(pb, 1, 64);   // exclusive parts inside the wave
+    if (lane == 0) ef = INF;
+    if (lane == 63) eb = INF;
+    __syncthreads();
+    for (int i = 0; i < wave; ++i) ef = fmin(ef, sh_scan[i]);
+    for (int i = wave + 1; i < nwave; ++i) eb = fmin(eb, sh_scan2[i]);
+    const double ctot = (double)Cs[FC_XP(nstep)] * 1e-6;     // covers the fp32 rounding of the C(t) differences
+    unsigned okm = 0;                                 // per <= 32 for every supported geometry
+    for (int t = u0; t < u1; ++t) {
+        const double ct = (double)Cs[FC_XP(t)];
+        ef = fmin(ef, (double)sumS[FC_XP(t)] - ct);
+        if (ct + ef + ctot < sb) okm |= 1u << (t - u0);
+    }
+    for (int t = u1 - 1; t >= u0; --t) {
+        const double ct = (double)Cs[FC_XP(t)];
+        eb = fmin(eb, (double)sumS[FC_XP(t)] + ct);
+        const bool okc = ((okm >> (t - u0)) & 1u) || (eb - ct + ctot < sb);
+        if (!okc) {
+            if (t <= bt) atomicMax(&sh.a, t + 1);     // uncertified prefix [0, a)
+            if (t >= bt) atomicMin(&sh.b, t - 1);     // uncertified suffix (b, nstep]
+        }
+    }
+}
+
+// ---- emit (thread 0): the window's FineCert record and its open chunks on k_fine_chunk's work list ----
+__device__ __forceinline__ void fc_emit(const FcCarve& cv, const FcShared& sh, double best, int bt, int bk, int s, int H, int w,
+                                        FineCert* cert, int* items, int* n_items) {
+    const int nstep = cv.nstep, nchunk = cv.nchunk;
+    FineCert o;
+    o.p = best; o.t = bt; o.k = bk; o.a = sh.a; o.b = sh.b;
+    // every uncertified shift lies in the prefix [0, a) or in the suffix (b, nstep] (the certificate's loop above): only
+    // the chunks that hold those are swept.  Chunk c holds shifts 64c+1 .. 64c+64 (+ shift 0 in chunk 0).  (Round 3: a
+    // window with any suffix open used to be swept whole -- 560 chunks instead of 165 on the 64 mixed streams of bench.py.)
+    const int a = sh.a, b = sh.b;
+    int npre = a == 0 ? 0 : (a == 1 ? 1 : (a - 2) / FS_CHUNK + 1);
+    int nsuf = b < nstep ? nchunk - b / FS_CHUNK : 0;  // shift b+1 is the first of the suffix: chunk b/64
+    if (npre + nsuf > nchunk) { npre = nchunk; nsuf = 0; }
+    o.nch = npre + nsuf; o.nsuf = nsuf;
+    cert[(size_t)s * H + w] = o;
+    if (o.nch > 0) {                                  // work list of k_fine_chunk
+        const int base = atomicAdd(n_items, o.nch);
+        for (int i = 0; i < o.nch; ++i) items[base + i] = ((s * H + w) << 8) | fc_open_chunk(i, o.nch, nsuf, nchunk);
+    }
+}
+
+// OV > 0: the reference geometry as compile-time constants (128*OV+1 shifts, 148*OV-point windows, NTAPS filter taps);
+// OV = 0: from the arguments.
+template <int OV, int NTAPS>
+__global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict__ sts,
+                                                   const cplx* __restrict__ win, long win_stream_stride,
+                                                   long win_stride, int nshift_rt, int nfft_rt,
+                                                   const cplx* __restrict__ tw_g, FineCert* __restrict__ cert, int H,
+                                                   int* __restrict__ items, int* __restrict__ n_items, FusedGather fg_in) {
+    const int nshift = OV > 0 ? 128 * OV + 1 : nshift_rt, nfft = OV > 0 ? 148 * OV : nfft_rt;
+    FusedGather fg = fg_in;
+    if (OV > 0) fg.ntaps = NTAPS;
+    const FcCarve cv = fc_carve(nshift, nfft);
+    __shared__ FcShared sh;
+    const int s = blockIdx.y, w = blockIdx.x;
+    if (w >= sts[s].n_win) return;
+    FcThread th;
+    th.tid = threadIdx.x; th.lane = th.tid & 63; th.wave = th.tid >> 6;
+    th.nthr = blockDim.x;                                 // >= 8 * nchunk, whole waves (as a compile-time constant: 1.2 us SLOWER)
+    th.nwave = th.nthr >> 6;
+    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 0);
+    FC_PRIO(0, 1, 2)                                      // window build: youngest workgroup of the CU first (see FC_PRIO)
+    if (fg.raw) {
+        fc_window_raw<OV, NTAPS>(cv, th, fg, sts + s, (const unsigned short*)(fg.raw + (size_t)s * fg.raw_stride), sts[s].win_start[w],
+                                 fg.win_out + (size_t)s * win_stream_stride + (size_t)w * win_stride);
+        if (th.tid == 0) { sh.a = 0; sh.b = cv.nstep; }
+        __syncthreads();
+    } else {
+        fc_window_load(cv, th, win + (size_t)s * win_stream_stride + (size_t)w * win_stride);
+        if (th.tid == 0) { sh.a = 0; sh.b = cv.nstep; }
+        __syncthreads();
+    }
+    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 1);
+    FC_PRIO(2, 1, 0)                                      // choice of S and the anchors: oldest first
+    const int lo = fc_choose_bins(cv, th, nfft, tw_g, sh);
+    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 2);
+    const int j = th.tid & (FC_NB - 1), c = th.tid / FC_NB;
+    const bool act = c < cv.nchunk;                       // lanes beyond the last chunk only help with the shared phases
+    const int k = ((lo + j) % nfft + nfft) % nfft;
+    fc_twiddles(cv, th, nfft, lo, tw_g);
+    __syncthreads();
+    fc_level1(cv, th, j, c);
+    __syncthreads();
+    DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 3);
+    double xr = 0.0, xi = 0.0;
+    if (act) fc_level2_anchor(cv, j, c, xr, xi);
     __syncthreads();                                      // S and the tables are dead: E and sumS take their place
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 4);
     FC_PRIO(0, 1, 2)                                      // E(t), slides, certificate: youngest first
@@ -2185,100 +2423,28 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
     // form the two scans meanwhile, each on its own -- no barrier and no exchange before the join in front of the block
     // reduction.  (Before: all four waves scanned together, then waves 2 and 3 sat out the slides.)  Only the association
     // of the fp64 sums differs (~1e-13 relative in E and C, far inside the certificate's margins); P*, t*, k* are untouched.
-    const int nslide = (FC_NB * nchunk + 63) >> 6;        // waves that hold slide lanes
-    const bool split = nwave - nslide >= 2;
+    const int nslide = (FC_NB * cv.nchunk + 63) >> 6;     // waves that hold slide lanes
+    const bool split = th.nwave - nslide >= 2;
     if (split) {
         DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 5);
-        if (wave == nslide || wave == nslide + 1) {       // (wave-uniform) the E wave and the C wave
-            const bool we = wave == nslide;
-            // a contiguous range of shifts per lane, an inclusive wave scan of the lane totals, a second pass with the running values
-            const int per = OV > 0 ? 2 * OV : (nstep + 63) >> 6;
-            const int i0 = lane * per < nstep ? lane * per : nstep, i1 = i0 + per < nstep ? i0 + per : nstep;
-            auto term = [&](int q) -> double {
-                const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
-                if (we) return (a1.x * a1.x + a1.y * a1.y) - (b1.x * b1.x + b1.y * b1.y);
-                // |d_q| in fp32, scaled up by 1 + 2^-20: see the block scan below
-                const double dr = a1.x - b1.x, di = a1.y - b1.y;
-                return (double)(__fsqrt_rn((float)(dr * dr + di * di)) * 1.00000095367431640625f);
-            };
-            double run = 0.0;
-            if (we) {                                     // E(0), in every lane
-                for (int i = lane; i < nfft; i += 64) { const cplx v = xs[FC_XP(i)]; run += v.x * v.x + v.y * v.y; }
-                for (int off = 32; off > 0; off >>= 1) run += __shfl_down(run, off, 64);
-                run = __shfl(run, 0, 64);
-            }
-            double g[OV > 0 ? 2 * OV : 1];                // reference geometry: the range's terms stay in registers for the second pass
-            double loc = 0.0;
-            if (OV > 0) {
-#pragma unroll
-                for (int u = 0; u < 2 * OV; ++u) { g[u] = term(i0 + u); loc += g[u]; }   // (nstep = 64 * per: every range is whole)
-            } else {
-                for (int q = i0; q < i1; ++q) loc += term(q);
-            }
-            double inc = loc;
-            for (int off = 1; off < 64; off <<= 1) {
-                const double o = __shfl_up(inc, off, 64);
-                if (lane >= off) inc += o;
-            }
-            const double exc = __shfl_up(inc, 1, 64);
-            if (lane > 0) run += exc;
-            if (OV > 0) {
-#pragma unroll
-                for (int u = 0; u < 2 * OV; ++u) {
-                    if (we) Et[i0 + u] = run; else Cs[FC_XP(i0 + u)] = (float)run;
-                    run += g[u];
-                }
-            } else {
-                for (int q = i0; q < i1; ++q) {
-                    if (we) Et[q] = run; else Cs[FC_XP(q)] = (float)run;
-                    run += term(q);
-                }
-            }
-            if (i1 == nstep && i0 < nstep) { if (we) Et[nstep] = run; else Cs[FC_XP(nstep)] = (float)run; }
-            FC_ROLE_STAMP(wave, we ? 12 : 13);
+        if (th.wave == nslide || th.wave == nslide + 1) { // (wave-uniform) the E wave and the C wave
+            const bool we = th.wave == nslide;
+            fc_scan_role<OV>(cv, th, nfft, we);
+            FC_ROLE_STAMP(th.wave, we ? 12 : 13);
         }
     } else {
-        // E(0) by a block reduction, then a block scan of g[q] = |x[q+nfft]|^2 - |x[q]|^2
-        double e0 = 0.0;
-        for (int i = tid; i < nfft; i += nthr) { const cplx v = xs[FC_XP(i)]; e0 += v.x * v.x + v.y * v.y; }
-        for (int off = 32; off > 0; off >>= 1) e0 += __shfl_down(e0, off, 64);
-        if (lane == 0) red_p[wave] = e0;
-        const int per = (nstep + nthr - 1) / nthr;
-        const int i0 = tid * per < nstep ? tid * per : nstep, i1 = i0 + per < nstep ? i0 + per : nstep;
-        // |d_q| in fp32 (v_sqrt_f32 is one instruction, the fp64 square root a dozen): C(t) only has to be an UPPER bound of
-        // the slack, each term is scaled up by 1 + 2^-20 > the rounding of the fp32 conversion and square root (< 2^-22)
-        double loc = 0.0, locd = 0.0;
-        for (int q = i0; q < i1; ++q) {
-            const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
-            loc += (a1.x * a1.x + a1.y * a1.y) - (b1.x * b1.x + b1.y * b1.y);
-            const double dr = a1.x - b1.x, di = a1.y - b1.y;
-            locd += (double)(__fsqrt_rn((float)(dr * dr + di * di)) * 1.00000095367431640625f);
-        }
-        double inc = loc, incd = locd;                    // inclusive scans across the wave
-        for (int off = 1; off < 64; off <<= 1) {
-            const double o = __shfl_up(inc, off, 64), od = __shfl_up(incd, off, 64);
-            if (lane >= off) { inc += o; incd += od; }
-        }
-        if (lane == 63) { sh_scan[wave] = inc; sh_scan2[wave] = incd; }
-        __syncthreads();
-        double run = inc - loc, rund = incd - locd;
-        for (int i = 0; i < wave; ++i) { run += sh_scan[i]; rund += sh_scan2[i]; }
-        for (int i = 0; i < nwave; ++i) run += red_p[i];  // + E(0)
-        for (int q = i0; q < i1; ++q) {
-            Et[q] = run;
-            Cs[FC_XP(q)] = (float)rund;
-            const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
-            run += (a1.x * a1.x + a1.y * a1.y) - (b1.x * b1.x + b1.y * b1.y);
-            const double dr = a1.x - b1.x, di = a1.y - b1.y;
-            rund += (double)(__fsqrt_rn((float)(dr * dr + di * di)) * 1.00000095367431640625f);
-        }
-        if (i1 == nstep && i0 < nstep) { Et[nstep] = run; Cs[FC_XP(nstep)] = (float)rund; }
+        fc_scan_block(cv, th, nfft, sh);
         DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 5);
     }
-    // ---- slides: lane (c, j) walks chunk c of bin k; the 8 lanes of a group share the shift ----
     double best = -1.0;
     int bt = 0x7fffffff;
+    // ---- phase "slides", left inline: lane (c, j) walks chunk c of bin k; the 8 lanes of a group share the shift.  (As a function
+    // of its own the loop is optimised once more before it is inlined, and the vectoriser then packs the group sums of two steps:
+    // 18 of the 27 v_add_f32_dpp become v_mov_b32_dpp + v_pk_add_f32, nine vector instructions more per eight steps of the chain's
+    // hottest loop -- profiles/fine_cert_phases.md.) ----
     if (act) {                                            // (uniform per 8-lane group)
+        cplx* xs = fc_at<cplx>(cv.xs);
+        float* sumS = fc_at<float>(cv.sumS);
         const cplx wk = tw_g[k];                          // exp(-2 pi i k/nfft): the recurrence turns by its conjugate
         const double wr = wk.x, wi = -wk.y;
         const int t0 = c * FS_CHUNK;
@@ -2312,104 +2478,20 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
     }
     FC_ROLE_STAMP(0, 14);
     int bk = k;
-    for (int off = 32; off > 0; off >>= 1) {
-        const double op = __shfl_down(best, off, 64);
-        const int ot = __shfl_down(bt, off, 64);
-        const int ok = __shfl_down(bk, off, 64);
-        if (op > best || (op == best && (ot < bt || (ot == bt && ok < bk)))) { best = op; bt = ot; bk = ok; }
-    }
+    fc_wave_best(best, bt, bk);
     __syncthreads();                                      // the join of the roles (without the split: red_p was E(0) until here)
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 6);
-    if (lane == 0) { red_p[wave] = best; red_t[wave] = bt; red_k[wave] = bk; }
-    __syncthreads();
-    best = red_p[0]; bt = red_t[0]; bk = red_k[0];
-    for (int i = 1; i < nwave; ++i)
-        if (red_p[i] > best || (red_p[i] == best && (red_t[i] < bt || (red_t[i] == bt && red_k[i] < bk)))) {
-            best = red_p[i]; bt = red_t[i]; bk = red_k[i];
-        }
-    // ---- certificate per shift.  Two bounds on every bin outside S:
-    //   Parseval at the shift itself:            |X_k(t)| <= s(t) = sqrt(R(t))
-    //   the recurrence from any other shift t':  |X_k(t)| <= s(t') + |C(t) - C(t')|   (each step adds at most |d_q|)
-    // so U(t) = min( C(t) + min_{t'<=t}(s(t') - C(t')),  -C(t) + min_{t'>=t}(s(t') + C(t')) ) and shift t is certified
-    // when U(t) < sqrt(P*).  fp32 group sums: each of the 8 terms and 7 additions errs by <= 2^-24 relative, all
-    // terms are <= N*E(t), so |sumS - exact| < 2e-6 * N*E(t); the margins cover that, the fp32 storage of s and C
-    // and the fp64 rounding of E and P.
-    {
-        const double INF = __longlong_as_double(0x7ff0000000000000LL);
-        const double sb = best > 0.0 ? sqrt(best) * (1.0 - 1e-9) : -1.0;
-        const int per = (nstep + nthr) / nthr;            // >= ceil((nstep+1)/nthr)
-        const int u0 = tid * per < nstep + 1 ? tid * per : nstep + 1, u1 = u0 + per < nstep + 1 ? u0 + per : nstep + 1;
-        double mf = INF, mb = INF;
-        for (int t = u0; t < u1; ++t) {
-            const double NE = (double)nfft * Et[t];
-            const float ss = sumS[FC_XP(t)];
-            const double R = NE - (double)ss + 4e-6 * NE;
-            // (fp32 square root: s(t) is stored in fp32 anyway; the 1e-6 margin covers both roundings, < 2^-22 together)
-            float sf = ss <= 3.0e38f ? __fsqrt_rn((float)(R > 0.0 ? R : 0.0)) * 1.000001f : __int_as_float(0x7f800000);   // (an overflowed fp32 sum bounds nothing)
-            if (!(sf >= 0.0f)) sf = __int_as_float(0x7f800000);                  // NaN input
-            const double sv = (double)sf;
-            (void)sv;
-            sumS[FC_XP(t)] = sf;                          // own range only: s(t) replaces the group sum
-            const double cv = (double)Cs[FC_XP(t)];
-            mf = fmin(mf, (double)sf - cv);
-            mb = fmin(mb, (double)sf + cv);
-        }
-        double pf = mf, pb = mb;                          // inclusive prefix-min / suffix-min across the wave
-        for (int off = 1; off < 64; off <<= 1) {
-            const double o = __shfl_up(pf, off, 64), ob = __shfl_down(pb, off, 64);
-            if (lane >= off) pf = fmin(pf, o);
-            if (lane + off < 64) pb = fmin(pb, ob);
-        }
-        __syncthreads();                                  // sh_scan / sh_scan2 are free again
-        if (lane == 63) sh_scan[wave] = pf;
-        if (lane == 0) sh_scan2[wave] = pb;
-        double ef = __shfl_up(pf, 1, 64), eb = __shfl_down(pb, 1, 64);   // exclusive parts inside the wave
-        if (lane == 0) ef = INF;
-        if (lane == 63) eb = INF;
-        __syncthreads();
-        for (int i = 0; i < wave; ++i) ef = fmin(ef, sh_scan[i]);
-        for (int i = wave + 1; i < nwave; ++i) eb = fmin(eb, sh_scan2[i]);
-        const double ctot = (double)Cs[FC_XP(nstep)] * 1e-6;     // covers the fp32 rounding of the C(t) differences
-        unsigned okm = 0;                                 // per <= 32 for every supported geometry
-        for (int t = u0; t < u1; ++t) {
-            const double cv = (double)Cs[FC_XP(t)];
-            ef = fmin(ef, (double)sumS[FC_XP(t)] - cv);
-            if (cv + ef + ctot < sb) okm |= 1u << (t - u0);
-        }
-        for (int t = u1 - 1; t >= u0; --t) {
-            const double cv = (double)Cs[FC_XP(t)];
-            eb = fmin(eb, (double)sumS[FC_XP(t)] + cv);
-            const bool okc = ((okm >> (t - u0)) & 1u) || (eb - cv + ctot < sb);
-            if (!okc) {
-                if (t <= bt) atomicMax(&sh_a, t + 1);     // uncertified prefix [0, a)
-                if (t >= bt) atomicMin(&sh_b, t - 1);     // uncertified suffix (b, nstep]
-            }
-        }
-    }
+    fc_block_best(th, sh, best, bt, bk);
+    fc_certificate(cv, th, nfft, sh, best, bt);
     __syncthreads();
 #ifdef GSMCAL_AB_LAZY_WIN
-    if (fg.raw && OV > 0 && NTAPS == 47 && fg.sym47 != 0 && (sh_a != 0 || sh_b < nstep)) {      // (block-uniform) chunks stay open: k_fine_chunk / the exact pass read the window
+    if (fg.raw && OV > 0 && NTAPS == 47 && fg.sym47 != 0 && (sh.a != 0 || sh.b < cv.nstep)) {      // (block-uniform) chunks stay open: k_fine_chunk / the exact pass read the window
         cplx* wout = fg.win_out + (size_t)s * win_stream_stride + (size_t)w * win_stride;
-        for (int i = tid; i < wlen; i += nthr) wout[i] = xs[FC_XP(i)];
+        const cplx* xs = fc_at<cplx>(cv.xs);
+        for (int i = th.tid; i < cv.wlen; i += th.nthr) wout[i] = xs[FC_XP(i)];
     }
 #endif
-    if (tid == 0) {
-        FineCert o;
-        o.p = best; o.t = bt; o.k = bk; o.a = sh_a; o.b = sh_b;
-        // every uncertified shift lies in the prefix [0, a) or in the suffix (b, nstep] (the certificate's loop above): only
-        // the chunks that hold those are swept.  Chunk c holds shifts 64c+1 .. 64c+64 (+ shift 0 in chunk 0).  (Round 3: a
-        // window with any suffix open used to be swept whole -- 560 chunks instead of 165 on the 64 mixed streams of bench.py.)
-        const int a = sh_a, b = sh_b;
-        int npre = a == 0 ? 0 : (a == 1 ? 1 : (a - 2) / FS_CHUNK + 1);
-        int nsuf = b < nstep ? nchunk - b / FS_CHUNK : 0;  // shift b+1 is the first of the suffix: chunk b/64
-        if (npre + nsuf > nchunk) { npre = nchunk; nsuf = 0; }
-        o.nch = npre + nsuf; o.nsuf = nsuf;
-        cert[(size_t)s * H + w] = o;
-        if (o.nch > 0) {                                  // work list of k_fine_chunk
-            const int base = atomicAdd(n_items, o.nch);
-            for (int i = 0; i < o.nch; ++i) items[base + i] = ((s * H + w) << 8) | fc_open_chunk(i, o.nch, nsuf, nchunk);
-        }
-    }
+    if (th.tid == 0) fc_emit(cv, sh, best, bt, bk, s, H, w, cert, items, n_items);
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 7);
 }
 

@@ -430,6 +430,47 @@ __device__ __forceinline__ uint4 ffast_chunk(const unsigned short* __restrict__ 
     }
     return v;
 }
+// Staging a span [first, first + span) of raw samples by whole 16-byte chunks, one chunk per lane (k_fine_cert's window build,
+// k_stream_tile_s47): `ao` = samples past a 16-byte boundary at g = 0; raw_first_al() <= first is the sample the first chunk
+// starts at (its address is 16-byte aligned), so chunk `tid` is ffast_chunk(base, first_al + 8 * tid, n).
+__device__ __forceinline__ long raw_align_off(const unsigned short* base) { return (long)(((uintptr_t)base >> 1) & 7); }
+__device__ __forceinline__ long raw_first_al(long first, long ao) {
+    long m = (first + ao) % 8;
+    if (m < 0) m += 8;
+    return first - m;
+}
+__device__ __forceinline__ int xs_pad(int p);
+// raw2iq.m:6-8 from the registers: the eight samples of chunk `tid` (in `pre`) go to the xs_pad layout at xq, staged entry
+// i = 8*tid + u - off with off = first - first_al; (I - mean) + 1i (Q - mean), zeros outside the span and outside the stream [0, n).
+// Entries below 0 are never written, entries from `hi` on neither (the caller's bound: the zeros it wants behind the span).
+__device__ __forceinline__ void raw_chunk_to_lds(cplx* xq, const uint4 pre, int tid, int off, long first, int span, int hi, long n,
+                                                 double mr, double mi) {
+    const int i_base = 8 * tid - off;
+    const long g_base = first + i_base;
+    const unsigned wv[4] = {pre.x, pre.y, pre.z, pre.w};
+    if (i_base >= 0 && i_base + 8 <= span && g_base >= 0 && g_base + 8 <= n) {
+        // the usual chunk: all eight samples inside the span and the stream -- no per-sample tests (they were most of this loop).
+        // xs_pad(i_base + u) = xs_pad(i_base) + u + ((r + u) >> 2) with r = i_base & 3 = (-off) & 3, the same in every lane: the
+        // eight slots are one lane address plus scalar offsets (three vector instructions per slot before)
+        const int r = __builtin_amdgcn_readfirstlane((-off) & 3);
+        cplx* xp = xq + xs_pad(i_base);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const unsigned q = wv[u >> 1] >> (16 * (u & 1));
+            xp[u + ((r + u) >> 2)] = make_double2((double)(q & 0xFFu) - mr, (double)((q >> 8) & 0xFFu) - mi);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i_base + u;
+            const long g = first + i;
+            const unsigned q = (wv[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
+            cplx v = make_double2(0.0, 0.0);
+            if (i < span && g >= 0 && g < n) v = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
+            if (i >= 0 && i < hi) xq[xs_pad(i)] = v;
+        }
+    }
+}
 
 template <int NT, bool SYM>
 __global__ void __launch_bounds__(256) k_front_fast(const uint8_t* __restrict__ raw, long stream_bytes,
@@ -1312,13 +1353,10 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
     if (tid < ST_TPB) {
         if (tid < ntl) {
             const StRange r = st_range<TILE>(tile0 + tid, nq, n0, ln[2], f1, f3);
-            const long ao = (long)(((uintptr_t)base >> 1) & 7);  // samples past a 16-byte boundary at g = 0
             StTile t;
             t.lo0 = r.lo0; t.lo2 = r.lo2; t.lo3 = r.lo3; t.cnt0 = r.cnt0; t.cnt2 = r.cnt2; t.L4 = r.L4;
             t.first = r.lo0 - (ntp - 1);
-            long m = (t.first + ao) % 8;
-            if (m < 0) m += 8;
-            t.first_al = t.first - m;
+            t.first_al = raw_first_al(t.first, raw_align_off(base));
             t.nchunk = (int)((t.first + r.cnt0 + ntp - 1 - t.first_al + 7) >> 3);
             tl[tid] = t;
         }
@@ -1359,35 +1397,10 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
         const StTile c = tl[t];
         const int cnt0 = c.cnt0, cnt2 = c.cnt2, L4 = c.L4;
         const long lo0 = c.lo0, lo2 = c.lo2, lo3 = c.lo3, first = c.first;
-        {   // raw2iq.m:6-8 from the registers: staged sample i = 8*tid + u - (first - first_al); zeros outside the span / the stream
+        {   // raw2iq.m:6-8 from the registers; zeros outside the span / the stream
             const int span = cnt0 + ntp - 1, off = (int)(first - c.first_al);
             const int nconv = (off + span + 8 + 7) >> 3;        // (finite zeros behind the span: the last lanes' discarded outputs read them)
-            if (tid < nconv) {
-                const int i_base = 8 * tid - off;
-                const long g_base = first + i_base;
-                const unsigned wv[4] = {pre.x, pre.y, pre.z, pre.w};
-                if (i_base >= 0 && i_base + 8 <= span && g_base >= 0 && g_base + 8 <= n0) {
-                    // xs_pad(i_base + u) = xs_pad(i_base) + u + ((r + u) >> 2) with r = i_base & 3 = (-off) & 3, the same in every
-                    // lane: the eight slots are one lane address plus scalar offsets (three vector instructions per slot before)
-                    const int r = __builtin_amdgcn_readfirstlane((-off) & 3);
-                    cplx* xp = xs + xs_pad(i_base);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const unsigned q = wv[u >> 1] >> (16 * (u & 1));
-                        xp[u + ((r + u) >> 2)] = make_double2((double)(q & 0xFFu) - mr, (double)((q >> 8) & 0xFFu) - mi);
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int i = i_base + u;
-                        const long g = first + i;
-                        const unsigned q = (wv[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
-                        cplx v = make_double2(0.0, 0.0);
-                        if (i < span && g >= 0 && g < n0) v = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
-                        if (i >= 0) xs[xs_pad(i)] = v;
-                    }
-                }
-            }
+            if (tid < nconv) raw_chunk_to_lds(xs, pre, tid, off, first, span, 8 * nconv, n0, mr, mi);   // (every entry >= 0 of these chunks)
         }
         const cplx s2t = S2[t], s4t = S4[t];                    // the tile's S rotators (uniform reads)
         __syncthreads();                                        // xs complete
