@@ -1,8 +1,10 @@
 /* gsmcal_mex.c -- MEX gateway: lets gsm_sync_demod.m / multi_rtl_sdr_gsm_FCCH_scanner.m call the
  * MI355X kernels through the reference's own function names, unchanged.
  *
- * NOT compiled in the build image (no MATLAB, no mex.h); it is the binding a maintainer of the
- * reference would add.  Build one MEX file per function, named like the .m file it shadows, and put
+ * It is the binding a maintainer of the reference would add.  The project's suite builds and runs every target without MATLAB,
+ * in both complex-storage modes, against a working mxArray stand-in (tests/mex_stub/mxstub.c): tests/test_mex_gateway_cpu.py over
+ * a recording fake of the ABI, tests/test_gpu_mex_gateway.py over libgsmcal.so itself, held to the Python API bit for bit.
+ * Build one MEX file per function, named like the .m file it shadows, and put
  * the output directory ahead of the reference on the MATLAB path:
  *
  *   for f in raw2iq chn_filter_8x_4x chn_filter_4x move_fft_snr_runtime_avg specific_fft_snr_fix_avg \
@@ -18,7 +20,12 @@
  *   power_spectrum    = gsmcal_band_power(s_all, coef, decimate_ratio)          replaces ..split_scanner.m:154-156
  *   power             = gsmcal_subband_power(s, coef, phase_rotate)             replaces ..diversity_scanner_another_bak.m:192-204
  * with s the 2N x D uint8 matrix fread() delivers (gsm_sync_demod.m:96; pass uint8(s) if it was read as double).
- * tests/test_abi_cpu.py compiles every target against a declaration-only mex.h (tests/mex_stub) as a prototype check.
+ * tests/test_abi_cpu.py also compiles every target against the declaration-only mex.h (tests/mex_stub) as a prototype check.
+ *
+ * Every target decides its arguments before it touches the library: their number, their class (double unless said otherwise;
+ * raw2iq takes doubles or uint8) and the shapes it relies on; a call that fails this ends in a gsmcal:args / gsmcal:type error
+ * with the usage line, no context is created for it.  pos_info is R x 2, or the scalar -1 the .m files' `pos_info==-1` accepts
+ * as well (it is widened to [-1 -1]).
  *
  * Both MEX complex-storage APIs are handled: with -R2018a (MX_HAS_INTERLEAVED_COMPLEX = 1) complex arrays
  * are interleaved like the ABI's double[2] and are passed through without a copy; without the flag -- the only API of the
@@ -99,6 +106,52 @@ static const double* cplx_in(const mxArray* a, mwSize* n) {
 
 static mxArray* scalar(double v) { return mxCreateDoubleScalar(v); }
 
+/* ---- argument checks: decided before the library is touched ------------------------------------------------------ */
+static void usage(const char* line) { mexErrMsgIdAndTxt("gsmcal:args", "usage: %s", line); }
+#define ARGS(ok, line) do { if (!(ok)) usage(line); } while (0)
+/* The class of an input.  `mex` defines MATLAB_MEX_FILE for everything it builds, and MATLAB's mex.h has mxIsDouble.  Built
+ * any other way (a reduced mex.h that declares only the accessors: tests/mex_stub) the class is read off the typed accessors,
+ * which answer NULL for an array of another class -- mxGetDoubles / mxGetComplexDoubles do so in MATLAB itself. */
+#ifdef MATLAB_MEX_FILE
+static int is_dbl(const mxArray* a) { return mxIsDouble(a); }                                   /* real or complex doubles */
+#elif GSMCAL_INTERLEAVED
+static int is_dbl(const mxArray* a) { return mxGetDoubles(a) != NULL || mxGetComplexDoubles(a) != NULL; }
+#else
+static int is_dbl(const mxArray* a) { return !mxIsUint8(a) && mxGetPr(a) != NULL; }
+#endif
+static int is_real(const mxArray* a) { return is_dbl(a) && !mxIsComplex(a); }                   /* what REAL_PTR may be taken of */
+static int is_num(const mxArray* a) { return is_real(a) && mxGetNumberOfElements(a) == 1; }     /* what mxGetScalar is taken of */
+static int is_u8(const mxArray* a) { return mxIsUint8(a) && !mxIsComplex(a); }
+static int all_num(int nrhs, const mxArray* prhs[], int first) {
+    int k;
+    for (k = first; k < nrhs; ++k) if (!is_num(prhs[k])) return 0;
+    return 1;
+}
+/* the 2N x D uint8 matrix of a fused target -> D captures of 2*(*n) bytes one behind the other, as the ABI reads them.  An odd row
+ * count leaves a last byte without its partner in every column: N = floor(rows / 2), and the columns are copied without it --
+ * handed over as they are, every capture after the first would start one byte early per column before it. */
+static const uint8_t* raw_in(const mxArray* a, long* n) {
+    const mwSize rows = mxGetM(a), d = mxGetN(a);
+    const uint8_t* src = U8_PTR(a);
+    uint8_t* t;
+    mwSize i;
+    *n = (long)(rows / 2);
+    if (rows % 2 == 0 || d == 1) return src;
+    t = (uint8_t*)mxMalloc((rows - 1) * d);
+    for (i = 0; i < d; ++i) memcpy(t + i * (rows - 1), src + i * rows, rows - 1);
+    return t;
+}
+/* pos_info as the .m files take it: R x 2 real, or the scalar -1 that `pos_info==-1` accepts too -- the ABI reads two columns,
+ * so that one is widened to [-1 -1].  Returns the R x 2 column-major table (ld = *rows), NULL for anything else. */
+static const double* pos_in(const mxArray* a, int* rows) {
+    static const double m1[2] = {-1.0, -1.0};
+    if (!is_real(a)) return NULL;
+    if (mxGetNumberOfElements(a) == 1 && mxGetScalar(a) == -1.0) { *rows = 1; return m1; }
+    if (mxGetN(a) != 2 || mxGetM(a) < 1) return NULL;
+    *rows = (int)mxGetM(a);
+    return REAL_PTR(a);
+}
+
 /* m x n complex output the ABI fills as interleaved doubles: cplx_out_begin() gives the buffer to hand to the ABI,
  * cplx_out_end() the finished mxArray (interleaved API: the array's own storage, no copy; split API: de-interleaved) */
 typedef struct { mxArray* arr; double* buf; mwSize m, n; } cplx_out;
@@ -134,36 +187,53 @@ static mxArray* cplx_col(const double* data, mwSize n) {   /* n x 1 complex colu
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #if defined(GSMCAL_FN_raw2iq)
-    /* b = raw2iq(a)                                   raw2iq.m:5 */
-    mwSize rows = mxGetM(prhs[0]), d = mxGetN(prhs[0]);
+    /* b = raw2iq(a)                                   raw2iq.m:5
+     * a: 2N x D byte values, as doubles (the reference) or as the uint8 matrix fread(...,'uint8') delivers */
+    mwSize rows, d;
     cplx_out o;
-    double* b = cplx_out_begin(&o, rows / 2, d);
-    chk(gsmcal_raw2iq(ctx(), REAL_PTR(prhs[0]), (long)rows, (int)d, b), "raw2iq");
+    double* b;
+    ARGS(nrhs == 1 && nlhs <= 1 && (is_real(prhs[0]) || is_u8(prhs[0])) && mxGetNumberOfElements(prhs[0]) >= 2,
+         "b = raw2iq(a) with a 2N x D real doubles or uint8");
+    rows = mxGetM(prhs[0]); d = mxGetN(prhs[0]);
+    b = cplx_out_begin(&o, rows / 2, d);
+    if (is_u8(prhs[0])) chk(gsmcal_raw2iq_u8(ctx(), U8_PTR(prhs[0]), (long)rows, (int)d, b), "raw2iq");
+    else chk(gsmcal_raw2iq(ctx(), REAL_PTR(prhs[0]), (long)rows, (int)d, b), "raw2iq");
     plhs[0] = cplx_out_end(&o);
 
 #elif defined(GSMCAL_FN_chn_filter_8x_4x)
     /* r = chn_filter_8x_4x(s)                         chn_filter_8x_4x.m:5 */
-    mwSize n = mxGetM(prhs[0]), d = mxGetN(prhs[0]), tot;
-    const double* s = cplx_in(prhs[0], &tot);
+    mwSize n, d, tot;
+    const double* s;
     cplx_out o;
-    double* b = cplx_out_begin(&o, (n + 1) / 2, d);
+    double* b;
+    ARGS(nrhs == 1 && nlhs <= 1 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1, "r = chn_filter_8x_4x(s) with s N x D doubles");
+    n = mxGetM(prhs[0]); d = mxGetN(prhs[0]);
+    s = cplx_in(prhs[0], &tot);
+    b = cplx_out_begin(&o, (n + 1) / 2, d);
     chk(gsmcal_chn_filter_8x_4x(ctx(), s, (long)n, (int)d, NULL, 0, b), "chn_filter_8x_4x");
     plhs[0] = cplx_out_end(&o);
 
 #elif defined(GSMCAL_FN_chn_filter_4x)
     /* r = chn_filter_4x(s)                            chn_filter_4x.m:5 */
-    mwSize n = mxGetM(prhs[0]), d = mxGetN(prhs[0]), tot;
-    const double* s = cplx_in(prhs[0], &tot);
+    mwSize n, d, tot;
+    const double* s;
     cplx_out o;
-    double* b = cplx_out_begin(&o, n, d);
+    double* b;
+    ARGS(nrhs == 1 && nlhs <= 1 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1, "r = chn_filter_4x(s) with s N x D doubles");
+    n = mxGetM(prhs[0]); d = mxGetN(prhs[0]);
+    s = cplx_in(prhs[0], &tot);
+    b = cplx_out_begin(&o, n, d);
     chk(gsmcal_chn_filter_4x(ctx(), s, (long)n, (int)d, NULL, 0, b), "chn_filter_4x");
     plhs[0] = cplx_out_end(&o);
 
 #elif defined(GSMCAL_FN_move_fft_snr_runtime_avg)
     /* [hit_flag,hit_idx,hit_avg_snr,hit_snr] = move_fft_snr_runtime_avg(s,mv_len,fft_len,th) */
     mwSize n;
-    const double* s = cplx_in(prhs[0], &n);
+    const double* s;
     int hf; double hi, ha, hs;
+    ARGS(nrhs == 4 && nlhs <= 4 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && all_num(nrhs, prhs, 1),
+         "[hit_flag,hit_idx,hit_avg_snr,hit_snr] = move_fft_snr_runtime_avg(s,mv_len,fft_len,th)");
+    s = cplx_in(prhs[0], &n);
     chk(gsmcal_move_fft_snr_runtime_avg(ctx(), s, (long)n, (int)mxGetScalar(prhs[1]), (int)mxGetScalar(prhs[2]),
                                         mxGetScalar(prhs[3]), &hf, &hi, &ha, &hs), "move_fft_snr_runtime_avg");
     plhs[0] = mxCreateLogicalScalar(hf != 0);
@@ -174,8 +244,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #elif defined(GSMCAL_FN_specific_fft_snr_fix_avg)
     /* [hit_flag,hit_idx,hit_snr] = specific_fft_snr_fix_avg(s,target_set,fft_len,th,avg_snr) */
     mwSize n;
-    const double* s = cplx_in(prhs[0], &n);
+    const double* s;
     int hf; double hi, hs;
+    ARGS(nrhs == 5 && nlhs <= 3 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && is_real(prhs[1]) &&
+         mxGetNumberOfElements(prhs[1]) >= 2 && all_num(nrhs, prhs, 2),
+         "[hit_flag,hit_idx,hit_snr] = specific_fft_snr_fix_avg(s,target_set,fft_len,th,avg_snr) with target_set of two elements");
+    s = cplx_in(prhs[0], &n);
     chk(gsmcal_specific_fft_snr_fix_avg(ctx(), s, (long)n, REAL_PTR(prhs[1]), (int)mxGetScalar(prhs[2]),
                                         mxGetScalar(prhs[3]), mxGetScalar(prhs[4]), &hf, &hi, &hs),
         "specific_fft_snr_fix_avg");
@@ -186,9 +260,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #elif defined(GSMCAL_FN_FCCH_coarse_position)
     /* [position,snr] = FCCH_coarse_position(s,decimation_ratio)     (row vectors; -1,-1 when none) */
     mwSize n;
-    const double* s = cplx_in(prhs[0], &n);
+    const double* s;
     double pos[GSMCAL_MAX_HITS], snr[GSMCAL_MAX_HITS];
     int cnt = 0;
+    ARGS(nrhs == 2 && nlhs <= 2 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && is_num(prhs[1]),
+         "[position,snr] = FCCH_coarse_position(s,decimation_ratio)");
+    s = cplx_in(prhs[0], &n);
     chk(gsmcal_FCCH_coarse_position(ctx(), s, (long)n, (int)mxGetScalar(prhs[1]), pos, snr, GSMCAL_MAX_HITS, &cnt),
         "FCCH_coarse_position");
     say();
@@ -199,10 +276,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #elif defined(GSMCAL_FN_FCCH_fine_correction)
     /* [FCCH_pos,r,sampling_ppm,carrier_ppm] = FCCH_fine_correction(s,base_position,ov,carrier_freq) */
     mwSize n;
-    const double* s = cplx_in(prhs[0], &n);
+    const double* s;
     double pos[GSMCAL_MAX_HITS], sp, cp;
     int npos = 0; long lr = -1;
-    double* r = (double*)mxMalloc(2 * n * sizeof(double));
+    double* r;
+    ARGS(nrhs == 4 && nlhs <= 4 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && is_real(prhs[1]) &&
+         mxGetNumberOfElements(prhs[1]) >= 1 && all_num(nrhs, prhs, 2),
+         "[FCCH_pos,r,sampling_ppm,carrier_ppm] = FCCH_fine_correction(s,base_position,ov,carrier_freq)");
+    s = cplx_in(prhs[0], &n);
+    r = (double*)mxMalloc(2 * n * sizeof(double));
     chk(gsmcal_FCCH_fine_correction(ctx(), s, (long)n, REAL_PTR(prhs[1]), (int)mxGetNumberOfElements(prhs[1]),
                                     (int)mxGetScalar(prhs[2]), mxGetScalar(prhs[3]), pos, GSMCAL_MAX_HITS, &npos,
                                     r, (long)n, &lr, &sp, &cp), "FCCH_fine_correction");
@@ -217,11 +299,16 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #elif defined(GSMCAL_FN_SCH_corr_rate_correction)
     /* [pos_info,r,sampling_ppm] = SCH_corr_rate_correction(s,FCCH_pos,sch_training_sequence,ov) */
     mwSize n = 0, nts;
-    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;   /* r = -1 upstream */
-    const double* ts = cplx_in(prhs[2], &nts);
+    const double *s, *ts;
     double pi[2 * GSMCAL_MAX_POS_ROWS], sp;
     int rows = 0, i; long lr = -1;
-    double* r = n ? (double*)mxMalloc(2 * n * sizeof(double)) : NULL;
+    double* r;
+    ARGS(nrhs == 4 && nlhs <= 3 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && is_real(prhs[1]) &&
+         mxGetNumberOfElements(prhs[1]) >= 1 && is_dbl(prhs[2]) && mxGetNumberOfElements(prhs[2]) >= 1 && is_num(prhs[3]),
+         "[pos_info,r,sampling_ppm] = SCH_corr_rate_correction(s,FCCH_pos,sch_training_sequence,ov)");
+    s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;   /* r = -1 upstream */
+    ts = cplx_in(prhs[2], &nts);
+    r = n ? (double*)mxMalloc(2 * n * sizeof(double)) : NULL;
     chk(gsmcal_SCH_corr_rate_correction(ctx(), s, (long)n, REAL_PTR(prhs[1]), (int)mxGetNumberOfElements(prhs[1]),
                                         ts, (int)nts, (int)mxGetScalar(prhs[3]), pi, GSMCAL_MAX_POS_ROWS, &rows,
                                         r, (long)n, &lr, &sp), "SCH_corr_rate_correction");
@@ -238,11 +325,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #elif defined(GSMCAL_FN_carrier_correct_post_SCH)
     /* [r,carrier_ppm] = carrier_correct_post_SCH(s,pos_info,ov,carrier_freq) */
     mwSize n = 0;
-    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
-    int rows = (int)mxGetM(prhs[1]);
+    const double *s, *pin = NULL;
+    int rows = 0;
     double cp; long lr = -1;
-    double* r = n ? (double*)mxMalloc(2 * n * sizeof(double)) : NULL;
-    chk(gsmcal_carrier_correct_post_SCH(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, (int)mxGetScalar(prhs[2]),
+    double* r;
+    ARGS(nrhs == 4 && nlhs <= 2 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && (pin = pos_in(prhs[1], &rows)) != NULL &&
+         all_num(nrhs, prhs, 2), "[r,carrier_ppm] = carrier_correct_post_SCH(s,pos_info,ov,carrier_freq) with pos_info R x 2 (or -1)");
+    s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    r = n ? (double*)mxMalloc(2 * n * sizeof(double)) : NULL;
+    chk(gsmcal_carrier_correct_post_SCH(ctx(), s, (long)n, pin, rows, rows, (int)mxGetScalar(prhs[2]),
                                         mxGetScalar(prhs[3]), r, (long)n, &lr, &cp), "carrier_correct_post_SCH");
     say();
     plhs[0] = lr < 0 ? scalar(-1.0) : cplx_col(r, (mwSize)lr);
@@ -254,10 +345,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * also hands the printed figures back: [freq, snr, max_idx, carrier_ppm] = FCCH_demod(...), rows of num_fcch entries with
      * max_idx the offset of :66.  At the :8 exit (pos_info == -1) the outputs are empty and carrier_ppm is NaN. */
     mwSize n = 0, i;
-    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
-    int rows = (int)mxGetM(prhs[1]), nb = 0;
+    const double *s, *pin = NULL;
+    int rows = 0, nb = 0;
     double v[3 * GSMCAL_MAX_HITS], mf, cp;
-    chk(gsmcal_FCCH_demod(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, (int)mxGetScalar(prhs[2]), mxGetScalar(prhs[3]),
+    ARGS(nrhs == 4 && nlhs <= 4 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && (pin = pos_in(prhs[1], &rows)) != NULL &&
+         all_num(nrhs, prhs, 2), "[freq, snr, max_idx, carrier_ppm] = FCCH_demod(s,pos_info,ov,carrier_freq) with pos_info R x 2 (or -1)");
+    s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    chk(gsmcal_FCCH_demod(ctx(), s, (long)n, pin, rows, rows, (int)mxGetScalar(prhs[2]), mxGetScalar(prhs[3]),
                           v, v + GSMCAL_MAX_HITS, v + 2 * GSMCAL_MAX_HITS, GSMCAL_MAX_HITS, &nb, &mf, &cp), "FCCH_demod");
     say();
     for (i = 0; i < 3 && (int)i < nlhs; ++i) {
@@ -273,18 +367,21 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * gsm_normal_training_sequence_gen(ov) (26*ov x 8 complex, :97) the third.  Prints the lines of :15,69,72,101,104; the three
      * outputs are the variables of :6-8 (-1 at the :9 and :14 exits), corr_val the 8 x 4 matrix of :97 (empty at those exits). */
     mwSize n = 0, nt = 0;
-    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
-    const double* ts;
-    int rows = (int)mxGetM(prhs[1]), idx = -1, rc;
+    const double *s, *ts, *pin = NULL;
+    int rows = 0, idx = -1, rc;
     double cp = -1.0; long lr = -1;
-    double* r = n ? (double*)mxMalloc(2 * n * sizeof(double)) : NULL;
+    double* r;
     cplx_out cv;
     double* cvb;
-    if (nrhs < 5 || mxGetN(prhs[2]) != 8)
-        mexErrMsgIdAndTxt("gsmcal:args", "usage: [idx, r, carrier_ppm] = BCCH_demod(s, pos_info, normal_training_sequence, ov, carrier_freq)");
+    ARGS(nrhs == 5 && nlhs <= 4 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && (pin = pos_in(prhs[1], &rows)) != NULL &&
+         is_dbl(prhs[2]) && mxGetN(prhs[2]) == 8 && mxGetM(prhs[2]) >= 1 && all_num(nrhs, prhs, 3),
+         "[idx, r, carrier_ppm, corr_val] = BCCH_demod(s, pos_info, normal_training_sequence, ov, carrier_freq) with pos_info R x 2 (or -1) "
+         "and normal_training_sequence 26*ov x 8");
+    s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    r = n ? (double*)mxMalloc(2 * n * sizeof(double)) : NULL;
     ts = cplx_in(prhs[2], &nt);
     cvb = cplx_out_begin(&cv, 8, 4);
-    rc = gsmcal_BCCH_demod(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, ts, (int)mxGetM(prhs[2]), (int)mxGetScalar(prhs[3]),
+    rc = gsmcal_BCCH_demod(ctx(), s, (long)n, pin, rows, rows, ts, (int)mxGetM(prhs[2]), (int)mxGetScalar(prhs[3]),
                            mxGetScalar(prhs[4]), &idx, r, (long)n, &lr, &cp, cvb, NULL);
     chk(rc, "BCCH_demod");
     say();
@@ -303,14 +400,16 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * when fewer than two SCH bursts decode consistently or pos_info == -1), then per SCH burst the frame number and the ok flag
      * (rows of num_sch entries, NaN where a burst was not decoded).  Prints the call's report lines. */
     mwSize n = 0, nt = 0, k;
-    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
-    const double* ts;
-    int rows = (int)mxGetM(prhs[1]), bsic = -1, nb, rc;
+    const double *s, *ts, *pin = NULL;
+    int rows = 0, bsic = -1, nb, rc;
     long fn = -1, pos = -1;
     double row[GSMCAL_SCH_COLS];
-    if (nrhs < 4) mexErrMsgIdAndTxt("gsmcal:args", "usage: [bsic, fn_anchor, pos_anchor, fn, ok] = SCH_decode(s, pos_info, sch_training_sequence, ov)");
+    ARGS(nrhs == 4 && nlhs <= 5 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && (pin = pos_in(prhs[1], &rows)) != NULL &&
+         is_dbl(prhs[2]) && mxGetNumberOfElements(prhs[2]) >= 1 && is_num(prhs[3]),
+         "[bsic, fn_anchor, pos_anchor, fn, ok] = SCH_decode(s, pos_info, sch_training_sequence, ov) with pos_info R x 2 (or -1)");
+    s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
     ts = cplx_in(prhs[2], &nt);
-    rc = gsmcal_SCH_decode(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, ts, (int)nt, (int)mxGetScalar(prhs[3]), &bsic, &fn, &pos,
+    rc = gsmcal_SCH_decode(ctx(), s, (long)n, pin, rows, rows, ts, (int)nt, (int)mxGetScalar(prhs[3]), &bsic, &fn, &pos,
                            row, NULL, NULL);
     chk(rc, "SCH_decode");
     say();
@@ -334,13 +433,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * type 1..4 (0: not recognised, -1: no block decoded or pos_info == -1); then the blocks as a num_blocks x 23 matrix of octets
      * (zero rows where a block failed) and the ok flag per block (NaN where it was not evaluated).  Prints the report lines. */
     mwSize n = 0, k, j;
-    const double* s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
-    int rows = (int)mxGetM(prhs[1]), nb, rc;
+    const double *s, *pin = NULL;
+    int rows = 0, nb, rc;
     double row[GSMCAL_SI_COLS];
     unsigned char oct[GSMCAL_MAX_HITS * GSMCAL_BLOCK_OCTETS];
     gsmcal_si_info si;
-    if (nrhs < 4) mexErrMsgIdAndTxt("gsmcal:args", "usage: [cell_id, lai, si_type, octets, ok] = BCCH_decode(s, pos_info, tsc, ov)");
-    rc = gsmcal_BCCH_decode(ctx(), s, (long)n, REAL_PTR(prhs[1]), rows, rows, (int)mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]), oct,
+    ARGS(nrhs == 4 && nlhs <= 5 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && (pin = pos_in(prhs[1], &rows)) != NULL &&
+         all_num(nrhs, prhs, 2), "[cell_id, lai, si_type, octets, ok] = BCCH_decode(s, pos_info, tsc, ov) with pos_info R x 2 (or -1)");
+    s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
+    rc = gsmcal_BCCH_decode(ctx(), s, (long)n, pin, rows, rows, (int)mxGetScalar(prhs[2]), (int)mxGetScalar(prhs[3]), oct,
                             row, NULL, &si);
     chk(rc, "BCCH_decode");
     say();
@@ -369,7 +470,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mwSize n = 0;
     const double* s;
     double pr;
-    if (nrhs < 1 || mxGetNumberOfElements(prhs[0]) < 2) mexErrMsgIdAndTxt("gsmcal:args", "usage: r = CW_check(s) with at least two samples");
+    ARGS(nrhs == 1 && nlhs <= 2 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 2, "r = CW_check(s) with at least two samples");
     s = cplx_in(prhs[0], &n);
     plhs[0] = mxCreateDoubleMatrix(n - 1, 1, mxREAL);
     chk(gsmcal_CW_check(ctx(), s, (long)n, REAL_PTR(plhs[0]), &pr), "CW_check");
@@ -382,7 +483,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mwSize n = 0, k;
     const double* s;
     double row[GSMCAL_IQ_COLS];
-    if (nrhs < 1 || mxGetNumberOfElements(prhs[0]) < 1) mexErrMsgIdAndTxt("gsmcal:args", "usage: gain = IQ_imbalance(s) with at least one sample");
+    ARGS(nrhs == 1 && nlhs <= 4 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1,
+         "[gain, phase_deg, irr_db, row] = IQ_imbalance(s) with at least one sample");
     s = cplx_in(prhs[0], &n);
     chk(gsmcal_IQ_imbalance(ctx(), s, (long)n, row), "IQ_imbalance");
     say();
@@ -401,15 +503,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * the delay in ppm (NaN when fewer than two bursts are used or pos_info == -1) and the whole 1 x GSMCAL_PAIR_COLS row (columns:
      * GSMCAL_P_*).  lag0 defaults to 0, max_lag to 2*ov, min_coherence to 0.5.  Prints the report lines. */
     mwSize na = 0, nb = 0, k;
-    const double *sa, *sb;
-    int rows, rc;
+    const double *sa, *sb, *pin = NULL;
+    int rows = 0, rc;
     double* row;
-    if (nrhs < 4) mexErrMsgIdAndTxt("gsmcal:args", "usage: [delay0, rel_carrier_hz, phase0, mean_coherence, rel_sampling_ppm, row] = pair_coherence(s_a, s_b, pos_info_a, ov, lag0, max_lag, min_coherence)");
+    ARGS(nrhs >= 4 && nrhs <= 7 && nlhs <= 6 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && is_dbl(prhs[1]) &&
+         mxGetNumberOfElements(prhs[1]) >= 1 && (pin = pos_in(prhs[2], &rows)) != NULL && all_num(nrhs, prhs, 3),
+         "[delay0, rel_carrier_hz, phase0, mean_coherence, rel_sampling_ppm, row] = pair_coherence(s_a, s_b, pos_info_a, ov, lag0, max_lag, "
+         "min_coherence) with pos_info_a R x 2 (or -1)");
     sa = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &na) : NULL;
     sb = mxGetNumberOfElements(prhs[1]) > 1 ? cplx_in(prhs[1], &nb) : NULL;
-    rows = (int)mxGetM(prhs[2]);
     row = (double*)mxCalloc(GSMCAL_PAIR_COLS, sizeof(double));
-    rc = gsmcal_pair_coherence(ctx(), sa, (long)na, sb, (long)nb, REAL_PTR(prhs[2]), rows, rows, (int)mxGetScalar(prhs[3]),
+    rc = gsmcal_pair_coherence(ctx(), sa, (long)na, sb, (long)nb, pin, rows, rows, (int)mxGetScalar(prhs[3]),
                                nrhs > 4 ? (int)mxGetScalar(prhs[4]) : 0, nrhs > 5 ? (int)mxGetScalar(prhs[5]) : 0,
                                nrhs > 6 ? mxGetScalar(prhs[6]) : 0.5, row, NULL);
     chk(rc, "pair_coherence");
@@ -436,8 +540,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     double info[GSMCAL_ALIGN_INFO_COLS];
     double* out;
     long out_len;
-    if (nrhs < 3 || mxGetNumberOfElements(prhs[2]) != GSMCAL_ALIGN_PARAMS)
-        mexErrMsgIdAndTxt("gsmcal:args", "usage: [out, info] = pair_align(s, ov, [delay slope_ppm carrier_hz phase anchor weight], out_len)");
+    ARGS(nrhs >= 3 && nrhs <= 4 && nlhs <= 2 && is_dbl(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1 && is_num(prhs[1]) &&
+         is_real(prhs[2]) && mxGetNumberOfElements(prhs[2]) == GSMCAL_ALIGN_PARAMS && all_num(nrhs, prhs, 3),
+         "[out, info] = pair_align(s, ov, [delay slope_ppm carrier_hz phase anchor weight], out_len)");
     s = mxGetNumberOfElements(prhs[0]) > 1 ? cplx_in(prhs[0], &n) : NULL;
     out_len = nrhs > 3 ? (long)mxGetScalar(prhs[3]) : (long)n;
     if (out_len < 1) mexErrMsgIdAndTxt("gsmcal:args", "pair_align: out_len must be at least 1");
@@ -454,22 +559,35 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #elif defined(GSMCAL_FN_total_ppm_calculation)
     /* ppm_out = total_ppm_calculation(ppm_in) */
     double out;
-    if (gsmcal_total_ppm_calculation(REAL_PTR(prhs[0]), (int)mxGetNumberOfElements(prhs[0]), &out) == GSMCAL_S_ALL_INF)
-        mexPrintf("total PPM calculation: No valid PPM input!\n");          /* total_ppm_calculation.m:8 */
+    ARGS(nrhs == 1 && nlhs <= 1 && is_real(prhs[0]) && mxGetNumberOfElements(prhs[0]) >= 1, "ppm_out = total_ppm_calculation(ppm_in)");
+    {
+        const int rc = gsmcal_total_ppm_calculation(REAL_PTR(prhs[0]), (int)mxGetNumberOfElements(prhs[0]), &out);
+        chk(rc, "total_ppm_calculation");                                   /* host arithmetic: no context is made for it */
+        if (rc == GSMCAL_S_ALL_INF) mexPrintf("total PPM calculation: No valid PPM input!\n");          /* total_ppm_calculation.m:8 */
+    }
     plhs[0] = scalar(out);
 #elif defined(GSMCAL_FN_gsmcal_calibrate)
     /* [table, pos_info] = gsmcal_calibrate(s, coef, sch_training_sequence, freq)      gsm_sync_demod.m:107-124 for all dongles
      * s: 2N x D uint8 (column = one dongle's interleaved I,Q bytes, exactly the ABI's capture-major layout);
      * table: D x 10 (columns: GSMCAL_T_*); pos_info: 1 x D cell, pos_info{i} = R x 2 (or the all -1 sentinel) */
-    mwSize rows2n = mxGetM(prhs[0]), d = mxGetN(prhs[0]), nts, i, k;
-    const double* ts = cplx_in(prhs[2], &nts);
-    const mwSize ncf = mxGetNumberOfElements(prhs[3]);
-    double* cf = (double*)mxMalloc(d * sizeof(double));
-    double* tab = (double*)mxMalloc(d * GSMCAL_TABLE_COLS * sizeof(double));
-    double* pi = (double*)mxMalloc(d * 2 * GSMCAL_MAX_POS_ROWS * sizeof(double));
-    if (!mxIsUint8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s must be uint8 (the bytes fread(...,'uint8') delivers)");
+    mwSize rows2n, d, nts, ncf, i, k;
+    long n2 = 0;
+    const uint8_t* raw;
+    const double* ts;
+    double *cf, *tab, *pi;
+    ARGS(nrhs == 4 && nlhs <= 2, "[table, pos_info] = gsmcal_calibrate(s, coef, sch_training_sequence, freq)");
+    if (!is_u8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s must be uint8 (the bytes fread(...,'uint8') delivers)");
+    rows2n = mxGetM(prhs[0]); d = mxGetN(prhs[0]); ncf = mxGetNumberOfElements(prhs[3]);
+    ARGS(rows2n >= 2 && d >= 1 && is_real(prhs[1]) && mxGetNumberOfElements(prhs[1]) >= 1 && is_dbl(prhs[2]) &&
+         mxGetNumberOfElements(prhs[2]) >= 1 && is_real(prhs[3]) && (ncf == 1 || ncf == d),
+         "[table, pos_info] = gsmcal_calibrate(s, coef, sch_training_sequence, freq) with freq a scalar or one value per column of s");
+    raw = raw_in(prhs[0], &n2);
+    ts = cplx_in(prhs[2], &nts);
+    cf = (double*)mxMalloc(d * sizeof(double));
+    tab = (double*)mxMalloc(d * GSMCAL_TABLE_COLS * sizeof(double));
+    pi = (double*)mxMalloc(d * 2 * GSMCAL_MAX_POS_ROWS * sizeof(double));
     for (i = 0; i < d; ++i) cf[i] = REAL_PTR(prhs[3])[ncf == d ? i : 0];
-    chk(gsmcal_calibrate_batch(ctx(), U8_PTR(prhs[0]), (int)d, (long)(rows2n / 2), REAL_PTR(prhs[1]),
+    chk(gsmcal_calibrate_batch(ctx(), raw, (int)d, n2, REAL_PTR(prhs[1]),
                                (int)mxGetNumberOfElements(prhs[1]), ts, (int)nts, cf, tab, pi, NULL, NULL), "gsmcal_calibrate");
     plhs[0] = mxCreateDoubleMatrix(d, GSMCAL_TABLE_COLS, mxREAL);
     for (i = 0; i < d; ++i)
@@ -477,7 +595,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nlhs > 1) {
         plhs[1] = mxCreateCellMatrix(1, d);
         for (i = 0; i < d; ++i) {
-            const mwSize r = (mwSize)tab[i * GSMCAL_TABLE_COLS + GSMCAL_T_N_POS_ROWS];
+            const double nr = tab[i * GSMCAL_TABLE_COLS + GSMCAL_T_N_POS_ROWS];
+            const mwSize r = nr >= 0.0 && nr <= GSMCAL_MAX_POS_ROWS ? (mwSize)nr : 0;
             mxArray* m = mxCreateDoubleMatrix(r, 2, mxREAL);
             for (k = 0; k < r; ++k) {
                 REAL_PTR(m)[k] = pi[i * 2 * GSMCAL_MAX_POS_ROWS + k];
@@ -491,12 +610,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
 #elif defined(GSMCAL_FN_gsmcal_fcch_scan)
     /* [snr, num_hit] = gsmcal_fcch_scan(s, coef)      multi_rtl_sdr_gsm_FCCH_scanner.m:132-135,163-186 for all captures
      * s: 2N x F uint8, one column per (dongle, frequency) capture in the order of s_all (:135); snr, num_hit: 1 x F */
-    mwSize rows2n = mxGetM(prhs[0]), f = mxGetN(prhs[0]);
-    if (!mxIsUint8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s must be uint8 (the bytes fread(...,'uint8') delivers)");
+    mwSize rows2n, f;
+    long n2 = 0;
+    const uint8_t* raw;
+    ARGS(nrhs == 2 && nlhs <= 2, "[snr, num_hit] = gsmcal_fcch_scan(s, coef)");
+    if (!is_u8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s must be uint8 (the bytes fread(...,'uint8') delivers)");
+    rows2n = mxGetM(prhs[0]); f = mxGetN(prhs[0]);
+    ARGS(rows2n >= 2 && f >= 1 && is_real(prhs[1]) && mxGetNumberOfElements(prhs[1]) >= 1, "[snr, num_hit] = gsmcal_fcch_scan(s, coef) with real taps");
+    raw = raw_in(prhs[0], &n2);
     plhs[0] = mxCreateDoubleMatrix(1, f, mxREAL);
     {
         mxArray* nh = mxCreateDoubleMatrix(1, f, mxREAL);
-        chk(gsmcal_fcch_scan_batch(ctx(), U8_PTR(prhs[0]), (int)f, (long)(rows2n / 2), REAL_PTR(prhs[1]),
+        chk(gsmcal_fcch_scan_batch(ctx(), raw, (int)f, n2, REAL_PTR(prhs[1]),
                                    (int)mxGetNumberOfElements(prhs[1]), REAL_PTR(plhs[0]), REAL_PTR(nh), NULL, NULL, NULL),
             "gsmcal_fcch_scan");
         if (nlhs > 1) plhs[1] = nh;
@@ -505,11 +630,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     /* power = gsmcal_band_power(s_all, coef, decimate_ratio)     multi_rtl_sdr_split_scanner.m:154-156 (diversity_scanner.m:
      * 156-158 per dongle) for all captures: mean(abs(r_flt(1:decimate_ratio:end,:)).^2, 1) with r_flt = filter(coef,1,raw2iq(s_all))
      * s_all: 2N x D uint8, one column per capture; coef: real taps; power: 1 x D linear */
-    mwSize rows2n = mxGetM(prhs[0]), d = mxGetN(prhs[0]);
-    if (!mxIsUint8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s_all must be uint8 (the bytes fread(...,'uint8') delivers)");
-    if (nrhs < 3 || mxIsComplex(prhs[1])) mexErrMsgIdAndTxt("gsmcal:args", "usage: power = gsmcal_band_power(s_all, coef, decimate_ratio)");
+    mwSize rows2n, d;
+    long n2 = 0;
+    const uint8_t* raw;
+    ARGS(nrhs == 3 && nlhs <= 1, "power = gsmcal_band_power(s_all, coef, decimate_ratio)");
+    if (!is_u8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s_all must be uint8 (the bytes fread(...,'uint8') delivers)");
+    rows2n = mxGetM(prhs[0]); d = mxGetN(prhs[0]);
+    ARGS(rows2n >= 2 && d >= 1 && is_real(prhs[1]) && mxGetNumberOfElements(prhs[1]) >= 1 && is_num(prhs[2]),
+         "power = gsmcal_band_power(s_all, coef, decimate_ratio) with real taps");
+    raw = raw_in(prhs[0], &n2);
     plhs[0] = mxCreateDoubleMatrix(1, d, mxREAL);
-    chk(gsmcal_band_power_batch(ctx(), U8_PTR(prhs[0]), (int)d, (long)(rows2n / 2), REAL_PTR(prhs[1]),
+    chk(gsmcal_band_power_batch(ctx(), raw, (int)d, n2, REAL_PTR(prhs[1]),
                                 (int)mxGetNumberOfElements(prhs[1]), (int)mxGetScalar(prhs[2]), REAL_PTR(plhs[0])),
         "gsmcal_band_power");
 #elif defined(GSMCAL_FN_gsmcal_subband_power)
@@ -517,12 +648,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
      * for all captures and all their sub-frequencies: power(j,c) = mean(abs(filter(coef,1,raw2iq(s(:,c)).*exp(1i*(1:N)'*phase_rotate(j,c)))).^2)
      * s: 2N x D uint8, one column per capture; coef: real taps (at most 128); phase_rotate: J x D (J <= GSMCAL_MAX_SUBBANDS), NaN = unused
      * slot; power: J x D linear, NaN in unused slots.  decimate_ratio (default 1, the script) keeps rows 1:decimate_ratio:end. */
-    mwSize rows2n = mxGetM(prhs[0]), d = mxGetN(prhs[0]);
-    if (!mxIsUint8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s must be uint8 (the bytes fread(...,'uint8') delivers)");
-    if (nrhs < 3 || mxIsComplex(prhs[1]) || mxIsComplex(prhs[2]) || mxGetN(prhs[2]) != d)
-        mexErrMsgIdAndTxt("gsmcal:args", "usage: power = gsmcal_subband_power(s, coef, phase_rotate) with phase_rotate J x size(s,2)");
+    mwSize rows2n, d;
+    long n2 = 0;
+    const uint8_t* raw;
+    ARGS(nrhs >= 3 && nrhs <= 4 && nlhs <= 1, "power = gsmcal_subband_power(s, coef, phase_rotate, decimate_ratio)");
+    if (!is_u8(prhs[0])) mexErrMsgIdAndTxt("gsmcal:type", "s must be uint8 (the bytes fread(...,'uint8') delivers)");
+    rows2n = mxGetM(prhs[0]); d = mxGetN(prhs[0]);
+    ARGS(rows2n >= 2 && d >= 1 && is_real(prhs[1]) && mxGetNumberOfElements(prhs[1]) >= 1 && is_real(prhs[2]) && mxGetM(prhs[2]) >= 1 &&
+         mxGetN(prhs[2]) == d && all_num(nrhs, prhs, 3),
+         "power = gsmcal_subband_power(s, coef, phase_rotate, decimate_ratio) with phase_rotate J x size(s,2)");
+    raw = raw_in(prhs[0], &n2);
     plhs[0] = mxCreateDoubleMatrix(mxGetM(prhs[2]), d, mxREAL);
-    chk(gsmcal_subband_power_batch(ctx(), U8_PTR(prhs[0]), (int)d, (long)(rows2n / 2), REAL_PTR(prhs[1]),
+    chk(gsmcal_subband_power_batch(ctx(), raw, (int)d, n2, REAL_PTR(prhs[1]),
                                    (int)mxGetNumberOfElements(prhs[1]), nrhs > 3 ? (int)mxGetScalar(prhs[3]) : 1, REAL_PTR(prhs[2]),
                                    (int)mxGetM(prhs[2]), REAL_PTR(plhs[0])), "gsmcal_subband_power");
 #else

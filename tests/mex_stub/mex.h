@@ -1,11 +1,11 @@
-/* Declaration-only stand-in for MATLAB's mex.h -- TEST INFRASTRUCTURE, nothing links against it.
+/* Declaration-only stand-in for MATLAB's mex.h -- TEST INFRASTRUCTURE.
  *
- * The build image has no MATLAB, so mex/gsmcal_mex.c can never be built here.  tests/test_abi_cpu.py compiles every
- * gateway target with `gcc -fsyntax-only` against these declarations: a check of syntax and of every call into
- * include/gsmcal.h (argument counts and types), not of MATLAB semantics.  Only the subset of the published MEX C API
- * that the gateway uses is declared -- the interleaved-complex one (-R2018a) by default, the split-complex one
- * (mxGetPr / mxGetPi, every release and still the default of `mex`) with -DGSMCAL_STUB_SPLIT.  Each mode declares ONLY its
- * own accessors, so a gateway path that reaches for the other API's functions does not compile. */
+ * Only the subset of the published MEX C API that mex/gsmcal_mex.c uses is declared -- the interleaved-complex one (-R2018a) by
+ * default, the split-complex one (mxGetPr / mxGetPi, every release and still the default of `mex`) with -DGSMCAL_STUB_SPLIT.
+ * Each mode declares ONLY its own accessors, so a gateway path that reaches for the other API's functions does not compile.
+ * Two uses: tests/test_abi_cpu.py compiles every gateway target with `gcc -fsyntax-only` against these declarations alone (syntax,
+ * and every call into include/gsmcal.h); tests/mex_gateway.py builds every target against them and links mxstub.c beside this
+ * file, a working mxArray and the functions declared here, so that the gateway runs without MATLAB. */
 #ifndef GSMCAL_TEST_MEX_STUB_H
 #define GSMCAL_TEST_MEX_STUB_H
 #include <stddef.h>
@@ -22,6 +22,9 @@ size_t mxGetN(const mxArray*);
 size_t mxGetNumberOfElements(const mxArray*);
 int mxIsComplex(const mxArray*);
 int mxIsUint8(const mxArray*);
+#ifdef MATLAB_MEX_FILE   /* what `mex` defines for everything it builds: the gateway then asks mxIsDouble, as it does under MATLAB */
+int mxIsDouble(const mxArray*);
+#endif
 double mxGetScalar(const mxArray*);
 #ifdef GSMCAL_STUB_SPLIT
 #define MX_HAS_INTERLEAVED_COMPLEX 0
