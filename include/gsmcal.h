@@ -55,6 +55,7 @@ enum {
     GSMCAL_S_BCCH_NO_DECODE = 15, /* gsmcal_BCCH_decode: no BCCH block passes the Fire code's check   */
     GSMCAL_S_PAIR_FEW = 16,       /* gsmcal_pair_coherence: fewer than two bursts of the pair are used */
     GSMCAL_S_ALIGN_SKIPPED = 17,  /* gsmcal_pair_align: a value of the member's parameter row is not finite */
+    GSMCAL_S_WEIGHTS_SINGULAR = 18, /* gsmcal_combine_weights: a value that is not finite, a Cholesky pivot <= 0, or lambda_1 <= 0 */
     /* < 0: failures */
     GSMCAL_E_ARG = -1,
     GSMCAL_E_HIP = -2,
@@ -80,6 +81,10 @@ enum {
 #define GSMCAL_ALIGN_PARAMS 6                          /* one member's row: delay, slope_ppm, carrier_hz, phase, anchor, weight */
 #define GSMCAL_ALIGN_INFO_COLS 4                       /* one row of the info table of gsmcal_pair_align_batch[_dev] */
 #define GSMCAL_ALIGN_TAPS 16                           /* taps of the interpolator, k = -7 .. 8 */
+#define GSMCAL_MAX_COV_WINDOWS 256                     /* windows of one gsmcal_array_covariance_batch[_dev] call */
+#define GSMCAL_COV_CHUNK 512                           /* samples of one partial sum of gsmcal_array_covariance_batch[_dev], counted from the window's start */
+#define GSMCAL_MAX_BEAMS 16                            /* weight vectors of one gsmcal_array_combine_batch[_dev] call */
+#define GSMCAL_WEIGHTS_INFO_COLS 4                     /* info of gsmcal_combine_weights: status, lambda_1, lambda_2, sweeps */
 
 /* columns of one row of the calibration table (doubles; this row is what ranks all-gather) */
 enum {
@@ -834,6 +839,46 @@ int gsmcal_pair_align_batch(gsmcal_ctx* ctx, const double* r, long stride, const
 int gsmcal_pair_align_batch_dev(gsmcal_ctx* ctx, const double* d_r, long stride, const long* d_r_len, int d, int oversampling_ratio,
                                 const int* members, const double* params, int G, long out_len, double* d_aligned, double* d_combined,
                                 double* d_info);
+
+/* ---- optimal combining: covariance of the aligned streams, the weights, the beams -------------------------
+ * The project's own functions.  x: [d][stride] complex (the `aligned` rows of gsmcal_pair_align_batch, or any streams on one time
+ * base); rows (host): [G] indices into it, each in [0, d), 1 <= G <= GSMCAL_MAX_ALIGN_MEMBERS; a row may be named twice.
+ *
+ * gsmcal_array_covariance_batch[_dev]: windows (host): [W][2] longs {start, len}, 1 <= W <= GSMCAL_MAX_COV_WINDOWS; cov: [W][G][G]
+ * complex, row-major:  cov[w][i][j] = sum_{n = start}^{start + len - 1} x_i[n] conj(x_j[n])  in fp64, not divided by len; len = 0
+ * gives an all-zero matrix.  cov[w][j][i] is the exact conjugate of cov[w][i][j] (one triangle is computed and mirrored) and the
+ * imaginary part of the diagonal is exactly +0.  The order of the sum is fixed: every window is cut into chunks of GSMCAL_COV_CHUNK
+ * samples counted from its own start, a chunk is added sample after sample with fused multiply-adds, the chunks' sums are added in
+ * chunk order (no atomics).  So a window's matrix is the same bits from call to call, between the two forms, alone or at any
+ * place of any window list, whatever other windows overlap it.  NaN and Inf propagate; nothing is screened.
+ * Decided before anything is enqueued: GSMCAL_E_ARG for a row index outside [0, d), G or W outside its range, start < 0, len < 0,
+ * start + len > stride, d < 1, stride < 1 or a NULL pointer.  _dev: x and cov are device pointers (rows and windows stay host
+ * arrays); only enqueues on the context's stream. */
+int gsmcal_array_covariance_batch(gsmcal_ctx* ctx, const double* x, long stride, int d, const int* rows, int G, const long* windows, int W,
+                                  double* cov);
+int gsmcal_array_covariance_batch_dev(gsmcal_ctx* ctx, const double* d_x, long stride, int d, const int* rows, int G, const long* windows,
+                                      int W, double* d_cov);
+
+/* The combining weights from covariances (pure host arithmetic; no context needed).  cov_signal, cov_noise: [G][G] complex as
+ * gsmcal_array_covariance_batch writes them; only the upper triangle (i <= j) and the real part of the diagonal are read.
+ * cov_noise NULL: w = the eigenvector of the largest eigenvalue of cov_signal (largest SNR when the noise is white and equal).
+ * cov_noise given: w = the dominant generalised eigenvector of  Rs w = lambda Rn w  (largest SINR), through Rn = L L^H, the Hermitian
+ * eigenproblem of L^-1 Rs L^-H (cyclic complex Jacobi) and w = L^-H u.  Either way |w|_2 = 1 and w[ref] is real and >= 0 (left as
+ * found when it is exactly 0).  weights: [G] complex.  info: GSMCAL_WEIGHTS_INFO_COLS doubles {status, lambda_1, lambda_2, sweeps}
+ * (lambda_2 NaN at G = 1).  Returns the status: 0, or GSMCAL_S_WEIGHTS_SINGULAR -- a value read that is not finite, a Cholesky pivot
+ * <= 0 or not finite, lambda_1 <= 0 -- with every weight NaN.  GSMCAL_E_ARG: G outside 1 .. 64, ref outside [0, G), a NULL
+ * cov_signal, weights or info. */
+int gsmcal_combine_weights(const double* cov_signal, const double* cov_noise, int G, int ref, double* weights, double* info);
+
+/* gsmcal_array_combine_batch[_dev]: weights (host): [B][G] complex, 1 <= B <= GSMCAL_MAX_BEAMS; out: [B][out_len] complex,
+ * 1 <= out_len <= stride:  out[b][n] = sum_g conj(weights[b][g]) x_{rows[g]}[n]  (w^H x), g in list order, every term two fused
+ * multiply-adds per part.  x is read once for all beams; a beam's row is the same bits alone or among other beams, from call to
+ * call and between the two forms.  GSMCAL_E_ARG as above, and for B or out_len outside its range.  An output that overlaps x is
+ * not supported.  _dev: x and out are device pointers (rows and weights stay host arrays); only enqueues on the context's stream. */
+int gsmcal_array_combine_batch(gsmcal_ctx* ctx, const double* x, long stride, int d, const int* rows, int G, const double* weights, int B,
+                               long out_len, double* out);
+int gsmcal_array_combine_batch_dev(gsmcal_ctx* ctx, const double* d_x, long stride, int d, const int* rows, int G, const double* weights,
+                                   int B, long out_len, double* d_out);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,

@@ -40,6 +40,9 @@ S_PAIR_FEW = 16
 MAX_ALIGN_MEMBERS = 64                  # members of one pair_align_batch call (GSMCAL_MAX_ALIGN_MEMBERS)
 ALIGN_PARAMS, ALIGN_INFO_COLS = 6, 4    # one member's parameter row (api.ALIGN_PARAM_FIELDS); one row of the info table (api.ALIGN_INFO_FIELDS)
 S_ALIGN_SKIPPED = 17
+MAX_COV_WINDOWS, COV_CHUNK = 256, 512   # windows of one array_covariance call; samples of one partial sum (GSMCAL_MAX_COV_WINDOWS, GSMCAL_COV_CHUNK)
+MAX_BEAMS, WEIGHTS_INFO_COLS = 16, 4    # weight vectors of one array_combine call; info of combine_weights: status, lambda_1, lambda_2, sweeps
+S_WEIGHTS_SINGULAR = 18
 HYPERFRAME = 2715648               # TDMA frames per GSM hyperframe: frame numbers wrap here
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
@@ -118,6 +121,13 @@ SIGNATURES = {
                                           C.c_long, c_double_p, c_double_p, c_double_p]),
     "gsmcal_pair_align_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, C.c_int,
                                               C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsmcal_array_covariance_batch": (C.c_int, [C.c_void_p, c_double_p, C.c_long, C.c_int, c_int_p, C.c_int, c_long_p, C.c_int, c_double_p]),
+    "gsmcal_array_covariance_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, c_int_p, C.c_int, c_long_p, C.c_int, C.c_void_p]),
+    "gsmcal_combine_weights": (C.c_int, [c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p]),
+    "gsmcal_array_combine_batch": (C.c_int, [C.c_void_p, c_double_p, C.c_long, C.c_int, c_int_p, C.c_int, c_double_p, C.c_int, C.c_long,
+                                             c_double_p]),
+    "gsmcal_array_combine_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, c_int_p, C.c_int, c_double_p, C.c_int, C.c_long,
+                                                 C.c_void_p]),
     "gsmcal_total_ppm_calculation": (C.c_int, [c_double_p, C.c_int, c_double_p]),
     "gsmcal_frontend_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                         c_double_p]),

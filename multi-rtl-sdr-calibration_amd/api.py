@@ -1187,15 +1187,134 @@ def pair_align_batch_dev(d_r, stride, d_r_len, d, oversampling_ratio, members, p
                                                   C.c_void_p(d_info)), "pair_align_batch_dev")
 
 
+WEIGHTS_INFO_FIELDS = ("status", "lambda_1", "lambda_2", "sweeps")                          # info of combine_weights
+
+
+def _rows_in(rows):
+    rw = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).ravel())
+    return rw, len(rw)
+
+
+def _windows_in(windows):
+    return np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+
+
+def array_covariance(x, rows, windows, ctx=None):
+    """The spatial covariance of streams on one time base (include/gsmcal.h).  x: (D, N) complex, e.g. the
+    "aligned" rows of pair_align_batch; rows: (G,) indices into it, 1 .. 64 of them; windows: (W, 2) {start, len}, 1 .. 256 of them.
+    Returns (W, G, G) complex: cov[w, i, j] = sum over the window of x_i conj(x_j), in fp64, not divided by len -- exactly Hermitian,
+    the diagonal exactly real, the same bits for a window wherever it stands in whatever list."""
+    ctx = ctx or default_context()
+    xa = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.complex128)))
+    d, stride = xa.shape
+    rw, g = _rows_in(rows)
+    wn = _windows_in(windows)
+    cov = np.empty((len(wn), g, g), dtype=np.complex128)
+    ctx.check(ctx.lib.gsmcal_array_covariance_batch(ctx.h, _dp(xa), stride, d, rw.ctypes.data_as(_lib.c_int_p), g,
+                                                    wn.ctypes.data_as(_lib.c_long_p), len(wn), _dp(cov)), "array_covariance")
+    return cov
+
+
+def array_covariance_dev(d_x, stride, d, rows, windows, d_cov, ctx=None):
+    """Device-pointer form of array_covariance: only enqueues on the context's stream (ctx.sync() before reading).  rows, windows: host
+    arrays.  d_cov: [W][G][G] complex.  Device or pinned host memory."""
+    ctx = ctx or default_context()
+    rw, g = _rows_in(rows)
+    wn = _windows_in(windows)
+    ctx.check(ctx.lib.gsmcal_array_covariance_batch_dev(ctx.h, C.c_void_p(d_x), int(stride), int(d), rw.ctypes.data_as(_lib.c_int_p), g,
+                                                        wn.ctypes.data_as(_lib.c_long_p), len(wn), C.c_void_p(d_cov)), "array_covariance_dev")
+
+
+def combine_weights(cov_signal, cov_noise=None, ref=0):
+    """The weights w of the beam w^H x (gsmcal_combine_weights; pure host arithmetic, no context).  cov_signal: (G, G) Hermitian, of
+    which the upper triangle is read.  Without cov_noise: the eigenvector of its largest eigenvalue.  With cov_noise (a covariance
+    of windows without the wanted signal): the dominant generalised eigenvector of Rs w = lambda Rn w, the weights of the largest
+    SINR.  |w| = 1, w[ref] real and >= 0.  Returns (weights (G,) complex, info dict of the WEIGHTS_INFO_FIELDS): status 0, or 18
+    (S_WEIGHTS_SINGULAR: a value that is not finite, cov_noise not positive definite, lambda_1 <= 0) with every weight NaN."""
+    lib = _lib.load()
+    rs = np.ascontiguousarray(np.asarray(cov_signal, dtype=np.complex128))
+    if rs.ndim != 2 or rs.shape[0] != rs.shape[1]:
+        raise ValueError("cov_signal must be (G, G)")
+    g = rs.shape[0]
+    rn = None
+    if cov_noise is not None:
+        rn = np.ascontiguousarray(np.asarray(cov_noise, dtype=np.complex128))
+        if rn.shape != rs.shape:
+            raise ValueError("cov_noise must have the shape of cov_signal")
+    w = np.empty(max(g, 1), dtype=np.complex128)
+    info = np.empty(_lib.WEIGHTS_INFO_COLS)
+    rc = lib.gsmcal_combine_weights(_dp(rs), _dp(rn) if rn is not None else None, g, int(ref), _dp(w), _dp(info))
+    if rc < 0:
+        raise GsmcalError(f"combine_weights failed with {rc} ")
+    out = {k: float(info[i]) for i, k in enumerate(WEIGHTS_INFO_FIELDS)}
+    out["status"], out["sweeps"] = int(info[0]), int(info[3])
+    return w[:g], out
+
+
+def _weights_in(weights, g):
+    w = np.ascontiguousarray(np.atleast_2d(np.asarray(weights, dtype=np.complex128)))
+    if w.shape[1] != g:
+        raise ValueError("one weight per row and beam: (B, G) or (G,)")
+    return w, w.shape[0]
+
+
+def array_combine(x, rows, weights, out_len=None, ctx=None):
+    """The beams out[b, n] = sum_g conj(weights[b, g]) x[rows[g], n] (w^H x; include/gsmcal.h).  weights: (G,)
+    for one beam -> (out_len,), or (B, G) for 1 .. 16 beams -> (B, out_len); out_len defaults to the row length.  x is read once for
+    all beams, and a beam's row is the same bits alone or among others."""
+    ctx = ctx or default_context()
+    xa = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.complex128)))
+    d, stride = xa.shape
+    rw, g = _rows_in(rows)
+    w, b = _weights_in(weights, g)
+    out_len = stride if out_len is None else int(out_len)
+    out = np.empty((b, max(out_len, 0)), dtype=np.complex128)
+    ctx.check(ctx.lib.gsmcal_array_combine_batch(ctx.h, _dp(xa), stride, d, rw.ctypes.data_as(_lib.c_int_p), g, _dp(w), b, out_len, _dp(out)),
+              "array_combine")
+    return out[0] if np.ndim(weights) == 1 else out
+
+
+def array_combine_dev(d_x, stride, d, rows, weights, out_len, d_out, ctx=None):
+    """Device-pointer form of array_combine: only enqueues on the context's stream.  rows, weights ((B, G) or (G,)): host arrays.
+    d_out: [B][out_len] complex; it must not overlap d_x."""
+    ctx = ctx or default_context()
+    rw, g = _rows_in(rows)
+    w, b = _weights_in(weights, g)
+    ctx.check(ctx.lib.gsmcal_array_combine_batch_dev(ctx.h, C.c_void_p(d_x), int(stride), int(d), rw.ctypes.data_as(_lib.c_int_p), g, _dp(w), b,
+                                                     int(out_len), C.c_void_p(d_out)), "array_combine_dev")
+
+
+def burst_windows(pos_info_raw_of_ref, oversampling_ratio, align_info, kinds=(1, 2)):
+    """The windows {round(pos) - 1, 148 ov} of the reference stream's SCH (kind 1) and BCCH (kind 2) rows that lie wholly inside
+    [combined_first, combined_end) of a pair_align info table: where every used member is valid, so a covariance over them sees
+    every stream.  pos_info_raw_of_ref: the (2, MAX_POS_ROWS) table of the reference stream.  Returns (W, 2) int64 (W may be 0)."""
+    pi = np.asarray(pos_info_raw_of_ref, dtype=np.float64).reshape(2, MAX_POS_ROWS)
+    t = align_rows(align_info)
+    first, end, L = t["combined_first"], t["combined_end"], 148 * int(oversampling_ratio)
+    out = []
+    for i in range(MAX_POS_ROWS):
+        pos = pi[0, i]
+        if pi[1, i] not in [float(k) for k in kinds] or not (pos == pos) or abs(pos) > 2.0 ** 52:
+            continue
+        p = int(np.floor(pos + 0.5)) - 1
+        if first <= p and p + L <= end:
+            out.append((p, L))
+    return np.array(out, dtype=np.int64).reshape(-1, 2)
+
+
 def coherent_combine(r_correct, r_len, pos_info_raw, oversampling_ratio, sch_table, ref=0, members=None, max_lag=None, min_coherence=0.5,
-                     want_aligned=False, ctx=None):
+                     want_aligned=False, ctx=None, weights=None):
     """One stream out of several calibrated dongles on one cell: pair_lag0 -> pair_coherence_batch for the pairs (ref, m) ->
     pair_align_params -> pair_align_batch, on what calibrate_batch(..., want_r=True) and sch_decode_batch returned.  members: the
     streams to put on ref's time base (default: every other stream).  The sum has equal weights 1 / (1 + len(members)) and ref
     itself as its first member; a member whose pair row has a status other than 0 is skipped (info says so).  Returns a dict:
     "combined" (N,) complex, "info" (align_rows names its columns; row 0 is ref), "pair_table" (len(members), PAIR_COLS), "params"
     (1 + len(members), ALIGN_PARAMS), "members" (ref first), with want_aligned "aligned" (1 + len(members), N).  The combined stream
-    has the shape the demod family takes: SCH_decode and the others read it with ref's pos_info."""
+    has the shape the demod family takes: SCH_decode and the others read it with ref's pos_info.
+    weights="max_ratio": the members are aligned as above, their covariance is summed over burst_windows (ref's SCH and BCCH bursts
+    inside the interval where every used member is valid), combine_weights(ref=0) gives its dominant eigenvector and "combined" is
+    array_combine with it over the members of status 0.  The dict then also holds "weights" (1 + len(members),) complex, NaN for a
+    skipped member, and "cov" (used, used) complex."""
     ctx = ctx or default_context()
     r, d, stride, rl, pi = _post_batch_in(r_correct, r_len, pos_info_raw)
     ms = [m for m in range(d) if m != ref] if members is None else [int(m) for m in members]
@@ -1204,7 +1323,26 @@ def coherent_combine(r_correct, r_len, pos_info_raw, oversampling_ratio, sch_tab
     table = pair_coherence_batch(r, rl, pi, oversampling_ratio, pairs, lag0, max_lag, min_coherence, ctx=ctx)
     w = 1.0 / (1 + len(ms))
     params = np.vstack([[0.0, 0.0, 0.0, 0.0, 0.0, w], pair_align_params(table, oversampling_ratio, w, min_coherence)])
-    out = pair_align_batch(r, rl, oversampling_ratio, [int(ref)] + ms, params, ctx=ctx, want_aligned=want_aligned)
+    if weights is None:
+        out = pair_align_batch(r, rl, oversampling_ratio, [int(ref)] + ms, params, ctx=ctx, want_aligned=want_aligned)
+    elif weights == "max_ratio":
+        out = pair_align_batch(r, rl, oversampling_ratio, [int(ref)] + ms, params, ctx=ctx, want_aligned=True, want_combined=False)
+        used = np.flatnonzero(align_rows(out["info"])["status"] == 0)
+        wins = burst_windows(pi[int(ref)], oversampling_ratio, out["info"])
+        if len(wins) == 0 or len(used) == 0 or used[0] != 0:
+            raise GsmcalError("coherent_combine: no burst of the reference stream lies inside the interval every member covers")
+        cov = array_covariance(out["aligned"], used, wins, ctx=ctx).sum(axis=0)
+        w, winfo = combine_weights(cov, ref=0)
+        if winfo["status"] != 0:
+            raise GsmcalError(f"coherent_combine: combine_weights ended with status {winfo['status']}")
+        out["combined"] = array_combine(out["aligned"], used, w, ctx=ctx)
+        out["weights"] = np.full(1 + len(ms), np.nan + 1j * np.nan)
+        out["weights"][used] = w
+        out["cov"] = cov
+        if not want_aligned:
+            del out["aligned"]
+    else:
+        raise ValueError('weights: None or "max_ratio"')
     out.update({"pair_table": table, "params": params, "members": np.array([int(ref)] + ms)})
     return out
 

@@ -1221,6 +1221,131 @@ int gsmcal_pair_align_params(const double* pair_row, int ov, double min_coh, dou
     return 0;
 }
 
+// ---- optimal combining: covariance of the aligned streams, the weights, the beams ------------------------------
+// k_array_cov (one workgroup per window and chunk of GSMCAL_COV_CHUNK samples) + k_array_cov_reduce (one per window: the chunk
+// partials in chunk order, both triangles); k_array_combine (one workgroup per AC_TILE output samples, every beam at once).
+#define AC_MAX_PARTIALS 4096L   /* chunk partials one k_array_cov launch leaves in the workspace (33 KB each at G = 64: 136 MB); a window with more is a launch of its own */
+
+static int array_rows_args(gsmcal_ctx* c, long stride, int d, const int* rows, int G) {
+    if (!rows || d < 1 || stride < 1) return GSMCAL_E_ARG;
+    if (G < 1 || G > GSMCAL_MAX_ALIGN_MEMBERS) { c->err = "array: 1 .. 64 rows"; return GSMCAL_E_ARG; }
+    for (int g = 0; g < G; ++g)
+        if (rows[g] < 0 || rows[g] >= d) { c->err = "array: a row index outside the batch"; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+static int array_cov_args(gsmcal_ctx* c, long stride, int d, const int* rows, int G, const long* windows, int W) {
+    RET_IF(array_rows_args(c, stride, d, rows, G));
+    if (!windows) return GSMCAL_E_ARG;
+    if (W < 1 || W > GSMCAL_MAX_COV_WINDOWS) { c->err = "array_covariance: 1 .. 256 windows"; return GSMCAL_E_ARG; }
+    for (int w = 0; w < W; ++w) {
+        const long start = windows[2 * w], len = windows[2 * w + 1];
+        if (start < 0 || len < 0 || start > stride || len > stride - start) { c->err = "array_covariance: a window outside the rows"; return GSMCAL_E_ARG; }
+    }
+    return 0;
+}
+
+int gsmcal_array_covariance_batch_dev(gsmcal_ctx* c, const double* d_x, long stride, int d, const int* rows, int G, const long* windows, int W,
+                                      double* d_cov) {
+    if (!c || !d_x || !d_cov) return GSMCAL_E_ARG;
+    RET_IF(array_cov_args(c, stride, d, rows, G, windows, W));
+    ENTER_ON_CTX_STREAM(c);
+    // {start, len, first partial} per window, the total behind them; launches of whole windows, at most AC_MAX_PARTIALS partials each
+    std::vector<long> tab((size_t)(W + 1) * 3, 0);
+    long total = 0, most = 1;
+    std::vector<int> cut{0};                                       // the launches' first windows
+    for (int w = 0, first_w = 0; w < W; ++w) {
+        const long nch = (windows[2 * w + 1] + GSMCAL_COV_CHUNK - 1) / GSMCAL_COV_CHUNK;
+        if (w > first_w && total + nch - tab[(size_t)first_w * 3 + 2] > AC_MAX_PARTIALS) { cut.push_back(w); first_w = w; }
+        tab[(size_t)w * 3] = windows[2 * w];
+        tab[(size_t)w * 3 + 1] = windows[2 * w + 1];
+        tab[(size_t)w * 3 + 2] = total;
+        total += nch;
+        most = std::max(most, total - tab[(size_t)first_w * 3 + 2]);
+    }
+    tab[(size_t)W * 3 + 2] = total;
+    cut.push_back(W);
+    if (most > 0x7fffffffL) { c->err = "array_covariance: a window of more than 2^31 chunks"; return GSMCAL_E_ARG; }
+    const int NB = (G + 3) / 4, ntri = NB * (NB + 1) / 2;
+    RET_IF(upload_if_changed(c, c->ac_rows, c->h_ac_rows, rows, (size_t)G, "array rows"));
+    RET_IF(upload_if_changed(c, c->ac_win, c->h_ac_win, tab.data(), tab.size(), "array_covariance windows"));
+    RET_IF(ensure(c, c->ac_part, (size_t)most * ntri * AC_BLOCK_ENTRIES * sizeof(cplx)));
+    const int* d_rows = (const int*)c->ac_rows.p;
+    const long* d_win = (const long*)c->ac_win.p;
+    for (size_t k = 0; k + 1 < cut.size(); ++k) {
+        const int w0 = cut[k], w1 = cut[k + 1];
+        const long base = tab[(size_t)w0 * 3 + 2], n = tab[(size_t)w1 * 3 + 2] - base;
+        if (n > 0)
+            LAUNCH(c, k_array_cov, dim3((unsigned)n), dim3(AC_COV_LANES), 0, (const cplx*)d_x, stride, d_rows, G, d_win, w0, w1, base,
+                   (cplx*)c->ac_part.p);
+        LAUNCH(c, k_array_cov_reduce, dim3((unsigned)ntri, (unsigned)(w1 - w0)), dim3(256), 0, (const cplx*)c->ac_part.p, d_win, w0, base, G, (cplx*)d_cov);
+    }
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_array_covariance_batch(gsmcal_ctx* c, const double* x, long stride, int d, const int* rows, int G, const long* windows, int W,
+                                  double* cov) {
+    if (!c || !x || !cov) return GSMCAL_E_ARG;
+    RET_IF(array_cov_args(c, stride, d, rows, G, windows, W));
+    ENTER(c);
+    const Stage io[] = {STAGE(ac_x, (size_t)d * stride * sizeof(cplx), x, nullptr, 0),
+                        STAGE(ac_cov, (size_t)W * G * G * sizeof(cplx), nullptr, cov, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_array_covariance_batch_dev(c, (const double*)c->ac_x.p, stride, d, rows, G, windows, W, (double*)c->ac_cov.p));
+    return stage_down(c, io);
+}
+
+int gsmcal_combine_weights(const double* cov_signal, const double* cov_noise, int G, int ref, double* weights, double* info) {
+    if (!cov_signal || !weights || !info || G < 1 || G > GSMCAL_MAX_ALIGN_MEMBERS || ref < 0 || ref >= G) return GSMCAL_E_ARG;
+    static_assert(gsmcal_cw::CW_SINGULAR == GSMCAL_S_WEIGHTS_SINGULAR && gsmcal_cw::CW_MAX_G == GSMCAL_MAX_ALIGN_MEMBERS, "combine_weights.h and gsmcal.h disagree");
+    return gsmcal_cw::combine_weights(cov_signal, cov_noise, G, ref, weights, info);
+}
+
+static int array_combine_args(gsmcal_ctx* c, long stride, int d, const int* rows, int G, const double* weights, int B, long out_len) {
+    RET_IF(array_rows_args(c, stride, d, rows, G));
+    if (!weights) return GSMCAL_E_ARG;
+    if (B < 1 || B > GSMCAL_MAX_BEAMS) { c->err = "array_combine: 1 .. 16 beams"; return GSMCAL_E_ARG; }
+    if (out_len < 1 || out_len > stride) { c->err = "array_combine: out_len must lie in 1 .. stride"; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+int gsmcal_array_combine_batch_dev(gsmcal_ctx* c, const double* d_x, long stride, int d, const int* rows, int G, const double* weights, int B,
+                                   long out_len, double* d_out) {
+    if (!c || !d_x || !d_out) return GSMCAL_E_ARG;
+    RET_IF(array_combine_args(c, stride, d, rows, G, weights, B, out_len));
+    ENTER_ON_CTX_STREAM(c);
+    RET_IF(upload_if_changed(c, c->ac_rows, c->h_ac_rows, rows, (size_t)G, "array rows"));
+    RET_IF(upload_if_changed(c, c->ac_w, c->h_ac_w, weights, (size_t)2 * B * G, "array_combine weights"));
+    const int* d_rows = (const int*)c->ac_rows.p;
+    const cplx* d_w = (const cplx*)c->ac_w.p;
+    const long tiles = (out_len + AC_TILE - 1) / AC_TILE, per_launch = 1L << 30;                   // (grid.x holds 2^31 - 1)
+    for (long t = 0; t < tiles; t += per_launch) {
+        const dim3 grid((unsigned)std::min(per_launch, tiles - t));
+#define AC_COMBINE(BT) LAUNCH(c, k_array_combine<BT>, grid, dim3(AC_TILE), 0, (const cplx*)d_x, stride, d_rows, G, d_w, B, out_len, t * AC_TILE, (cplx*)d_out)
+        if (B == 1) AC_COMBINE(1);
+        else if (B == 2) AC_COMBINE(2);
+        else if (B <= 4) AC_COMBINE(4);
+        else if (B <= 8) AC_COMBINE(8);
+        else AC_COMBINE(16);
+#undef AC_COMBINE
+    }
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_array_combine_batch(gsmcal_ctx* c, const double* x, long stride, int d, const int* rows, int G, const double* weights, int B,
+                               long out_len, double* out) {
+    if (!c || !x || !out) return GSMCAL_E_ARG;
+    RET_IF(array_combine_args(c, stride, d, rows, G, weights, B, out_len));
+    ENTER(c);
+    const Stage io[] = {STAGE(ac_x, (size_t)d * stride * sizeof(cplx), x, nullptr, 0),
+                        STAGE(ac_out, (size_t)B * out_len * sizeof(cplx), nullptr, out, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(gsmcal_array_combine_batch_dev(c, (const double*)c->ac_x.p, stride, d, rows, G, weights, B, out_len, (double*)c->ac_out.p));
+    return stage_down(c, io);
+}
+
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out) {
     if (!ppm_in || !ppm_out || n < 1) return GSMCAL_E_ARG;

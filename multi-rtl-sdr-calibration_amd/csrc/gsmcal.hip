@@ -36,6 +36,8 @@
 #include "kernels_iqcheck.h"
 #include "kernels_pair.h"
 #include "kernels_align.h"
+#include "kernels_array.h"
+#include "combine_weights.h"
 #include "state.h"
 
 #define GSMCAL_VERSION "gsmcal-mi355x 0.1 (gfx950)"
