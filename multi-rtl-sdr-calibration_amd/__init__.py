@@ -13,7 +13,7 @@ from ._lib import GsmcalError, MAX_HITS, MAX_POS_ROWS, MAX_SUBBANDS, TABLE_COLS,
 from .api import (  # noqa: F401
     Context, default_context, raw2iq, filter, chn_filter_8x_4x, chn_filter_4x, move_fft_snr_runtime_avg,
     specific_fft_snr_fix_avg, FCCH_coarse_position, FCCH_fine_correction, SCH_corr_rate_correction,
-    carrier_correct_post_SCH, total_ppm_calculation, SCH_equalise, frontend_batch, fcch_scan_batch, calibrate_batch,
+    carrier_correct_post_SCH, total_ppm_calculation, SCH_equalise, frontend_batch, frontend_batch_dev, fcch_scan_batch, calibrate_batch,
     last_batch_details, last_batch_snr, TABLE_FIELDS, fcch_scan_batch_dev, calibrate_batch_dev, synth_expand_dev,
     set_verbose, last_call_report, num2str, band_power_batch, band_power_batch_dev, split_spectrum_scan,
     diversity_spectrum_scan, FCCH_demod, fcch_demod_batch, fcch_demod_batch_dev, demod_rows, DEMOD_FIELDS,

@@ -592,6 +592,15 @@ def frontend_batch(raw, coef, decim, ctx=None):
     return out
 
 
+def frontend_batch_dev(d_raw, d, n, coef, decim, d_out, ctx=None):
+    """Device-pointer form of frontend_batch: only enqueues on the context's stream (ctx.sync() before reading).
+    d_raw: [d][2n] bytes; d_out: [d][ceil(n/decim)] complex."""
+    ctx = ctx or default_context()
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    ctx.check(ctx.lib.gsmcal_frontend_batch_dev(ctx.h, C.c_void_p(d_raw), int(d), int(n), _dp(coef), len(coef), int(decim),
+                                                C.c_void_p(d_out)), "frontend_batch_dev")
+
+
 def band_power_batch(raw, coef, decim, ctx=None):
     """raw: (D, 2N) uint8 -> (D,) linear band power mean(abs(filter(coef,1,raw2iq(s))(1:decim:end)).^2)
     (multi_rtl_sdr_split_scanner.m:154-156; coef = [1], decim = 1: scan_band_power_spectrum.m:80-84)."""
