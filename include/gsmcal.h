@@ -352,7 +352,7 @@ int gsmcal_filter(gsmcal_ctx* ctx, const double* coef, int ntaps, const double* 
  *   nothing hits; at fft_len = 3 all bins are signal bins and noise_power is a rounding residue (0 or an ulp either side): the
  *   call returns cleanly, which windows hit is not defined by the reference.
  *   mv_len >= 1, len >= 1 (fewer than fft_len samples: no window, no hit).  The scan keeps len + mv_len + 128 SNRs in LDS
- *   behind gsmcal_coarse_scan_lds_fixed() = 12 368 bytes of its own, 159 KiB in all: up to len + mv_len = 18 678
+ *   behind gsmcal_coarse_scan_lds_fixed() = 11 344 bytes of its own, 159 KiB in all: up to len + mv_len = 18 806
  *   (GSMCAL_E_UNSUPPORTED beyond).
  *   gsmcal_FCCH_coarse_position derives fft_len = 2^floor(log2(148/decimation_ratio)) itself: decimation_ratio 2 .. 74 is
  *   served (fft_len 64 .. 2; 5, 6, 7 and 8 give the 16-point kernels), 1 (128-point windows) and 75 and above (windows of one

@@ -64,7 +64,6 @@ int gsmcal_ctx_create_on_stream(int device_id, void* hip_stream, gsmcal_ctx** ou
     (void)hipFuncSetAttribute((const void*)k_front_fast31_sym, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_front_fast31, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_coarse_scan_lat, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_coarse_scan_thr, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_coarse_scan_inl, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_coarse_scan_gen, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
     (void)hipFuncSetAttribute((const void*)k_coarse_scan_ref, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
@@ -402,7 +401,7 @@ static int coarse_api(gsmcal_ctx* c, const double* s, long len, CoarseArgs a, St
     }
     if (fft_len < 2 || fft_len > 64) return GSMCAL_E_UNSUPPORTED;
     const long nwin = n_first - (fft_len - 1);
-    const size_t lds = coarse_scan_lds(n_first > 0 ? n_first : 0, a.mode == 0 ? 10 * fft_len : a.mv_len);
+    const size_t lds = cs_carve(false, n_first > 0 ? n_first : 0, a.mode == 0 ? 10 * fft_len : a.mv_len).launch;
     if (lds > 159 * 1024) return GSMCAL_E_UNSUPPORTED;
     // (the refusals above are decided before anything is uploaded)
     RET_IF(upload_array(c, s, (size_t)len));

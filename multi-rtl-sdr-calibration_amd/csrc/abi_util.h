@@ -50,7 +50,7 @@ int gsmcal_last_batch_details(gsmcal_ctx* c, int d, double* coarse_pos, double* 
     return 0;
 }
 
-long gsmcal_coarse_scan_lds_fixed(void) { return (long)coarse_scan_lds_fixed(); }
+long gsmcal_coarse_scan_lds_fixed(void) { return (long)cs_carve(false, 0, 0).fixed; }
 
 int gsmcal_last_batch_snr(gsmcal_ctx* c, int stream, double* snr, long cap, long* n_table, long* n_moving) {
     if (!c || stream < 0 || stream >= c->last_S || !snr || cap < 1) return GSMCAL_E_ARG;

@@ -949,9 +949,9 @@ static const auto k_front_fast47 = &k_front_fast<47, false>;
 static const auto k_front_fast31_sym = &k_front_fast<31, true>;
 static const auto k_front_fast31 = &k_front_fast<31, false>;
 
-// instances of the coarse scan: 16-point windows with the latency / throughput register budgets, and any window length
-static const auto k_coarse_scan_lat = &k_coarse_scan<3, true>;   // (one register budget serves both: no spills at 165 registers)
-static const auto k_coarse_scan_thr = &k_coarse_scan<3, true>;
+// instances of the coarse scan: 16-point windows (one register budget serves small and big batches: no spills at 165 registers),
+// and any window length
+static const auto k_coarse_scan_lat = &k_coarse_scan<3, true>;
 static const auto k_coarse_scan_gen = &k_coarse_scan<2, false>;
 static const auto k_coarse_scan_ref = &k_coarse_scan<3, true, true>;   // the drivers' window geometry as constants
 static const auto k_coarse_scan_inl = &k_coarse_scan<3, true, true, true>;   // ... with the window SNRs computed in place (throughput batches)
@@ -1005,10 +1005,6 @@ int hits_capacity(long len_dec, int dec_ratio) {
     return h;
 }
 
-size_t coarse_scan_lds(long nwin, int mv_len, bool inl = false) {
-    return coarse_scan_lds_fixed(inl) + (size_t)(nwin + mv_len + 128) * sizeof(double);
-}
-
 // Partial tap sums of the head rows (see coarse()): uploaded on the context's stream BEFORE fork_lanes(), so the fork
 // event orders the copy ahead of every lane's k_coarse_snr (inside coarse() only lane 0 was ordered behind it).
 int ensure_head(gsmcal_ctx* c, int front_decim) {
@@ -1056,7 +1052,7 @@ int coarse(gsmcal_ctx* c, int S, const cplx* d_dec, long stride, long len, int d
     const long n_first = (long)ceil(23.0 * 1250.0 / (double)dec_ratio);
     const long nwin = n_first - (fft_len - 1);
     a.g_fft_len = fft_len; a.g_n_first = n_first;
-    const size_t lds = coarse_scan_lds(n_first, 10 * fft_len);
+    const size_t lds = cs_carve(false, n_first, 10 * fft_len).launch;
     if (lds > 159 * 1024 || nwin < 1) return GSMCAL_E_UNSUPPORTED;
     // latency path (few streams: one wave of k_coarse_snr workgroups still fits the chip): k_coarse_snr fills in every window of
     // the stream and the hop walk of k_coarse_scan becomes table look-ups; bigger batches keep the table to the moving
@@ -1091,7 +1087,7 @@ int coarse(gsmcal_ctx* c, int S, const cplx* d_dec, long stride, long len, int d
             a.snr_g = (double*)c->cur->snrbuf.p;
             c->cur->snr_stride = ntab;
         }
-        LAUNCH(c, k_coarse_scan_inl, dim3(S), dim3(256), coarse_scan_lds(n_first, 10 * fft_len, true), (StreamState*)c->cur->state.p, a);   // 47 584 bytes: three per CU
+        LAUNCH(c, k_coarse_scan_inl, dim3(S), dim3(256), cs_carve(true, n_first, 10 * fft_len).launch, (StreamState*)c->cur->state.p, a);   // 46 560 bytes: three per CU
         CHECK_LAUNCH(c);
         return 0;
     }
@@ -1102,11 +1098,9 @@ int coarse(gsmcal_ctx* c, int S, const cplx* d_dec, long stride, long len, int d
     if (fft_len == 16 && a.snr_nwin > 0) LAUNCH_GEOM(refg, c, (k_coarse_snr<true, true, true>), (k_coarse_snr<true, true>), sgrid, dim3(CS_SNR_THREADS), 0, a);
     else if (fft_len == 16) LAUNCH_GEOM(refg, c, (k_coarse_snr<true, false, true>), (k_coarse_snr<true>), sgrid, dim3(256), 0, a);
     else LAUNCH(c, k_coarse_snr<false>, sgrid, dim3(256), 0, a);
-    // register budgets of the same kernel: small batches run one workgroup per CU anyway, big ones want four
     if (fft_len != 16) LAUNCH(c, k_coarse_scan_gen, dim3(S), dim3(256), lds, (StreamState*)c->cur->state.p, a);
     else if (refg) LAUNCH(c, k_coarse_scan_ref, dim3(S), dim3(256), lds, (StreamState*)c->cur->state.p, a);
-    else if (S <= 512) LAUNCH(c, k_coarse_scan_lat, dim3(S), dim3(256), lds, (StreamState*)c->cur->state.p, a);
-    else LAUNCH(c, k_coarse_scan_thr, dim3(S), dim3(256), lds, (StreamState*)c->cur->state.p, a);
+    else LAUNCH(c, k_coarse_scan_lat, dim3(S), dim3(256), lds, (StreamState*)c->cur->state.p, a);
     CHECK_LAUNCH(c);
     return 0;
 }

@@ -443,9 +443,157 @@ __device__ void d_scan_accept(const StreamState* st, int s, double* snr_numhit, 
                               double* pos_snr, int* counts, const DevParams& P, int lane);   // kernels_estim.h
 
 // ---- k_coarse_scan: first hit + hop walk of FCCH_coarse_position, one workgroup per stream ----
-// grid S, block 256.  LDS: state copy | 64 twiddles | 4 x 36 hop samples | 2 x 11 x 17 hop powers | (INL: prefix ring, CS_RING) |
-// snr[mv_len + nwin + 64]: coarse_scan_lds_fixed(INL) + the snr part.
-//
+// grid S, block 256.  The body (at the end of this section) is its phases (cs_*) between its barriers; the dynamic LDS they
+// share is laid out by cs_carve(), for the kernel and the host alike; the static LDS is CsShared.
+// WAVES: minimum waves per SIMD the register allocator must leave room for (2: small batches, 4: four workgroups per CU).
+#define CS_ROW 36
+#define CS_RING (2 * 256 + 2 * 4)    // INL: prefixes of the last two rounds (one per window) + their four wave totals
+#define CS_XW (256 + 15)             // samples that the 256 windows of an INL round cover
+#define CS_HX (8 + 15)               // samples of the (at most 8) head windows that are redone with per-sample DC removal
+
+// k_coarse_scan's dynamic LDS, written down once: the kernel's pointers and the size of every launch come from here.
+// Byte offsets from the base, in this order:
+//   st       state copy | tw  64 twiddles | rows  4 x CS_ROW hop samples | Pb  [group][window][17] hop powers (2 x 11 x 17) |
+//   hop_sig  (signal, noise) of the hit each hop settled on | ring  (inl) prefix ring, CS_RING |
+//   S        the SNR array S = [999 x mv_len | snr[0..nwin) | 0 x 64]
+// inl: the INL form's prefix ring on top (11 344 -> 15 504 bytes; 46 560 with the reference geometry's S, three workgroups per CU).
+// `fixed` is everything in front of S; `launch` adds (n_first + mv_len + 128) doubles for S, of which the kernel indexes
+// mv_len + nwin + 64 (nwin = n_first - (fft_len - 1) <= n_first - 1).
+// Before the hop walk its buffers are free, and three phases borrow them: xw (CS_XW samples of an INL round, over rows | Pb),
+// hx (the head windows' samples, over rows, once xw is read no more) and Cb (the 257 chunk prefixes of the block scan, over
+// rows).  During the walk the records recs[group][window][4] of ratio mode lie inside Pb, behind the first group's powers: the
+// trip through Pb (exact replay, generic lengths) uses one group's 11 x 17 powers at a time.
+struct CsCarve {
+    size_t st, tw, rows, Pb, hop_sig, ring, S;
+    size_t xw, hx, Cb, recs;         // overlays
+    size_t fixed, launch;            // bytes in front of S | dynamic LDS of the launch
+};
+__host__ __device__ constexpr CsCarve cs_carve(bool inl, long n_first, int mv_len) {
+    CsCarve c{};
+    c.st = 0;
+    c.tw = (sizeof(StreamState) + 15) & ~(size_t)15;
+    c.rows = c.tw + 64 * sizeof(cplx);
+    c.Pb = c.rows + 4 * CS_ROW * sizeof(cplx);
+    c.hop_sig = c.Pb + 2 * 11 * 17 * sizeof(double);
+    c.ring = c.hop_sig + 2 * MAXH * sizeof(double);
+    c.S = c.ring + (inl ? CS_RING * sizeof(double) : 0);
+    c.xw = c.hx = c.Cb = c.rows;
+    c.recs = c.Pb + 11 * 17 * sizeof(double);
+    c.fixed = c.S;
+    c.launch = c.fixed + (size_t)(n_first + mv_len + 128) * sizeof(double);
+    return c;
+}
+static_assert(cs_carve(false, 0, 0).fixed == 11344 && cs_carve(true, 0, 0).fixed == 15504, "the fixed part, without and with the INL ring");
+static_assert(cs_carve(true, 3594, 160).launch == 46560, "INL at the reference geometry: three workgroups per CU");
+static_assert(cs_carve(true, 0, 0).xw + CS_XW * sizeof(cplx) <= cs_carve(true, 0, 0).hop_sig, "xw fits in rows | Pb");
+static_assert(cs_carve(true, 0, 0).hx + CS_HX * sizeof(cplx) <= cs_carve(true, 0, 0).Pb, "hx fits in rows");
+static_assert(cs_carve(false, 0, 0).Cb + 257 * sizeof(double) <= cs_carve(false, 0, 0).Pb, "Cb fits in rows");
+static_assert(cs_carve(false, 0, 0).recs + 2 * 11 * 4 * sizeof(double) <= cs_carve(false, 0, 0).hop_sig, "recs fits in Pb");
+// a pointer into the carve (every phase forms its pointers from the one base, the kernel's dynamic LDS)
+template <typename T>
+__device__ __forceinline__ T* cs_at(unsigned char* lds, size_t off) { return (T*)(lds + off); }
+// static LDS (the two arrays on 16-byte lines: each is read with whole 16-byte loads)
+struct alignas(16) CsShared {
+    unsigned long long tot2[2];      // the stream's byte sums (prologue)
+    double ws[4];                    // wave totals of the block scan
+    double avg;                      // sum/mv_len seen by the hit window
+    int hit;                    // first hit window (0-based) or INT_MAX
+    int pred;                        // first window the certificate decided as a hit, INT_MAX if none
+    int unc;                         // first window the certificate could not decide, INT_MAX if none
+    int exact;                       // 1: run the exact serial replay
+    int redo;                        // a hop decision sat inside delta: repeat with the exact replay
+    int n;                           // hops of the table walk
+};
+#define CS_NONE 0x7fffffff
+
+// ---- prologue ----
+
+// the front kernel's partial byte sums (the stream's mean): requested by the first wave BEFORE the table loads, so
+// that the two round trips to L2 overlap; summed after them
+__device__ __forceinline__ void cs_partial_sums_request(const CoarseArgs& a, int tid, unsigned long long (&pvi)[4], unsigned long long (&pvq)[4]) {
+    if (tid < 64) {
+        const unsigned long long* pp = a.partial + (size_t)blockIdx.x * a.npartial * 2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int b = tid + 64 * k;
+            if (b < a.npartial) { pvi[k] = pp[2 * b]; pvq[k] = pp[2 * b + 1]; }
+        }
+    }
+}
+__device__ __forceinline__ void cs_partial_sums_total(CsShared& sh, int tid, const unsigned long long (&pvi)[4], const unsigned long long (&pvq)[4]) {
+    if (tid < 64) {
+        unsigned long long si = (pvi[0] + pvi[1]) + (pvi[2] + pvi[3]), sq = (pvq[0] + pvq[1]) + (pvq[2] + pvq[3]);   // (integers: any order)
+        for (int off = 32; off > 0; off >>= 1) {
+            si += __shfl_down(si, off, 64);
+            sq += __shfl_down(sq, off, 64);
+        }
+        if (tid == 0) { sh.tot2[0] = si; sh.tot2[1] = sq; }
+    }
+}
+struct CsMean { double mr, mi; unsigned long long ti, tq; };
+// raw2iq.m:8, as in stream_mean (behind the barrier that follows cs_partial_sums_total)
+__device__ __forceinline__ CsMean cs_stream_mean(const CoarseArgs& a, const CsShared& sh) {
+    CsMean m;
+    m.ti = sh.tot2[0]; m.tq = sh.tot2[1];
+    m.mr = (double)m.ti / (double)a.n0;
+    m.mi = (double)m.tq / (double)a.n0;
+    return m;
+}
+
+// padded copy S = [999 x mv_len | snr[0..nwin) | 0 x 64]: S[q] is the SNR evicted by window q
+// (999 while the history still holds its seed, move_fft_snr_runtime_avg.m:11), S[mv_len+q] is
+// window q's own SNR; every load of the unrolled recurrence of the exact replay is unconditional.  The global loads go out
+// first, 16 per lane in flight, and everything else of the prologue runs under their latency.
+__device__ __forceinline__ void cs_table_load(const CoarseArgs& a, const CoarseGeom& g, double* S, int tid) {
+    const int mv_len = g.mv_len;
+    const double* sg = a.snr_g + (size_t)blockIdx.x * a.snr_stride;
+    const long tot = mv_len + g.nwin + 64;
+    for (long i0 = 0; i0 < tot; i0 += 16 * 256) {
+        double rv[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const long i = i0 + tid + 256 * u;
+            rv[u] = (i >= mv_len && i < mv_len + g.nwin) ? sg[i - mv_len] : (i < mv_len ? 999.0 : 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const long i = i0 + tid + 256 * u;
+            if (i < tot) S[i] = rv[u];
+        }
+    }
+}
+
+// the stream's state, whole 16-byte words (global -> LDS at the start unless it is built here, LDS -> global at the end)
+__device__ __forceinline__ void cs_state_copy(StreamState* to, const StreamState* from, int tid) {
+    const uint4* src = (const uint4*)from;
+    uint4* dst = (uint4*)to;
+    for (int i = tid; i < (int)(sizeof(StreamState) / 16); i += 256) dst[i] = src[i];
+}
+// batch path: this kernel is the first to touch the stream's state -- build it from scratch in LDS (all zero,
+// then, behind a barrier, the sentinels the reference functions start from), no memset / finish-mean launches needed
+__device__ __forceinline__ void cs_state_zero(StreamState* st, int tid) {
+    uint4* dst = (uint4*)st;
+    for (int i = tid; i < (int)(sizeof(StreamState) / 16); i += 256) dst[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+__device__ __forceinline__ void cs_state_init(StreamState* st, const CoarseArgs& a, const CsMean& m) {
+    st->n0 = a.n0;
+    st->sum_i = m.ti; st->sum_q = m.tq;
+    st->mean_re = m.mr; st->mean_im = m.mi;
+    st->sampling_ppm1 = INFINITY; st->carrier_ppm1 = INFINITY;
+    st->sampling_ppm2 = INFINITY; st->carrier_ppm2 = INFINITY;
+    st->fcch_is_sentinel = 1;
+}
+
+// twiddles of the window DFTs (16 included: the hop walk's own spectra)
+__device__ __forceinline__ void cs_twiddles(cplx* tw, int fft_len, int tid) {
+    if (fft_len >= 2 && fft_len <= 64)
+        for (int i = tid; i < fft_len; i += 256) {
+            double sn, cs;
+            sincospi(-2.0 * (double)i / (double)fft_len, &sn, &cs);
+            tw[i] = make_double2(cs, sn);
+        }
+}
+
 // (1) First hit, move_fft_snr_runtime_avg.m:30-42.  The loop is serial only through the ROUNDING of sum_snr (two
 // dependent fp64 adds per window); its decisions (snr - sum_snr/mv_len > th) almost never depend on that rounding.
 // Each thread takes a run of windows, sums the mv_len entries its first window sees directly and slides from there.
@@ -456,28 +604,46 @@ __device__ void d_scan_accept(const StreamState* st, int s, double* snr_numhit, 
 // mv_len * V for the reference's own rounding as here, and the term derived with that form below for its prefixes: 1.2e-9
 // in all).  A window whose margin to the threshold exceeds `delta`
 // (1e-6 + 4x that bound) is decided for good, and the first decided hit stands if no undecided window precedes it.
-// Otherwise (a margin inside delta, a non-finite SNR) wave 0 replays the reference's running-sum updates in the
-// reference's order, 64 windows at a time: every lane advances the same wave-uniform sum from broadcast LDS reads,
-// lane j keeps the sum window j sees, then the 64 lanes evaluate snr - sum/mv_len > th with the true divide of :30
-// and a ballot picks the first hit (~18 ns per window: the latency of two dependent v_add_f64).  mode 1 -- the API's
-// move_fft_snr_runtime_avg, which REPORTS hit_avg_snr -- always takes the exact replay.
-// (2) Hop walk, FCCH_coarse_position.m:32-86 + specific_fft_snr_fix_avg.m:10-25, by wave 0.  A hop looks at the 11
-// windows around +10 frames and, if those all miss, the 11 around +11 frames.  All 22 spectra of a hop come from one
-// pass: lane (group, half, bin k) takes bin k of its half's first window by a direct 16-point DFT and slides it
-// through the next windows (X_k(t+1) = (X_k(t) + x[t+16] - x[t]) e^{+2 pi i k/16}); the powers go through LDS to
-// 22 lanes that form the SNRs (first max, 3 bins, log10) and a ballot applies the reference's first-hit rule.  The
-// samples the NEXT hop can ask for are known one hop early (4 rows of 36 for the four (branch, group) pairs), so
-// every hop also fetches those and the following hop finds its windows in LDS.  With a certified average
-// (1) the hop decisions carry the same delta check; a decision inside delta repeats the stream with the exact replay.
-// WAVES: minimum waves per SIMD the register allocator must leave room for (2: small batches, 4: four workgroups per CU).
-#define CS_ROW 36
-#define CS_RING (2 * 256 + 2 * 4)    // INL: prefixes of the last two rounds (one per window) + their four wave totals
-// inl: the INL form's prefix ring on top (12 368 -> 16 528 bytes; 47 584 with the reference geometry's S, three workgroups per CU)
-__host__ __device__ inline size_t coarse_scan_lds_fixed(bool inl = false) {
-    return ((sizeof(StreamState) + 15) & ~(size_t)15) + 64 * sizeof(cplx) + 4 * CS_ROW * sizeof(cplx) + (2 * 11 * 17 + 2 * MAXH) * sizeof(double) +
-           (inl ? CS_RING * sizeof(double) : 0);
+struct CsCert {
+    double V, delta;
+    int sc_total;                    // entries of S that windows can see
+    int sc_per;                      // entries (and windows) per thread
+};
+__device__ __forceinline__ CsCert cs_cert_delta(const CoarseGeom& g, bool inl_form) {
+    CsCert ce;
+    ce.V = 1000.0;
+    ce.sc_total = g.mv_len + (int)g.nwin;
+    ce.sc_per = (ce.sc_total + 255) / 256;
+    // adds behind a prefix value: a thread's chunk + the block scan, or (inl_form, cs_inline_rounds) the chain through the rounds
+    const double cert_adds = inl_form ? 4.0 * (double)((g.nwin + 255) / 256) + 16.0 : (double)ce.sc_per + 32.0;
+    ce.delta = 1e-6 + 4.0 * 1.1102230246251565e-16 * ce.V *
+                          ((2.0 * (double)g.nwin + (double)g.mv_len + 64.0) +
+                           2.0 * cert_adds * (double)ce.sc_total / (double)g.mv_len);
+    return ce;
+}
+// a margin the certificate cannot vouch for | a window it cannot decide (NaN lands here)
+__device__ __forceinline__ bool cs_margin_open(double mg, double delta) { return !(fabs(mg) > delta); }
+__device__ __forceinline__ bool cs_undecided(double v, double mg, const CsCert& ce) { return !(fabs(v) <= ce.V) || cs_margin_open(mg, ce.delta); }
+
+// no hit, no hops (the start of the moving search, and again before a stream is repeated with the exact replay)
+__device__ __forceinline__ void cs_reset_answer(StreamState* st) {
+    st->n_coarse = 0;
+    st->coarse_hit_flag = 0;
+    st->hit_avg_snr = INFINITY;
+    st->mv_hit_idx = -1.0;
+    st->mv_hit_snr = INFINITY;
 }
 
+// ---- moving search ----
+
+// totals of the waves in front of wave w, always added in this order: both ends of a window's sum come out of the same operations
+__device__ __forceinline__ double cs_waves_before(const double* ws, int w) {
+    double o = 0.0;
+    if (w > 0) o = ws[0];
+    if (w > 1) o += ws[1];
+    if (w > 2) o += ws[2];
+    return o;
+}
 // INL (throughput batches, 16-point windows): the moving search's window SNRs are computed HERE, straight into the LDS copy the
 // scan reads -- k_coarse_snr<true,false>'s arithmetic, value for value -- so the table never makes the trip through HBM and the
 // k_coarse_snr launch in front of this kernel is gone (a.snr_g non-null: it is still written out, for gsmcal_last_batch_snr).
@@ -496,475 +662,617 @@ __host__ __device__ inline size_t coarse_scan_lds_fixed(bool inl = false) {
 // read: the decided hit's average takes S[pred .. pred + mv_len); the replay runs with every round computed or, after a hop
 // decision inside delta, ends at the decided hit, in a 64-window group that lies inside the hit's round; the head windows are
 // redone inside round 0; the hop walk has its own spectra.
+// k_coarse_snr<true, false>: 256 windows per round from the 271 raw samples they cover (the DC term is removed in the
+// spectrum), the next round's samples requested before this round's spectra; in round 0 the head windows again with
+// per-sample DC removal; every round tests its windows.  S = [999 x mv_len | snr | 0 x 64] as in cs_table_load.
+// (The rounds' barriers are the loop's own, in here.)  Returns the rounds computed.
+__device__ __forceinline__ int cs_inline_rounds(const CoarseArgs& a, const CoarseGeom& g, const DecView& s, unsigned char* lds, const CsCarve& cv,
+                                                const CsCert& ce, CsShared& sh, int tid) {
+    const int fft_len = g.fft_len, mv_len = g.mv_len;
+    const double th = g.th;
+    const long len = a.len;
+    double* snr_s = cs_at<double>(lds, cv.S);
+    double* cs_ring = cs_at<double>(lds, cv.ring);             // [2][256] exclusive wave scans | [2][4] wave totals
+    const long nwin = g.nwin;
+    for (int i = tid; i < mv_len; i += 256) snr_s[i] = 999.0;
+    for (int i = tid; i < 64; i += 256) snr_s[mv_len + nwin + i] = 0.0;
+    // the certificate needs window j - mv_len in this round or the one before; otherwise (and in mode 1) the exact replay
+    if (tid == 0) { sh.pred = CS_NONE; sh.unc = (a.mode == 0 && mv_len <= 256) ? CS_NONE : 0; }
+    cplx* xw = cs_at<cplx>(lds, cv.xw);                        // the hop buffers (rows | Pb, 5.3 KB) are not in use yet
+    const cplx* sp = s.s;
+    const cplx z = make_double2(0.0, 0.0);
+    cplx c0 = tid < len ? sp[tid] : z, c1 = (tid < 15 && 256 + tid < len) ? sp[256 + tid] : z;
+    const int lane = tid & 63, wave = tid >> 6;
+    const bool all_rounds = a.snr_g != nullptr;
+    const double inv = 1.0 / (double)mv_len;
+    bool testing = true;                               // block-uniform: every window so far is a decided miss
+    double cbase = 999.0 * (double)mv_len, cbase_prev = cbase;   // C[mv_len + b0] of this round and of the one before (:11-12; exact)
+    int rounds_done = 0;
+    for (long b0 = 0; b0 < nwin; b0 += 256) {
+        xw[tid] = c0;
+        if (tid < 15) xw[256 + tid] = c1;
+        __syncthreads();
+        if (testing) {                                 // the verdict on the rounds before this one
+            const int pred = sh.pred;
+            if (sh.unc < pred) testing = false;
+            else if (pred != CS_NONE) {
+                if (!all_rounds) break;
+                testing = false;
+            }
+        }
+        const long nb = b0 + 256;
+        if (nb < nwin) {
+            c0 = nb + tid < len ? sp[nb + tid] : z;
+            if (tid < 15) c1 = nb + 256 + tid < len ? sp[nb + 256 + tid] : z;
+        }
+        const bool inw = b0 + tid < nwin;
+        double v = 0.0;
+        if (inw) {
+            v = window_snr16_from(s, xw + tid);
+            snr_s[mv_len + b0 + tid] = v;
+        }
+        if (b0 == 0 && s.n_head > 0) {                 // (block-uniform) the head windows again, before they are tested
+            __syncthreads();                           // (xw is read no more)
+            cplx* hx = cs_at<cplx>(lds, cv.hx);
+            const int nh = s.n_head < 8 ? s.n_head : 8;
+            if (tid < nh + fft_len - 1 && tid < g.n_first) hx[tid] = dv_load(s, tid);
+            __syncthreads();
+            if (tid < nh && tid < nwin) {
+                v = window_snr16_head(hx + tid, s.floor2);
+                snr_s[mv_len + tid] = v;
+            }
+        }
+        const int par = (int)(b0 >> 8) & 1;
+        double* ex = cs_ring + par * 256;
+        double* ws = cs_ring + 512 + par * 4;
+        double excl = 0.0;
+        if (testing) {
+            const double inc = wave_scan_incl(v);
+            excl = inc - v;
+            ex[tid] = excl;
+            if (lane == 63) ws[wave] = inc;
+        }
+        __syncthreads();
+        if (testing) {
+            const int j = (int)b0 + tid;               // this thread's window
+            const double chi = (cbase + cs_waves_before(ws, wave)) + excl;        // C[mv_len + j]
+            double clo;                                                        // C[j]
+            if (j < mv_len) clo = 999.0 * (double)j;                           // (exact)
+            else {
+                const int q = j - mv_len, t = q & 255;                         // window q: this round (q >= b0) or the one before
+                const bool same = q >= (int)b0;
+                const int p = same ? par : par ^ 1;
+                clo = ((same ? cbase : cbase_prev) + cs_waves_before(cs_ring + 512 + p * 4, t >> 6)) + cs_ring[p * 256 + t];
+            }
+            const double mg = (v - (chi - clo) * inv) - th;
+            if (inw) {
+                if (cs_undecided(v, mg, ce)) atomicMin(&sh.unc, j);
+                else if (mg > 0.0) atomicMin(&sh.pred, j);
+            }
+            cbase_prev = cbase;
+            cbase += ((ws[0] + ws[1]) + ws[2]) + ws[3];
+        }
+        ++rounds_done;
+    }
+    return rounds_done;
+}
+// the table the rounds computed, on request (behind a barrier)
+__device__ __forceinline__ void cs_table_keep(const CoarseArgs& a, const CoarseGeom& g, const double* S, int tid) {
+    double* tab = a.snr_g + (size_t)blockIdx.x * a.snr_stride;
+    for (long i = tid; i < g.nwin; i += 256) tab[i] = S[g.mv_len + i];
+}
+
+// The block-scan certificate (non-INL), three steps with a barrier behind each:
+// window sums from a block-wide prefix scan of S: C[p] = sum_{i<p} S[i] at every thread's chunk start (Cb) plus
+// a partial chunk sum; window j sees C[j+mv_len] - C[j].  (<= sc_per + 32 fp64 adds of magnitude <= sc_total V per
+// C value: the second term of cert_delta.)
+__device__ __forceinline__ void cs_cert_chunk_sums(const double* snr_s, const CsCert& ce, CsShared& sh, int tid, double& loc, double& inc) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int p0 = tid * ce.sc_per;
+    loc = 0.0;
+    for (int i = 0; i < ce.sc_per; ++i) loc += (p0 + i < ce.sc_total) ? snr_s[p0 + i] : 0.0;
+    inc = wave_scan_incl(loc);
+    if (lane == 63) sh.ws[wave] = inc;
+}
+__device__ __forceinline__ void cs_cert_chunk_starts(double* Cb, const CsShared& sh, int tid, double loc, double inc) {
+    const int wave = tid >> 6;
+    double base = 0.0;
+    for (int i = 0; i < wave; ++i) base += sh.ws[i];
+    Cb[tid] = base + (inc - loc);
+    if (tid == 255) Cb[256] = base + inc;
+}
+__device__ __forceinline__ void cs_cert_block_scan(const double* snr_s, const double* Cb, const CoarseGeom& g, const CsCert& ce, CsShared& sh, int tid) {
+    const int mv_len = g.mv_len, sc_per = ce.sc_per;
+    const int p0 = tid * sc_per;
+    const int j0 = p0, j1 = j0 + sc_per < (int)g.nwin ? j0 + sc_per : (int)g.nwin;
+    if (j0 < j1) {
+        const int idx = j0 + mv_len, bq = idx / sc_per, rq = idx - bq * sc_per;
+        double cx = Cb[bq];
+        for (int i = 0; i < rq; ++i) cx += snr_s[bq * sc_per + i];
+        double sm = cx - Cb[tid];
+        const double inv = 1.0 / (double)mv_len;
+        for (int j = j0; j < j1; ++j) {
+            const double v = snr_s[mv_len + j];
+            const double mg = (v - sm * inv) - g.th;
+            if (cs_undecided(v, mg, ce)) { atomicMin(&sh.unc, j); break; }
+            if (mg > 0.0) { atomicMin(&sh.pred, j); break; }
+            sm += v - snr_s[j];
+        }
+    }
+}
+// wave 0: the average the decided hit sees (64 lanes + a reduction tree: within the same bound)
+__device__ __forceinline__ void cs_cert_hit_average(const double* snr_s, int mv_len, CsShared& sh, int tid) {
+    const int pred = sh.pred;
+    const bool ok = !(sh.unc < pred);
+    double sm = 0.0;
+    if (ok && pred != CS_NONE) {
+        for (int q = tid; q < mv_len; q += 64) sm += snr_s[pred + q];
+    }
+    sm = wave_sum(sm);
+    if (tid == 0) {
+        if (!ok) sh.exact = 1;
+        else if (pred != CS_NONE) { sh.hit = pred; sh.avg = sm / (double)mv_len; }
+    }
+}
+// Without a certified first hit (a margin inside delta, a non-finite SNR) wave 0 replays the reference's running-sum updates in the
+// reference's order, 64 windows at a time: every lane advances the same wave-uniform sum from broadcast LDS reads,
+// lane j keeps the sum window j sees, then the 64 lanes evaluate snr - sum/mv_len > th with the true divide of :30
+// and a ballot picks the first hit (~18 ns per window: the latency of two dependent v_add_f64).  mode 1 -- the API's
+// move_fft_snr_runtime_avg, which REPORTS hit_avg_snr -- always takes the exact replay.
+__device__ __forceinline__ void cs_exact_replay(const double* snr_s, const CoarseGeom& g, CsShared& sh, int lane) {
+    const int mv_len = g.mv_len;
+    const long nwin = g.nwin;
+    const double dmv = (double)mv_len, th = g.th;
+    // :11-12 store = 999*ones(1,mv_len); sum_snr = sum(store): sequential sum of 999s (wave-uniform)
+    double sum_snr = 0.0;
+    for (int i = 0; i < mv_len; ++i) sum_snr += 999.0;
+    for (int base = 0; base < (int)nwin; base += 64) {
+        const int i = base + lane;
+        const double nw = snr_s[mv_len + i];                  // (in-bounds by the zero suffix)
+        double mine = 0.0;
+        const double* So = snr_s + base;                     // evicted values
+        const double* Sn = snr_s + mv_len + base;            // new values
+#pragma unroll
+        for (int j0 = 0; j0 < 64; j0 += 8) {
+            double o[8], v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {                    // wave-uniform (broadcast) LDS reads
+                v[u] = Sn[j0 + u];
+                o[u] = So[j0 + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                mine = lane == j0 + u ? sum_snr : mine;      // the sum window j sees
+                sum_snr = sum_snr - o[u];                    // :37
+                sum_snr = sum_snr + v[u];                    // :38
+            }
+        }                                                    // (updates past nwin are never used)
+        const double avg = mine / dmv;
+        const bool h = i < nwin && (nw - avg > th);          // :30-32 strict >
+        const unsigned long long m = __ballot(h);
+        if (m) {
+            const int f = __ffsll((long long)m) - 1;
+            if (lane == f) { sh.hit = (int)base + f; sh.avg = avg; }
+            break;
+        }
+    }
+}
+// thread 0: the hit as move_fft_snr_runtime_avg returns it
+__device__ __forceinline__ void cs_publish_hit(const double* snr_s, int mv_len, StreamState* st, const CsShared& sh, int hit) {
+    const double h_snr = snr_s[mv_len + hit];
+    const double h_pta = h_snr - sh.avg;
+    st->coarse_hit_flag = 1;
+    st->mv_hit_idx = (double)(hit + 1);
+    st->mv_hit_snr = h_snr;
+    st->hit_avg_snr = h_snr - h_pta;                         // :48
+}
+
+// ---- hop walk ----
+// (2) Hop walk, FCCH_coarse_position.m:32-86 + specific_fft_snr_fix_avg.m:10-25, by wave 0.  A hop looks at the 11
+// windows around +10 frames and, if those all miss, the 11 around +11 frames.  All 22 spectra of a hop come from one
+// pass: lane (group, half, bin k) takes bin k of its half's first window by a direct 16-point DFT and slides it
+// through the next windows (X_k(t+1) = (X_k(t) + x[t+16] - x[t]) e^{+2 pi i k/16}); the powers go through LDS to
+// 22 lanes that form the SNRs (first max, 3 bins, log10) and a ballot applies the reference's first-hit rule.  The
+// samples the NEXT hop can ask for are known one hop early (4 rows of 36 for the four (branch, group) pairs), so
+// every hop also fetches those and the following hop finds its windows in LDS.  With a certified average
+// (1) the hop decisions carry the same delta check; a decision inside delta repeats the stream with the exact replay.
+struct HopGeom { long d0, d1; int max_offset, nt; long limit; };
+__device__ __forceinline__ HopGeom hop_geom(int dec, long len, int fft_len) {
+    HopGeom hg;
+    hg.d0 = (long)round(12500.0 / (double)dec);     // :35 round() half away from zero
+    hg.d1 = (long)round(13750.0 / (double)dec);     // :36
+    hg.max_offset = 5; hg.nt = 2 * hg.max_offset + 1;
+    hg.limit = (len - (fft_len - 1)) - hg.max_offset;
+    return hg;
+}
+// the first hit as hop 0 (one thread)
+__device__ __forceinline__ void cs_hop_first(StreamState* st, long cur, int dec) {
+    st->coarse_pos[0] = (double)((cur - 1) * dec + 1);  // :91
+    st->coarse_snr[0] = st->mv_hit_snr;
+}
+
+// ---- hop loop of FCCH_coarse_position.m:32-86 on the SNR table of the whole stream (k_coarse_snr computed every
+// window, not only those of the moving search): specific_fft_snr_fix_avg.m:10-25 is then 11 table entries and
+// a ballot.  One wave; lanes 0..10 hold the +10-frame candidates, lanes 16..26 the +11-frame ones of the same
+// hop, fetched together.  With a certified average (1) a decision inside cert_delta repeats the stream with
+// the exact replay, as in the moving search.
+__device__ __forceinline__ void cs_walk_table(const CoarseArgs& a, const HopGeom& hg, StreamState* st, CsShared& sh, int hit, bool exact,
+                                              double th, double cert_delta, int lane) {
+    const double* tab = a.snr_g + (size_t)blockIdx.x * a.snr_stride;
+    const double hit_avg_snr = st->hit_avg_snr;
+    const int dec = a.decimation_ratio;
+    const long d0 = hg.d0, d1 = hg.d1;
+    const int max_offset = hg.max_offset, nt = hg.nt;
+    const long limit = hg.limit;
+    const unsigned gmask = (1u << nt) - 1u;
+    long cur = hit + 1;
+    int nn = 1;
+    bool redo = false;
+    if (lane == 0) cs_hop_first(st, cur, dec);
+    const int grp = lane >> 4, ci = lane & 15;
+    while (nn < MAXH) {
+        const long nx0 = cur + d0, nx1 = cur + d1;
+        if (nx0 > limit) break;                              // :49
+        const bool g1ok = nx1 <= limit;                      // :67
+        const bool cand = ci < nt && (grp == 0 || (grp == 1 && g1ok));
+        const long w = (grp ? nx1 : nx0) - max_offset + ci;  // 1-based window
+        const double v = cand ? tab[w - 1] : -INFINITY;
+        const bool is_hit = cand && (v - hit_avg_snr > th);  // NaN compares false
+        const bool is_unc = !exact && cand && cs_margin_open((v - hit_avg_snr) - th, cert_delta);
+        const unsigned long long hb = __ballot(is_hit), ub = __ballot(is_unc);
+        const unsigned h0 = (unsigned)hb & gmask, u0 = (unsigned)ub & gmask;
+        const unsigned h1 = (unsigned)(hb >> 16) & gmask, u1 = (unsigned)(ub >> 16) & gmask;
+        // every candidate the reference looks at (up to the first hit, else all of the group) must be decided for good
+        if (u0 & (h0 ? (2u << (__ffs(h0) - 1)) - 1u : gmask)) { redo = true; break; }
+        int src;
+        long ncur;
+        if (h0) {
+            src = __ffs(h0) - 1;
+            ncur = nx0 - max_offset + src;
+        } else if (g1ok) {                                   // :65 try across the idle frame
+            if (u1 & (h1 ? (2u << (__ffs(h1) - 1)) - 1u : gmask)) { redo = true; break; }
+            if (!h1) break;                                  // both miss
+            src = __ffs(h1) - 1;
+            ncur = nx1 - max_offset + src;
+            src += 16;
+        } else break;                                        // :67
+        if (lane == src) {
+            st->coarse_pos[nn] = (double)((ncur - 1) * dec + 1);
+            st->coarse_snr[nn] = v;
+        }
+        cur = ncur;
+        ++nn;
+    }
+    if (lane == 0) {
+        sh.n = nn;
+        if (redo) sh.redo = 1;
+        st->n_coarse = nn;
+    }
+}
+
+// ---- hop loop of FCCH_coarse_position.m:32-86 (positions 1-based, decimated units) on the walk's own spectra, whole block ----
+// loader threads (tid < 4*CS_ROW): one look-ahead sample each; spectrum threads (tid < 11*16): one
+// (window, bin) each, the 16 bins of window dw in the 16 lanes of one DPP row.  Ratio mode decides a window
+// inside its row: first maximum and total by the reference trees over row DPP moves, the neighbours of every
+// bin by row rotates, and the lane that holds the maximum publishes the window's record (signal, noise,
+// hit / undecided bits).  The exact replay and the generic lengths keep the trip through Pb (the reference's
+// sequential total needs all 16 powers in one lane): lanes < 11 of wave 0 publish the same record a barrier
+// later.  EVERY wave then takes the ballots from the group's 11 records and walks on by itself -- cur, n,
+// took1 and the exits are the same in all of them, nothing goes back through LDS and one barrier per
+// group (records complete) is all a hop of ratio mode needs behind the one for its rows.  The records of the
+// two groups lie apart: a wave may publish the +11-frame group while another still reads the +10-frame one;
+// those of the next hop are written behind that hop's row barrier, which every wave passes with its
+// ballots taken.
+struct HopRows { int r0, r1, off0, off1; };   // row and offset of each group's first window (start nx - 6)
+// Certified decisions without the logarithm: 10 log10(sig/noise) - hit_avg_snr > th  <=>  sig/noise > R,
+// R = 10^((hit_avg_snr + th)/10).  The reference's rounded evaluation sits within 1e-12 dB of the true
+// value and hit_avg_snr within cert_delta of the exactly replayed one, so sig > R (1 + eps) noise is a
+// hit and sig < R (1 - eps) noise a miss for good, eps = 0.2303 cert_delta + 1e-12 (d(ratio)/ratio =
+// ln(10)/10 per dB); anything in between sends the stream to the exact replay.  Only the SNR of the
+// hit a hop settles on is reported: those logarithms are taken after the walk, one lane per hop.
+struct HopRatio { double Rhi, Rlo; };
+__device__ __forceinline__ HopRatio hop_ratio(double hit_avg_snr, double th, double cert_delta) {
+    const double R = exp10((hit_avg_snr + th) / 10.0);
+    const double r_eps = 0.2303 * cert_delta + 1e-12;
+    return HopRatio{R * (1.0 + r_eps), R * (1.0 - r_eps)};
+}
+
+// rows in (this hop's samples into LDS) and look-ahead out (the loads of what the next hop can ask for)
+// pf, pg: this thread's look-ahead sample and its index (-1: outside the stream); pbase: nx_b - 11 of the hop that fetched the rows, b
+// the branch it then took (took1: the +11-frame one)
+__device__ __forceinline__ HopRows cs_hop_fetch(const DecView& s, long len, const HopGeom& hg, cplx* rows, int tid, long nx0, long nx1, bool g1ok,
+                                                bool have_pf, bool took1, long pbase, cplx& pf, long& pg) {
+    HopRows hr{0, 1, 0, 0};
+    const long d0 = hg.d0, d1 = hg.d1;
+    if (have_pf) {
+        // DC removal (DecView) on the way into LDS: the loads themselves were issued a hop ago
+        if (tid < 4 * CS_ROW) rows[tid] = pg < 0 ? make_double2(0.0, 0.0) : dv_fix(s, pf, pg);
+        hr.r0 = took1 ? 2 : 0; hr.r1 = hr.r0 + 1;
+        hr.off0 = (int)((nx0 - 6) - (pbase + d0));
+        hr.off1 = (int)((nx1 - 6) - (pbase + d1));
+    } else if (tid < 64) {                           // first hop: fetch its own 2 x 26 samples now
+        const int gq = tid >> 5, i = tid & 31;
+        if (i < 26) {
+            const long gi = (gq ? nx1 : nx0) - 6 + i;
+            rows[gq * CS_ROW + i] = (gi >= 0 && gi < len && (gq == 0 || g1ok)) ? dv_load(s, gi) : make_double2(0.0, 0.0);
+        }
+    }
+    if (tid < 4 * CS_ROW) {
+        // fetch what the next hop can ask for (plain loads, nothing waits on them in this hop):
+        // rows (branch b, group g) start at nx_b + d_g - 11
+        const int rr = tid / CS_ROW, i = tid - rr * CS_ROW;
+        long gi = ((rr & 2) ? nx1 : nx0) - 11 + ((rr & 1) ? d1 : d0) + i;
+        if (gi < 0 || gi >= len || ((rr & 2) && !g1ok)) gi = -1;
+        pf = s.s[gi < 0 ? 0 : gi];
+        pg = gi;
+    }
+    return hr;
+}
+// ratio mode: candidate dw (move_fft_snr_runtime_avg.m:22-27) inside its row, from the power p of bin dk.  First maximum: the
+// reference tree (pairs, ties and unordered compares to the lower index), both lanes of a pair forming the
+// same result; after xor 1 and xor 2 a quad is uniform, so the mirrors pair the right subtrees.
+__device__ __forceinline__ void cs_hop_decide_row(double p, int dk, int dw, double floor2, const HopRatio& hr, double* rec) {
+    const double pm = dpp_move_f64<0x121, 0xF>(p), pp = dpp_move_f64<0x12F, 0xF>(p);   // row_ror 1 / 15: bins dk - 1, dk + 1 (mod 16)
+    double sig = pm + p;
+    sig = sig + pp;
+    double mv = p, tot = p;
+    int mi = dk;
+#define HOP_ROWSTEP(CTRL, BIT) {                                                                                        \
+        const double ov = dpp_move_f64<CTRL, 0xF>(mv);                                   \
+        const int oi = (int)dpp_move_u32<CTRL, 0xF>((unsigned)mi);                       \
+        const bool up = (dk & (BIT)) != 0;                                               \
+        const double lo = up ? ov : mv, hi = up ? mv : ov;                               \
+        const bool r = hi > lo;                                                          \
+        mv = r ? hi : lo;                                                                \
+        mi = r ? (up ? mi : oi) : (up ? oi : mi);                                        \
+        tot += dpp_move_f64<CTRL, 0xF>(tot);     /* the tree total: (((0+1)+(2+3))+...) */ \
+    }
+    HOP_ROWSTEP(0xB1, 1)                 // quad_perm [1,0,3,2]
+    HOP_ROWSTEP(0x4E, 2)                 // quad_perm [2,3,0,1]
+    HOP_ROWSTEP(0x141, 4)                // row_half_mirror: the other quad
+    HOP_ROWSTEP(0x140, 8)                // row_mirror: the other half
+#undef HOP_ROWSTEP
+    if (dk == mi) {                      // (one lane per row: mv is this lane's own power)
+        const double c_sig = sig, c_noise = tot - sig;   // (the tree total differs from the sequential one by ~1e-16: inside eps)
+        const bool residue = tot <= floor2;              // rounding residue of the DC removal, a NaN SNR: a definite miss
+        const bool okn = c_noise > 0.0 && c_noise < INFINITY && c_sig < INFINITY;
+        const bool is_hit = !residue && okn && c_sig > hr.Rhi * c_noise;
+        const bool is_unc = !residue && !(is_hit || (okn && c_sig < hr.Rlo * c_noise));
+        rec[dw * 4] = c_sig; rec[dw * 4 + 1] = c_noise;
+        ((int*)(rec + dw * 4 + 2))[0] = (is_hit ? 1 : 0) | (is_unc ? 2 : 0);
+    }
+}
+// the SNR of a candidate from all its 16 powers in one lane (move_fft_snr_runtime_avg.m:22-27): the exact replay
+__device__ __forceinline__ double cs_hop_snr16(const double* pr, double floor2) {
+    double P[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) P[k] = pr[k];
+    // first maximum by a tree (ties: the lower index), total by a tree
+    double mv[8]; int mi[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { const bool r = P[2 * k + 1] > P[2 * k]; mv[k] = r ? P[2 * k + 1] : P[2 * k]; mi[k] = 2 * k + (r ? 1 : 0); }
+#pragma unroll
+    for (int w = 4; w >= 1; w >>= 1)
+#pragma unroll
+        for (int k = 0; k < w; ++k) { const bool r = mv[2 * k + 1] > mv[2 * k]; mv[k] = r ? mv[2 * k + 1] : mv[2 * k]; mi[k] = r ? mi[2 * k + 1] : mi[2 * k]; }
+    const double pc = mv[0], pm = pr[(mi[0] + 15) & 15], pp = pr[(mi[0] + 1) & 15];
+    double sig = pm + pc;
+    sig = sig + pp;
+    double tot = 0.0;                    // the reference's sequential sum(chn_tmp): the exact replay
+#pragma unroll
+    for (int k = 0; k < 16; ++k) tot += P[k];
+    double v = 10.0 * log10(sig / (tot - sig));
+    if (tot <= floor2) v = NAN_D;         // rounding residue of the DC removal: 0/0 in the reference (snr_from_power)
+    return v;
+}
+// exact replay and generic lengths: the record of candidate `tid` from its SNR v
+__device__ __forceinline__ void cs_hop_decide_lane(double v, double hit_avg_snr, double th, bool exact, double cert_delta, double* rec, int tid) {
+    const bool is_hit = v - hit_avg_snr > th;    // NaN compares false
+    const bool is_unc = !exact && cs_margin_open((v - hit_avg_snr) - th, cert_delta);
+    rec[tid * 4] = v;
+    ((int*)(rec + tid * 4 + 2))[0] = (is_hit ? 1 : 0) | (is_unc ? 2 : 0);
+}
+// ballots over the group's 11 records, the same in every wave: the hop settles on window `ncur` (HOP_SETTLED), the walk ends
+// (HOP_STOP), or the +11-frame group is tried (HOP_NEXT_GROUP)
+enum { HOP_NEXT_GROUP, HOP_SETTLED, HOP_STOP };
+struct HopTaken { int verdict; long ncur; };
+__device__ __forceinline__ HopTaken cs_hop_take(const double* rec, const HopGeom& hg, StreamState* st, CsShared& sh, double* hop_sig, int dec, int grp,
+                                                long nx0, long nx1, bool g1ok, bool exact, bool ratio_mode, int tid, int n) {
+    const int lane = tid & 63, nt = hg.nt;
+    const bool cand = lane < nt;
+    const double ra = cand ? rec[lane * 4] : 0.0, rb = cand ? rec[lane * 4 + 1] : 0.0;
+    const int bits = cand ? ((const int*)(rec + lane * 4 + 2))[0] : 0;
+    const unsigned long long hm = __ballot((bits & 1) != 0);
+    if (!exact) {
+        // every candidate the reference looks at (up to the first hit, else all of the group) must be
+        // decided for good
+        const unsigned long long unc = __ballot((bits & 2) != 0);
+        const unsigned long long looked = hm ? (2ull << (__ffsll((long long)hm) - 1)) - 1 : (1ull << nt) - 1;
+        if (unc & looked) { if (tid == 0) sh.redo = 1; return HopTaken{HOP_STOP, 0}; }
+    }
+    if (hm) {
+        const int found = __ffsll((long long)hm) - 1;    // candidate the hop settles on
+        const long ncur = (grp ? nx1 : nx0) - hg.max_offset + found;
+        if (tid == found) {
+            st->coarse_pos[n] = (double)((ncur - 1) * dec + 1);
+            if (ratio_mode) { hop_sig[2 * n] = ra; hop_sig[2 * n + 1] = rb; }
+            else st->coarse_snr[n] = ra;
+        }
+        return HopTaken{HOP_SETTLED, ncur};
+    }
+    return HopTaken{(grp == 0 && g1ok) ? HOP_NEXT_GROUP : HOP_STOP, 0};   // :65 try across the idle frame; else :67 / both miss
+}
+// the reported SNRs of hops 1..n-1 (:25), one lane per hop.  Batch path: the value k_coarse_snr's table holds for the
+// window (window_snr16: its FFT, DC term and sequential total), so that a hop reports the same bits whether it was
+// looked up in the full table (small batches, depth 1) or decided on the walk's own spectra (calls in flight,
+// throughput batches) -- "results are identical at every depth" (gsmcal.h) holds for the details too.  The direct
+// DFT's powers differ from the FFT's in the last places (<= 4e-14 dB on the SNR): they decide, with their margin,
+// and are not reported.  (A hop lies >= d0 - 5 windows in: past the head rows; its 16 samples end inside the stream.
+// The reference geometry's forms only: in the general form the 16-point FFT's registers open a scratch frame.)
+template <bool TABLE_VALUE>
+__device__ __forceinline__ void cs_hop_report(const DecView& s, StreamState* st, const double* hop_sig, int dec, bool table_value, bool ratio_mode, int n, int tid) {
+    if (TABLE_VALUE && table_value) {
+        if (tid >= 1 && tid < n) st->coarse_snr[tid] = window_snr16(s, (long)((st->coarse_pos[tid] - 1.0) / (double)dec));
+    } else if (ratio_mode && tid >= 1 && tid < n)
+        st->coarse_snr[tid] = 10.0 * log10(hop_sig[2 * tid] / hop_sig[2 * tid + 1]);
+    if (tid == 0) st->n_coarse = n;
+}
+
+// ---- specific_fft_snr_fix_avg stand-alone (mode 2) ----
+// the reference's loop (specific_fft_snr_fix_avg.m:10-11) indexes window by window: a hit in a window that fits
+// returns before a later window would run past the end of s; only a miss up to there is MATLAB's index error
+struct CsSpecific { long lo, hi, hi_fit, cnt; };
+__device__ __forceinline__ CsSpecific cs_specific_range(const CoarseArgs& a, int fft_len) {
+    CsSpecific r;
+    r.lo = a.t_lo; r.hi = a.t_hi;
+    r.hi_fit = r.hi + fft_len - 1 > a.len ? a.len - (fft_len - 1) : r.hi;
+    r.cnt = r.hi_fit >= r.lo ? r.hi_fit - r.lo + 1 : 0;
+    return r;
+}
+template <bool FFT16>
+__device__ __forceinline__ void cs_specific_window(const DecView& s, const CsSpecific& r, int fft_len, const cplx* tw, double* snr_s, int tid) {
+    for (long i = tid; i < r.cnt; i += 256) snr_s[i] = FFT16 ? window_snr16(s, r.lo - 1 + i) : window_snr_generic(s, r.lo - 1 + i, fft_len, tw);
+}
+// thread 0, behind a barrier: the first window over the fixed average
+__device__ __forceinline__ void cs_specific_first_hit(const CoarseArgs& a, const CsSpecific& r, double th, const double* snr_s, StreamState* st) {
+    bool hit = false;
+    for (long i = 0; i < r.cnt && !hit; ++i)
+        if (snr_s[i] - a.avg_snr > th) {
+            st->coarse_hit_flag = 1;
+            st->mv_hit_idx = (double)(r.lo + i);
+            st->mv_hit_snr = snr_s[i];
+            hit = true;
+        }
+    if (!hit && r.hi_fit < r.hi) set_status(st, 3, GSMCAL_E_INDEX);
+}
+
 template <int WAVES, bool FFT16, bool REFG = false, bool INL = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) k_coarse_scan(StreamState* __restrict__ sts, CoarseArgs a_in) {
     CoarseArgs a = a_in;
     if (REFG) { a.mode = 0; a.decimation_ratio = 8; }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int sh_hit;     // first hit window (0-based) or INT_MAX
-    __shared__ double sh_avg;  // sum/mv_len seen by the hit window
-    __shared__ int sh_pred;    // first window the certificate decided as a hit, INT_MAX if none
-    __shared__ int sh_unc;     // first window the certificate could not decide, INT_MAX if none
-    __shared__ int sh_exact;   // 1: run the exact serial replay
-    __shared__ int sh_redo;    // a hop decision sat inside delta: repeat with the exact replay
-    StreamState* st = (StreamState*)smem;                 // LDS copy of the stream state
-    cplx* tw = (cplx*)(smem + ((sizeof(StreamState) + 15) & ~(size_t)15));
-    cplx* rows = tw + 64;                                 // 4 x CS_ROW samples of the current hop
-    double* Pb = (double*)(rows + 4 * CS_ROW);            // [group][window][17]: powers of the hop's 22 windows
-    double* hop_sig_base = Pb + 2 * 11 * 17;             // (signal, noise) of the hit each hop settled on
-    double* cs_ring = hop_sig_base + 2 * MAXH;            // (INL) [2][256] exclusive wave scans | [2][4] wave totals
-    double* snr_s = cs_ring + (INL ? CS_RING : 0);
+    __shared__ CsShared sh;
     StreamState* st_g = sts + blockIdx.x;
     const long len = a.len;
     const CoarseGeom g = REFG ? CoarseGeom{16, 160, a.th0, 3594L, 3594L - 15L} : coarse_geom<false>(a);   // (derived here, under the latency of the loads below: with the host's values this kernel ran 1.2 us SLOWER)
     const int fft_len = g.fft_len, mv_len = g.mv_len;
     const double th = g.th;
     const int tid = threadIdx.x;
+    const CsCarve cv = cs_carve(INL, g.n_first, mv_len);
+    StreamState* st = cs_at<StreamState>(smem, cv.st);          // LDS copy of the stream state
+    cplx* tw = cs_at<cplx>(smem, cv.tw);
+    cplx* rows = cs_at<cplx>(smem, cv.rows);                    // 4 x CS_ROW samples of the current hop
+    double* Pb = cs_at<double>(smem, cv.Pb);                    // [group][window][17]: powers of the hop's 22 windows
+    double* hop_sig = cs_at<double>(smem, cv.hop_sig);          // (signal, noise) of the hit each hop settled on
+    double* snr_s = cs_at<double>(smem, cv.S);
 #define CS_STAMP(i) DEV_STAMP(KID_COARSE_SCAN, blockIdx.x, i)
     CS_STAMP(0);
     const bool bad = fft_len > 64 || fft_len < 2 || g.n_first > len || (FFT16 != (fft_len == 16));   // s(1:n_first): MATLAB index error
-    // padded copy S = [999 x mv_len | snr[0..nwin) | 0 x 64]: S[q] is the SNR evicted by window q
-    // (999 while the history still holds its seed, move_fft_snr_runtime_avg.m:11), S[mv_len+q] is
-    // window q's own SNR; every load of the unrolled recurrence below is unconditional.  The global loads go out
-    // first, 16 per lane in flight, and everything else of the prologue runs under their latency.
-    // the front kernel's partial byte sums (the stream's mean): requested by the first wave BEFORE the table loads below, so
-    // that the two round trips to L2 overlap; summed after them
+
+    // ---- prologue: the mean, S, the state, the twiddles, the certificate's bound ----
     unsigned long long pvi[4] = {0, 0, 0, 0}, pvq[4] = {0, 0, 0, 0};
     const bool pre_mean = a.mean_corr && a.npartial <= 256;
-    if (pre_mean && tid < 64) {
-        const unsigned long long* pp = a.partial + (size_t)blockIdx.x * a.npartial * 2;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int b = tid + 64 * k;
-            if (b < a.npartial) { pvi[k] = pp[2 * b]; pvq[k] = pp[2 * b + 1]; }
-        }
-    }
-    if (!INL && !bad && a.mode != 2) {
-        const double* sg = a.snr_g + (size_t)blockIdx.x * a.snr_stride;
-        const long tot = mv_len + g.nwin + 64;
-        for (long i0 = 0; i0 < tot; i0 += 16 * 256) {
-            double rv[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const long i = i0 + tid + 256 * u;
-                rv[u] = (i >= mv_len && i < mv_len + g.nwin) ? sg[i - mv_len] : (i < mv_len ? 999.0 : 0.0);
-            }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const long i = i0 + tid + 256 * u;
-                if (i < tot) snr_s[i] = rv[u];
-            }
-        }
-    }
-    double mr0 = 0.0, mi0 = 0.0;
-    unsigned long long ti0 = 0, tq0 = 0;
+    if (pre_mean) cs_partial_sums_request(a, tid, pvi, pvq);
+    if (!INL && !bad && a.mode != 2) cs_table_load(a, g, snr_s, tid);
+    CsMean mean{0.0, 0.0, 0, 0};
     if (pre_mean) {                                                           // batch path: means from the front kernel
-        __shared__ unsigned long long sh_tot2[2];
-        if (tid < 64) {
-            unsigned long long si = (pvi[0] + pvi[1]) + (pvi[2] + pvi[3]), sq = (pvq[0] + pvq[1]) + (pvq[2] + pvq[3]);   // (integers: any order)
-            for (int off = 32; off > 0; off >>= 1) {
-                si += __shfl_down(si, off, 64);
-                sq += __shfl_down(sq, off, 64);
-            }
-            if (tid == 0) { sh_tot2[0] = si; sh_tot2[1] = sq; }
-        }
+        cs_partial_sums_total(sh, tid, pvi, pvq);
         __syncthreads();
-        ti0 = sh_tot2[0]; tq0 = sh_tot2[1];
-        mr0 = (double)ti0 / (double)a.n0;
-        mi0 = (double)tq0 / (double)a.n0;
-    } else if (a.mean_corr) stream_mean(a, blockIdx.x, &mr0, &mi0, &ti0, &tq0);
-    const DecView s = dec_view(a, blockIdx.x, a.mean_corr ? mr0 : st_g->mean_re, a.mean_corr ? mi0 : st_g->mean_im);
+        mean = cs_stream_mean(a, sh);
+    } else if (a.mean_corr) stream_mean(a, blockIdx.x, &mean.mr, &mean.mi, &mean.ti, &mean.tq);   // (whole block: wave 0 adds, barrier)
+    const DecView s = dec_view(a, blockIdx.x, a.mean_corr ? mean.mr : st_g->mean_re, a.mean_corr ? mean.mi : st_g->mean_im);
     if (a.mean_corr) {
-        // batch path: this kernel is the first to touch the stream's state -- build it from scratch in LDS (all zero,
-        // then the sentinels the reference functions start from), no memset / finish-mean launches needed
-        uint4* dst = (uint4*)st;
-        for (int i = tid; i < (int)(sizeof(StreamState) / 16); i += 256) dst[i] = make_uint4(0u, 0u, 0u, 0u);
+        cs_state_zero(st, tid);
         __syncthreads();
-        if (tid == 0) {
-            st->n0 = a.n0;
-            st->sum_i = ti0; st->sum_q = tq0;
-            st->mean_re = mr0; st->mean_im = mi0;
-            st->sampling_ppm1 = INFINITY; st->carrier_ppm1 = INFINITY;
-            st->sampling_ppm2 = INFINITY; st->carrier_ppm2 = INFINITY;
-            st->fcch_is_sentinel = 1;
-        }
-    } else {
-        const uint4* src = (const uint4*)st_g;
-        uint4* dst = (uint4*)st;
-        for (int i = tid; i < (int)(sizeof(StreamState) / 16); i += 256) dst[i] = src[i];
-    }
-    // twiddles of the window DFTs: the batch path with the full SNR table needs them only if its hop walk falls back to
+        if (tid == 0) cs_state_init(st, a, mean);
+    } else cs_state_copy(st, st_g, tid);
+    // the batch path with the full SNR table needs the twiddles only if its hop walk falls back to
     // its own spectra (built there); sincospi on the way to the first barrier costs the whole block ~1 us
     const bool tw_lazy = FFT16 && a.mode == 0 && a.snr_nwin > 0;
-    auto make_tw = [&]() {
-        if (fft_len >= 2 && fft_len <= 64)
-            for (int i = tid; i < fft_len; i += 256) {
-                double sn, cs;
-                sincospi(-2.0 * (double)i / (double)fft_len, &sn, &cs);
-                tw[i] = make_double2(cs, sn);
-            }
-    };
-    if (!tw_lazy) make_tw();
-    const double cert_V = 1000.0;
-    const int sc_total = mv_len + (int)g.nwin;            // entries of S that windows can see
-    const int sc_per = (sc_total + 255) / 256;            // entries (and windows) per thread
-    // adds behind a prefix value: a thread's chunk + the block scan, or (INL && FFT16, above) the chain through the rounds
-    const double cert_adds = (INL && FFT16) ? 4.0 * (double)((g.nwin + 255) / 256) + 16.0 : (double)sc_per + 32.0;
-    const double cert_delta = 1e-6 + 4.0 * 1.1102230246251565e-16 * cert_V *
-                              ((2.0 * (double)g.nwin + (double)mv_len + 64.0) +
-                               2.0 * cert_adds * (double)sc_total / (double)mv_len);
+    if (!tw_lazy) cs_twiddles(tw, fft_len, tid);
+    const CsCert ce = cs_cert_delta(g, INL && FFT16);
+    const double cert_delta = ce.delta;
+
+    // ---- moving search: the first hit ----
     const bool inl_run = INL && FFT16 && !bad && a.mode != 2;
     if (inl_run) {
-        // k_coarse_snr<true, false>: 256 windows per round from the 271 raw samples they cover (the DC term is removed in the
-        // spectrum), the next round's samples requested before this round's spectra; in round 0 the head windows again with
-        // per-sample DC removal; every round tests its windows (see INL above).  S = [999 x mv_len | snr | 0 x 64] as above.
-        const long nwin = g.nwin;
-        for (int i = tid; i < mv_len; i += 256) snr_s[i] = 999.0;
-        for (int i = tid; i < 64; i += 256) snr_s[mv_len + nwin + i] = 0.0;
-        // the certificate needs window j - mv_len in this round or the one before; otherwise (and in mode 1) the exact replay
-        if (tid == 0) { sh_pred = 0x7fffffff; sh_unc = (a.mode == 0 && mv_len <= 256) ? 0x7fffffff : 0; }
-        cplx* xw = rows;                                  // 271 samples: the hop buffers (rows | Pb, 5.3 KB) are not in use yet
-        const cplx* sp = s.s;
-        const cplx z = make_double2(0.0, 0.0);
-        cplx c0 = tid < len ? sp[tid] : z, c1 = (tid < 15 && 256 + tid < len) ? sp[256 + tid] : z;
-        const int lane = tid & 63, wave = tid >> 6;
-        const bool all_rounds = a.snr_g != nullptr;
-        const double inv = 1.0 / (double)mv_len;
-        // totals of the waves in front of wave w, always added in this order: both ends of a window's sum come out of the same operations
-        auto waves_before = [](const double* ws, int w) {
-            double o = 0.0;
-            if (w > 0) o = ws[0];
-            if (w > 1) o += ws[1];
-            if (w > 2) o += ws[2];
-            return o;
-        };
-        bool testing = true;                               // block-uniform: every window so far is a decided miss
-        double cbase = 999.0 * (double)mv_len, cbase_prev = cbase;   // C[mv_len + b0] of this round and of the one before (:11-12; exact)
-#ifdef GSMCAL_DEVTIMING
-        int rounds_done = 0;
-#endif
-        for (long b0 = 0; b0 < nwin; b0 += 256) {
-            xw[tid] = c0;
-            if (tid < 15) xw[256 + tid] = c1;
-            __syncthreads();
-            if (testing) {                                 // the verdict on the rounds before this one
-                const int pred = sh_pred;
-                if (sh_unc < pred) testing = false;
-                else if (pred != 0x7fffffff) {
-                    if (!all_rounds) break;
-                    testing = false;
-                }
-            }
-            const long nb = b0 + 256;
-            if (nb < nwin) {
-                c0 = nb + tid < len ? sp[nb + tid] : z;
-                if (tid < 15) c1 = nb + 256 + tid < len ? sp[nb + 256 + tid] : z;
-            }
-            const bool inw = b0 + tid < nwin;
-            double v = 0.0;
-            if (inw) {
-                v = window_snr16_from(s, xw + tid);
-                snr_s[mv_len + b0 + tid] = v;
-            }
-            if (b0 == 0 && s.n_head > 0) {                 // (block-uniform) the head windows again, before they are tested
-                __syncthreads();                           // (xw is read no more)
-                cplx* hx = rows;
-                const int nh = s.n_head < 8 ? s.n_head : 8;
-                if (tid < nh + fft_len - 1 && tid < g.n_first) hx[tid] = dv_load(s, tid);
-                __syncthreads();
-                if (tid < nh && tid < nwin) {
-                    v = window_snr16_head(hx + tid, s.floor2);
-                    snr_s[mv_len + tid] = v;
-                }
-            }
-            const int par = (int)(b0 >> 8) & 1;
-            double* ex = cs_ring + par * 256;
-            double* ws = cs_ring + 512 + par * 4;
-            double excl = 0.0;
-            if (testing) {
-                const double inc = wave_scan_incl(v);
-                excl = inc - v;
-                ex[tid] = excl;
-                if (lane == 63) ws[wave] = inc;
-            }
-            __syncthreads();
-            if (testing) {
-                const int j = (int)b0 + tid;               // this thread's window
-                const double chi = (cbase + waves_before(ws, wave)) + excl;        // C[mv_len + j]
-                double clo;                                                        // C[j]
-                if (j < mv_len) clo = 999.0 * (double)j;                           // (exact)
-                else {
-                    const int q = j - mv_len, t = q & 255;                         // window q: this round (q >= b0) or the one before
-                    const bool same = q >= (int)b0;
-                    const int p = same ? par : par ^ 1;
-                    clo = ((same ? cbase : cbase_prev) + waves_before(cs_ring + 512 + p * 4, t >> 6)) + cs_ring[p * 256 + t];
-                }
-                const double mg = (v - (chi - clo) * inv) - th;
-                if (inw) {
-                    if (!(fabs(v) <= cert_V) || !(fabs(mg) > cert_delta)) atomicMin(&sh_unc, j);   // (NaN lands here)
-                    else if (mg > 0.0) atomicMin(&sh_pred, j);
-                }
-                cbase_prev = cbase;
-                cbase += ((ws[0] + ws[1]) + ws[2]) + ws[3];
-            }
-#ifdef GSMCAL_DEVTIMING
-            ++rounds_done;
-#endif
-        }
+        [[maybe_unused]] const int rounds_done = cs_inline_rounds(a, g, s, smem, cv, ce, sh, tid);
 #ifdef GSMCAL_DEVTIMING
         if (g_stamps && tid == 0 && blockIdx.x < DEV_STAMP_BLOCKS)       // rounds computed (word 15: below any time stamp, no phase)
             g_stamps[((size_t)KID_COARSE_SCAN * DEV_STAMP_BLOCKS + blockIdx.x) * 16 + 15] = (unsigned long long)rounds_done;
 #endif
         if (a.snr_g) {
             __syncthreads();
-            double* tab = a.snr_g + (size_t)blockIdx.x * a.snr_stride;
-            for (long i = tid; i < nwin; i += 256) tab[i] = snr_s[mv_len + i];
+            cs_table_keep(a, g, snr_s, tid);
         }
     }
     __syncthreads();
     const bool want_cert = !bad && a.mode == 0;
     if (tid == 0) {
-        st->n_coarse = 0;
-        st->coarse_hit_flag = 0;
-        st->hit_avg_snr = INFINITY;
-        st->mv_hit_idx = -1.0;
-        st->mv_hit_snr = INFINITY;
-        sh_hit = 0x7fffffff;
+        cs_reset_answer(st);
+        sh.hit = CS_NONE;
         if (!inl_run) {                                    // (the rounds above have posted their verdicts)
-            sh_pred = 0x7fffffff;
-            sh_unc = 0x7fffffff;
+            sh.pred = CS_NONE;
+            sh.unc = CS_NONE;
         }
-        sh_exact = want_cert ? 0 : 1;
-        sh_redo = 0;
+        sh.exact = want_cert ? 0 : 1;
+        sh.redo = 0;
         if (bad) set_status(st, 3, GSMCAL_E_INDEX);
     }
     __syncthreads();
     int n = 0;
     CS_STAMP(1);
     if (want_cert) {
-      if (!(INL && FFT16)) {
-        // window sums from a block-wide prefix scan of S: C[p] = sum_{i<p} S[i] at every thread's chunk start (Cb) plus
-        // a partial chunk sum; window j sees C[j+mv_len] - C[j].  (<= sc_per + 32 fp64 adds of magnitude <= sc_total V per
-        // C value: the second term of cert_delta.)
-        __shared__ double sh_ws[4];
-        double* Cb = (double*)rows;                        // 257 doubles; the hop buffers are not in use yet
-        const int lane = tid & 63, wave = tid >> 6;
-        const int p0 = tid * sc_per;
-        double loc = 0.0;
-        for (int i = 0; i < sc_per; ++i) loc += (p0 + i < sc_total) ? snr_s[p0 + i] : 0.0;
-        const double inc = wave_scan_incl(loc);
-        if (lane == 63) sh_ws[wave] = inc;
-        __syncthreads();
-        double base = 0.0;
-        for (int i = 0; i < wave; ++i) base += sh_ws[i];
-        Cb[tid] = base + (inc - loc);
-        if (tid == 255) Cb[256] = base + inc;
-        __syncthreads();
-        const int j0 = p0, j1 = j0 + sc_per < (int)g.nwin ? j0 + sc_per : (int)g.nwin;
-        if (j0 < j1) {
-            const int idx = j0 + mv_len, bq = idx / sc_per, rq = idx - bq * sc_per;
-            double cx = Cb[bq];
-            for (int i = 0; i < rq; ++i) cx += snr_s[bq * sc_per + i];
-            double sm = cx - Cb[tid];
-            const double inv = 1.0 / (double)mv_len;
-            for (int j = j0; j < j1; ++j) {
-                const double v = snr_s[mv_len + j];
-                const double mg = (v - sm * inv) - th;
-                if (!(fabs(v) <= cert_V) || !(fabs(mg) > cert_delta)) { atomicMin(&sh_unc, j); break; }   // (NaN lands here)
-                if (mg > 0.0) { atomicMin(&sh_pred, j); break; }
-                sm += v - snr_s[j];
-            }
+        if (!(INL && FFT16)) {
+            double loc, inc;
+            double* Cb = cs_at<double>(smem, cv.Cb);                 // the hop buffers are not in use yet
+            cs_cert_chunk_sums(snr_s, ce, sh, tid, loc, inc);
+            __syncthreads();
+            cs_cert_chunk_starts(Cb, sh, tid, loc, inc);
+            __syncthreads();
+            cs_cert_block_scan(snr_s, Cb, g, ce, sh, tid);
+            __syncthreads();
         }
-        __syncthreads();
-      }
-        if (tid < 64) {
-            // the average the decided hit sees (64 lanes + a reduction tree: within the same bound)
-            const int pred = sh_pred;
-            const bool ok = !(sh_unc < pred);
-            double sm = 0.0;
-            if (ok && pred != 0x7fffffff) {
-                for (int q = tid; q < mv_len; q += 64) sm += snr_s[pred + q];
-            }
-            sm = wave_sum(sm);
-            if (tid == 0) {
-                if (!ok) sh_exact = 1;
-                else if (pred != 0x7fffffff) { sh_hit = pred; sh_avg = sm / (double)mv_len; }
-            }
-        }
+        if (tid < 64) cs_cert_hit_average(snr_s, mv_len, sh, tid);
         __syncthreads();
     }
     CS_STAMP(2);
     if (!bad && a.mode != 2) {
       for (int pass = 0; pass < 2; ++pass) {               // pass 1 only after a hop decision fell inside delta
-        // ---- move_fft_snr_runtime_avg ----
-        const long nwin = g.nwin;
-        const double dmv = (double)mv_len;
-        const bool exact = sh_exact != 0;                  // block-uniform
-        if (tid < 64 && exact) {
-            const int lane = tid;
-            // :11-12 store = 999*ones(1,mv_len); sum_snr = sum(store): sequential sum of 999s (wave-uniform)
-            double sum_snr = 0.0;
-            for (int i = 0; i < mv_len; ++i) sum_snr += 999.0;
-            for (int base = 0; base < (int)nwin; base += 64) {
-                const int i = base + lane;
-                const double nw = snr_s[mv_len + i];                  // (in-bounds by the zero suffix)
-                double mine = 0.0;
-                const double* So = snr_s + base;                     // evicted values
-                const double* Sn = snr_s + mv_len + base;            // new values
-#pragma unroll
-                for (int j0 = 0; j0 < 64; j0 += 8) {
-                    double o[8], v[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {                    // wave-uniform (broadcast) LDS reads
-                        v[u] = Sn[j0 + u];
-                        o[u] = So[j0 + u];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        mine = lane == j0 + u ? sum_snr : mine;      // the sum window j sees
-                        sum_snr = sum_snr - o[u];                    // :37
-                        sum_snr = sum_snr + v[u];                    // :38
-                    }
-                }                                                    // (updates past nwin are never used)
-                const double avg = mine / dmv;
-                const bool h = i < nwin && (nw - avg > th);          // :30-32 strict >
-                const unsigned long long m = __ballot(h);
-                if (m) {
-                    const int f = __ffsll((long long)m) - 1;
-                    if (lane == f) { sh_hit = (int)base + f; sh_avg = avg; }
-                    break;
-                }
-            }
-        }
+        const bool exact = sh.exact != 0;                  // block-uniform
+        if (tid < 64 && exact) cs_exact_replay(snr_s, g, sh, tid);
         __syncthreads();
         CS_STAMP(3);
-        const int hit = sh_hit;
-        if (hit != 0x7fffffff && tid == 0) {
-            const double h_snr = snr_s[mv_len + hit];
-            const double h_pta = h_snr - sh_avg;
-            st->coarse_hit_flag = 1;
-            st->mv_hit_idx = (double)(hit + 1);
-            st->mv_hit_snr = h_snr;
-            st->hit_avg_snr = h_snr - h_pta;                         // :48
-        }
+        const int hit = sh.hit;
+        if (hit != CS_NONE && tid == 0) cs_publish_hit(snr_s, mv_len, st, sh, hit);
         __syncthreads();
+
+        // ---- hop walk ----
         if (a.mode == 0) {
-            if (hit == 0x7fffffff) {
+            const int dec = a.decimation_ratio;
+            if (hit == CS_NONE) {
                 if (tid == 0) set_status(st, 3, GSMCAL_S_NO_FCCH);
             } else if (FFT16 && a.snr_nwin >= len - (fft_len - 1) &&
                        st->hit_avg_snr + th > a.snr_screen_db + 1e-6 + (exact ? 0.0 : cert_delta)) {
-                // ---- hop loop of FCCH_coarse_position.m:32-86 on the SNR table of the whole stream (k_coarse_snr computed every
-                // window, not only those of the moving search): specific_fft_snr_fix_avg.m:10-25 is then 11 table entries and
-                // a ballot.  One wave; lanes 0..10 hold the +10-frame candidates, lanes 16..26 the +11-frame ones of the same
-                // hop, fetched together.  With a certified average (1) a decision inside cert_delta repeats the stream with
-                // the exact replay, as in the moving search.
-                __shared__ int sh_n;
-                if (tid < 64) {
-                    const int lane = tid;
-                    const double* tab = a.snr_g + (size_t)blockIdx.x * a.snr_stride;
-                    const double hit_avg_snr = st->hit_avg_snr;
-                    const int dec = a.decimation_ratio;
-                    const long d0 = (long)round(12500.0 / (double)dec);     // :35 round() half away from zero
-                    const long d1 = (long)round(13750.0 / (double)dec);     // :36
-                    const int max_offset = 5, nt = 2 * max_offset + 1;
-                    const long limit = (len - (fft_len - 1)) - max_offset;
-                    const unsigned gmask = (1u << nt) - 1u;
-                    long cur = hit + 1;
-                    int nn = 1;
-                    bool redo = false;
-                    if (lane == 0) {
-                        st->coarse_pos[0] = (double)((cur - 1) * dec + 1);  // :91
-                        st->coarse_snr[0] = st->mv_hit_snr;
-                    }
-                    const int grp = lane >> 4, ci = lane & 15;
-                    while (nn < MAXH) {
-                        const long nx0 = cur + d0, nx1 = cur + d1;
-                        if (nx0 > limit) break;                              // :49
-                        const bool g1ok = nx1 <= limit;                      // :67
-                        const bool cand = ci < nt && (grp == 0 || (grp == 1 && g1ok));
-                        const long w = (grp ? nx1 : nx0) - max_offset + ci;  // 1-based window
-                        const double v = cand ? tab[w - 1] : -INFINITY;
-                        const bool is_hit = cand && (v - hit_avg_snr > th);  // NaN compares false
-                        const bool is_unc = !exact && cand && !(fabs((v - hit_avg_snr) - th) > cert_delta);
-                        const unsigned long long hb = __ballot(is_hit), ub = __ballot(is_unc);
-                        const unsigned h0 = (unsigned)hb & gmask, u0 = (unsigned)ub & gmask;
-                        const unsigned h1 = (unsigned)(hb >> 16) & gmask, u1 = (unsigned)(ub >> 16) & gmask;
-                        // every candidate the reference looks at (up to the first hit, else all of the group) must be decided for good
-                        if (u0 & (h0 ? (2u << (__ffs(h0) - 1)) - 1u : gmask)) { redo = true; break; }
-                        int src;
-                        long ncur;
-                        if (h0) {
-                            src = __ffs(h0) - 1;
-                            ncur = nx0 - max_offset + src;
-                        } else if (g1ok) {                                   // :65 try across the idle frame
-                            if (u1 & (h1 ? (2u << (__ffs(h1) - 1)) - 1u : gmask)) { redo = true; break; }
-                            if (!h1) break;                                  // both miss
-                            src = __ffs(h1) - 1;
-                            ncur = nx1 - max_offset + src;
-                            src += 16;
-                        } else break;                                        // :67
-                        if (lane == src) {
-                            st->coarse_pos[nn] = (double)((ncur - 1) * dec + 1);
-                            st->coarse_snr[nn] = v;
-                        }
-                        cur = ncur;
-                        ++nn;
-                    }
-                    if (lane == 0) {
-                        sh_n = nn;
-                        if (redo) sh_redo = 1;
-                        st->n_coarse = nn;
-                    }
-                }
+                if (tid < 64) cs_walk_table(a, hop_geom(dec, len, fft_len), st, sh, hit, exact, th, cert_delta, tid);
                 __syncthreads();
-                n = sh_n;
+                n = sh.n;
             } else {
-                // ---- hop loop of FCCH_coarse_position.m:32-86 (positions 1-based, decimated units), whole block ----
-                if (tw_lazy) make_tw();                                  // (block-uniform; the barrier below the set-up covers it)
-                const int lane = tid & 63;
+                if (tw_lazy) cs_twiddles(tw, fft_len, tid);              // (block-uniform; the barrier below the set-up covers it)
                 const double hit_avg_snr = st->hit_avg_snr;
-                const int dec = a.decimation_ratio;
-                const long d0 = (long)round(12500.0 / (double)dec);     // :35 round() half away from zero
-                const long d1 = (long)round(13750.0 / (double)dec);     // :36
-                const int max_offset = 5, nt = 2 * max_offset + 1;
-                const long limit = (len - (fft_len - 1)) - max_offset;
-                long cur = hit + 1;
-                n = 1;
-                if (tid == 0) {
-                    st->coarse_pos[0] = (double)((cur - 1) * dec + 1);  // :91
-                    st->coarse_snr[0] = st->mv_hit_snr;
-                }
-                // Certified decisions without the logarithm: 10 log10(sig/noise) - hit_avg_snr > th  <=>  sig/noise > R,
-                // R = 10^((hit_avg_snr + th)/10).  The reference's rounded evaluation sits within 1e-12 dB of the true
-                // value and hit_avg_snr within cert_delta of the exactly replayed one, so sig > R (1 + eps) noise is a
-                // hit and sig < R (1 - eps) noise a miss for good, eps = 0.2303 cert_delta + 1e-12 (d(ratio)/ratio =
-                // ln(10)/10 per dB); anything in between sends the stream to the exact replay.  Only the SNR of the
-                // hit a hop settles on is reported: those logarithms are taken after the walk, one lane per hop.
-                const double R = exp10((hit_avg_snr + th) / 10.0);
-                const double r_eps = 0.2303 * cert_delta + 1e-12;
-                const double Rhi = R * (1.0 + r_eps), Rlo = R * (1.0 - r_eps);
-                double* hop_sig = hop_sig_base;
+                const HopGeom hg = hop_geom(dec, len, fft_len);
+                const HopRatio hrat = hop_ratio(hit_avg_snr, th, cert_delta);
                 constexpr bool fast = FFT16;
                 const bool ratio_mode = !exact && fast;
-                // loader threads (tid < 4*CS_ROW): one look-ahead sample each; spectrum threads (tid < 11*16): one
-                // (window, bin) each, the 16 bins of window dw in the 16 lanes of one DPP row.  Ratio mode decides a window
-                // inside its row: first maximum and total by the reference trees over row DPP moves, the neighbours of every
-                // bin by row rotates, and the lane that holds the maximum publishes the window's record (signal, noise,
-                // hit / undecided bits).  The exact replay and the generic lengths keep the trip through Pb (the reference's
-                // sequential total needs all 16 powers in one lane): lanes < 11 of wave 0 publish the same record a barrier
-                // later.  EVERY wave then takes the ballots from the group's 11 records and walks on by itself -- cur, n,
-                // took1 and the exits are the same in all of them, nothing goes back through LDS and one barrier per
-                // group (records complete) is all a hop of ratio mode needs behind the one for its rows.  The records of the
-                // two groups lie apart: a wave may publish the +11-frame group while another still reads the +10-frame one;
-                // those of the next hop are written behind that hop's row barrier, which every wave passes with its
-                // ballots taken.
-                double* recs = Pb + 11 * 17;                               // [group][window][4]: a | b | bits (int) | -
+                double* recs = cs_at<double>(smem, cv.recs);                     // [group][window][4]: a | b | bits (int) | -
+                long cur = hit + 1;
+                n = 1;
+                if (tid == 0) cs_hop_first(st, cur, dec);
                 bool took1 = false;                                        // the hop before settled on a +11-frame candidate
                 cplx pf = make_double2(0.0, 0.0);
                 long pg = -1;
                 long pbase0 = 0, pbase1 = 0;                               // nx0 - 11, nx1 - 11 of the hop that fetched the rows
                 bool have_pf = false;
-                const cplx* sraw = s.s;
                 const int dw = tid >> 4, dk = tid & 15;                    // spectrum role
                 __syncthreads();
 #ifdef GSMCAL_DEVTIMING
@@ -978,36 +1286,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
 #define HOP_CYC(i) do { } while (0)
 #endif
                 while (n < MAXH) {                                         // (cur, n: block-uniform)
-                    const long nx0 = cur + d0, nx1 = cur + d1;
-                    if (nx0 > limit) break;                              // :49
+                    const long nx0 = cur + hg.d0, nx1 = cur + hg.d1;
+                    if (nx0 > hg.limit) break;                           // :49
 #ifdef GSMCAL_DEVTIMING
                     c0 = __builtin_readcyclecounter();
 #endif
-                    const bool g1ok = nx1 <= limit;
-                    int r0 = 0, r1 = 1, off0 = 0, off1 = 0;              // row and offset of each group's first window (start nx - 6)
+                    const bool g1ok = nx1 <= hg.limit;
+                    HopRows hr{0, 1, 0, 0};
                     if (fast) {
-                        if (have_pf) {
-                            // DC removal (DecView) on the way into LDS: the loads themselves were issued a hop ago
-                            if (tid < 4 * CS_ROW) rows[tid] = pg < 0 ? make_double2(0.0, 0.0) : dv_fix(s, pf, pg);
-                            r0 = took1 ? 2 : 0; r1 = r0 + 1;
-                            off0 = (int)((nx0 - 6) - ((took1 ? pbase1 : pbase0) + d0));
-                            off1 = (int)((nx1 - 6) - ((took1 ? pbase1 : pbase0) + d1));
-                        } else if (tid < 64) {                           // first hop: fetch its own 2 x 26 samples now
-                            const int gq = tid >> 5, i = tid & 31;
-                            if (i < 26) {
-                                const long gi = (gq ? nx1 : nx0) - 6 + i;
-                                rows[gq * CS_ROW + i] = (gi >= 0 && gi < len && (gq == 0 || g1ok)) ? dv_load(s, gi) : make_double2(0.0, 0.0);
-                            }
-                        }
-                        if (tid < 4 * CS_ROW) {
-                            // fetch what the next hop can ask for (plain loads, nothing waits on them in this hop):
-                            // rows (branch b, group g) start at nx_b + d_g - 11
-                            const int rr = tid / CS_ROW, i = tid - rr * CS_ROW;
-                            long gi = ((rr & 2) ? nx1 : nx0) - 11 + ((rr & 1) ? d1 : d0) + i;
-                            if (gi < 0 || gi >= len || ((rr & 2) && !g1ok)) gi = -1;
-                            pf = sraw[gi < 0 ? 0 : gi];
-                            pg = gi;
-                        }
+                        hr = cs_hop_fetch(s, len, hg, rows, tid, nx0, nx1, g1ok, have_pf, took1, took1 ? pbase1 : pbase0, pf, pg);
                         pbase0 = nx0 - 11; pbase1 = nx1 - 11;
                         have_pf = true;
                     }
@@ -1018,8 +1305,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                     for (int grp = 0; grp < 2 && !stop && !settled; ++grp) {   // +10-frame candidates, then (rarely) the +11-frame ones
                         double* rec = recs + grp * (11 * 4);
                         if (fast) {
-                            if (tid < nt * 16) {                         // bin dk of window dw: direct 16-point DFT, four partial sums
-                                const cplx* x = rows + (grp ? r1 : r0) * CS_ROW + (grp ? off1 : off0) + dw;
+                            if (tid < hg.nt * 16) {                      // bin dk of window dw: direct 16-point DFT, four partial sums
+                                // phase "cs_hop_dft16", left inline: as a function it is simplified on its own before it is inlined,
+                                // and the 16-point instantiations then spill ~65 registers around the walk (208 .. 232 bytes of scratch)
+                                const cplx* x = rows + (grp ? hr.r1 : hr.r0) * CS_ROW + (grp ? hr.off1 : hr.off0) + dw;
                                 double pr_[4] = {0.0, 0.0, 0.0, 0.0}, pi_[4] = {0.0, 0.0, 0.0, 0.0};
                                 // the two LDS reads of step m + 3 (sample and twiddle) go out ahead of the FMAs of step m: four steps
                                 // in registers, the scheduler kept from sinking a read down to its first use.  (The 15 twiddle
@@ -1044,101 +1333,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
 #undef HOP_LOAD
                                 const double xr = (pr_[0] + pr_[1]) + (pr_[2] + pr_[3]), xi = (pi_[0] + pi_[1]) + (pi_[2] + pi_[3]);
                                 const double p = xr * xr + xi * xi;
-                                if (ratio_mode) {
-                                    // candidate dw (move_fft_snr_runtime_avg.m:22-27) inside its row.  First maximum: the reference
-                                    // tree (pairs, ties and unordered compares to the lower index), both lanes of a pair forming the
-                                    // same result; after xor 1 and xor 2 a quad is uniform, so the mirrors pair the right subtrees.
-                                    const double pm = dpp_move_f64<0x121, 0xF>(p), pp = dpp_move_f64<0x12F, 0xF>(p);   // row_ror 1 / 15: bins dk - 1, dk + 1 (mod 16)
-                                    double sig = pm + p;
-                                    sig = sig + pp;
-                                    double mv = p, tot = p;
-                                    int mi = dk;
-#define HOP_ROWSTEP(CTRL, BIT) {                                                                                        \
-                                        const double ov = dpp_move_f64<CTRL, 0xF>(mv);                                   \
-                                        const int oi = (int)dpp_move_u32<CTRL, 0xF>((unsigned)mi);                       \
-                                        const bool up = (dk & (BIT)) != 0;                                               \
-                                        const double lo = up ? ov : mv, hi = up ? mv : ov;                               \
-                                        const bool r = hi > lo;                                                          \
-                                        mv = r ? hi : lo;                                                                \
-                                        mi = r ? (up ? mi : oi) : (up ? oi : mi);                                        \
-                                        tot += dpp_move_f64<CTRL, 0xF>(tot);     /* the tree total: (((0+1)+(2+3))+...) */ \
-                                    }
-                                    HOP_ROWSTEP(0xB1, 1)                 // quad_perm [1,0,3,2]
-                                    HOP_ROWSTEP(0x4E, 2)                 // quad_perm [2,3,0,1]
-                                    HOP_ROWSTEP(0x141, 4)                // row_half_mirror: the other quad
-                                    HOP_ROWSTEP(0x140, 8)                // row_mirror: the other half
-#undef HOP_ROWSTEP
-                                    if (dk == mi) {                      // (one lane per row: mv is this lane's own power)
-                                        const double c_sig = sig, c_noise = tot - sig;   // (the tree total differs from the sequential one by ~1e-16: inside eps)
-                                        const bool residue = tot <= s.floor2;            // rounding residue of the DC removal, a NaN SNR: a definite miss
-                                        const bool okn = c_noise > 0.0 && c_noise < INFINITY && c_sig < INFINITY;
-                                        const bool is_hit = !residue && okn && c_sig > Rhi * c_noise;
-                                        const bool is_unc = !residue && !(is_hit || (okn && c_sig < Rlo * c_noise));
-                                        rec[dw * 4] = c_sig; rec[dw * 4 + 1] = c_noise;
-                                        ((int*)(rec + dw * 4 + 2))[0] = (is_hit ? 1 : 0) | (is_unc ? 2 : 0);
-                                    }
-                                } else Pb[dw * 17 + dk] = p;
+                                if (ratio_mode) cs_hop_decide_row(p, dk, dw, s.floor2, hrat, rec);
+                                else Pb[dw * 17 + dk] = p;
                             }
                             HOP_CYC(2);
                             if (!ratio_mode) __syncthreads();            // (block-uniform)
                         }
-                        if (!ratio_mode && tid < nt) {                   // candidate `tid`, from all its powers in one lane
-                            double v = -INFINITY;
-                            if (fast) {
-                                {                                        // (move_fft_snr_runtime_avg.m:22-27)
-                                    double P[16];
-                                    const double* pr = Pb + tid * 17;
-#pragma unroll
-                                    for (int k = 0; k < 16; ++k) P[k] = pr[k];
-                                    // first maximum by a tree (ties: the lower index), total by a tree
-                                    double mv[8]; int mi[8];
-#pragma unroll
-                                    for (int k = 0; k < 8; ++k) { const bool r = P[2 * k + 1] > P[2 * k]; mv[k] = r ? P[2 * k + 1] : P[2 * k]; mi[k] = 2 * k + (r ? 1 : 0); }
-#pragma unroll
-                                    for (int w = 4; w >= 1; w >>= 1)
-#pragma unroll
-                                        for (int k = 0; k < w; ++k) { const bool r = mv[2 * k + 1] > mv[2 * k]; mv[k] = r ? mv[2 * k + 1] : mv[2 * k]; mi[k] = r ? mi[2 * k + 1] : mi[2 * k]; }
-                                    const double pc = mv[0], pm = pr[(mi[0] + 15) & 15], pp = pr[(mi[0] + 1) & 15];
-                                    double sig = pm + pc;
-                                    sig = sig + pp;
-                                    double tot = 0.0;                    // the reference's sequential sum(chn_tmp): the exact replay
-#pragma unroll
-                                    for (int k = 0; k < 16; ++k) tot += P[k];
-                                    v = 10.0 * log10(sig / (tot - sig));
-                                    if (tot <= s.floor2) v = NAN_D;       // rounding residue of the DC removal: 0/0 in the reference (snr_from_power)
-                                }
-                            } else v = window_snr_generic(s, (grp ? nx1 : nx0) - max_offset - 1 + tid, fft_len, tw);
-                            const bool is_hit = v - hit_avg_snr > th;    // NaN compares false
-                            const bool is_unc = !exact && !(fabs((v - hit_avg_snr) - th) > cert_delta);
-                            rec[tid * 4] = v;
-                            ((int*)(rec + tid * 4 + 2))[0] = (is_hit ? 1 : 0) | (is_unc ? 2 : 0);
+                        if (!ratio_mode && tid < hg.nt) {                // candidate `tid`, from all its powers in one lane
+                            const double v = fast ? cs_hop_snr16(Pb + tid * 17, s.floor2)
+                                                  : window_snr_generic(s, (grp ? nx1 : nx0) - hg.max_offset - 1 + tid, fft_len, tw);
+                            cs_hop_decide_lane(v, hit_avg_snr, th, exact, cert_delta, rec, tid);
                         }
                         __syncthreads();                                 // the group's 11 records are complete
-                        {
-                            const bool cand = lane < nt;
-                            const double ra = cand ? rec[lane * 4] : 0.0, rb = cand ? rec[lane * 4 + 1] : 0.0;
-                            const int bits = cand ? ((const int*)(rec + lane * 4 + 2))[0] : 0;
-                            const unsigned long long hm = __ballot((bits & 1) != 0);
-                            if (!exact) {
-                                // every candidate the reference looks at (up to the first hit, else all of the group) must be
-                                // decided for good
-                                const unsigned long long unc = __ballot((bits & 2) != 0);
-                                const unsigned long long looked = hm ? (2ull << (__ffsll((long long)hm) - 1)) - 1 : (1ull << nt) - 1;
-                                if (unc & looked) { if (tid == 0) sh_redo = 1; stop = true; }
-                            }
-                            if (!stop) {
-                                if (hm) {
-                                    const int found = __ffsll((long long)hm) - 1;    // candidate the hop settles on
-                                    const long ncur = (grp ? nx1 : nx0) - max_offset + found;
-                                    if (tid == found) {
-                                        st->coarse_pos[n] = (double)((ncur - 1) * dec + 1);
-                                        if (ratio_mode) { hop_sig[2 * n] = ra; hop_sig[2 * n + 1] = rb; }
-                                        else st->coarse_snr[n] = ra;
-                                    }
-                                    cur = ncur; took1 = grp != 0; settled = true;
-                                } else if (!(grp == 0 && g1ok)) stop = true;   // :67 / both miss; else :65 try across the idle frame
-                            }
-                        }
+                        const HopTaken t = cs_hop_take(rec, hg, st, sh, hop_sig, dec, grp, nx0, nx1, g1ok, exact, ratio_mode, tid, n);
+                        if (t.verdict == HOP_STOP) stop = true;
+                        else if (t.verdict == HOP_SETTLED) { cur = t.ncur; took1 = grp != 0; settled = true; }
                         HOP_CYC(3);
                     }
                     if (stop) break;
@@ -1154,57 +1363,32 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
                     r[14] = acc + 100ull * (unsigned long long)n;
                 }
 #endif
+#undef HOP_CYC
                 __syncthreads();
-                // the reported SNRs of hops 1..n-1 (:25), one lane per hop.  Batch path: the value k_coarse_snr's table holds for the
-                // window (window_snr16: its FFT, DC term and sequential total), so that a hop reports the same bits whether it was
-                // looked up in the full table (small batches, depth 1) or decided on the walk's own spectra (calls in flight,
-                // throughput batches) -- "results are identical at every depth" (gsmcal.h) holds for the details too.  The direct
-                // DFT's powers differ from the FFT's in the last places (<= 4e-14 dB on the SNR): they decide, with their margin,
-                // and are not reported.  (A hop lies >= d0 - 5 windows in: past the head rows; its 16 samples end inside the stream.
-                // The reference geometry's forms only: in the general form the 16-point FFT's registers open a scratch frame.)
-                if (REFG && fast && a.mean_corr) {
-                    if (tid >= 1 && tid < n) st->coarse_snr[tid] = window_snr16(s, (long)((st->coarse_pos[tid] - 1.0) / (double)dec));
-                } else if (ratio_mode && tid >= 1 && tid < n)
-                    st->coarse_snr[tid] = 10.0 * log10(hop_sig[2 * tid] / hop_sig[2 * tid + 1]);
-                if (tid == 0) st->n_coarse = n;
+                cs_hop_report<REFG && fast>(s, st, hop_sig, dec, a.mean_corr != 0, ratio_mode, n, tid);
             }
         }
         __syncthreads();
-        const int redo = sh_redo;
+        const int redo = sh.redo;
         __syncthreads();
         if (!redo) break;                                  // block-uniform
         if (tid == 0) {                                    // start over with the exact replay
-            sh_exact = 1; sh_redo = 0; sh_hit = 0x7fffffff;
-            st->n_coarse = 0; st->coarse_hit_flag = 0; st->hit_avg_snr = INFINITY; st->mv_hit_idx = -1.0; st->mv_hit_snr = INFINITY;
+            sh.exact = 1; sh.redo = 0; sh.hit = CS_NONE;
+            cs_reset_answer(st);
         }
         n = 0;
         __syncthreads();
       }
       CS_STAMP(4);
     } else if (!bad) {
-        // ---- specific_fft_snr_fix_avg stand-alone ----
-        const long lo = a.t_lo, hi = a.t_hi;
-        if (hi >= lo) {
-            if (lo < 1) {
+        const CsSpecific r = cs_specific_range(a, fft_len);
+        if (r.hi >= r.lo) {
+            if (r.lo < 1) {
                 if (tid == 0) set_status(st, 3, GSMCAL_E_INDEX);
             } else {
-                // the reference's loop (specific_fft_snr_fix_avg.m:10-11) indexes window by window: a hit in a window that fits
-                // returns before a later window would run past the end of s; only a miss up to there is MATLAB's index error
-                const long hi_fit = hi + fft_len - 1 > len ? len - (fft_len - 1) : hi;
-                const long cnt = hi_fit >= lo ? hi_fit - lo + 1 : 0;
-                for (long i = tid; i < cnt; i += 256) snr_s[i] = FFT16 ? window_snr16(s, lo - 1 + i) : window_snr_generic(s, lo - 1 + i, fft_len, tw);
+                cs_specific_window<FFT16>(s, r, fft_len, tw, snr_s, tid);
                 __syncthreads();
-                if (tid == 0) {
-                    bool hit = false;
-                    for (long i = 0; i < cnt && !hit; ++i)
-                        if (snr_s[i] - a.avg_snr > th) {
-                            st->coarse_hit_flag = 1;
-                            st->mv_hit_idx = (double)(lo + i);
-                            st->mv_hit_snr = snr_s[i];
-                            hit = true;
-                        }
-                    if (!hit && hi_fit < hi) set_status(st, 3, GSMCAL_E_INDEX);
-                }
+                if (tid == 0) cs_specific_first_hit(a, r, th, snr_s, st);
             }
         }
     }
@@ -1214,12 +1398,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES,
         d_scan_accept(st, blockIdx.x, a.accept.snr_numhit, a.accept.positions, a.accept.pos_snr, a.accept.counts, a.P, tid);
     __syncthreads();
     CS_STAMP(5);
-    {
-        const uint4* src = (const uint4*)st;
-        uint4* dst = (uint4*)st_g;
-        for (int i = tid; i < (int)(sizeof(StreamState) / 16); i += 256) dst[i] = src[i];
-    }
+    cs_state_copy(st_g, st, tid);
     CS_STAMP(6);
+#undef CS_STAMP
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -455,7 +455,7 @@ def test_front_end_filter_and_decimation(g, fe, n, decim, name):
 
 # ---- limits -------------------------------------------------------------------------------------------------------------------------
 def coarse_scan_lds(cx, nwin, mv_len):
-    """host_plan.h coarse_scan_lds: the scan's own part (gsmcal_coarse_scan_lds_fixed: state copy, twiddles, hop buffers), then
+    """cs_carve().launch (kernels_detect.h): the scan's own part (gsmcal_coarse_scan_lds_fixed: state copy, twiddles, hop buffers), then
     nwin + mv_len + 128 SNRs"""
     return cx.lib.gsmcal_coarse_scan_lds_fixed() + (nwin + mv_len + 128) * 8
 
