@@ -880,6 +880,63 @@ int gsmcal_array_combine_batch(gsmcal_ctx* ctx, const double* x, long stride, in
 int gsmcal_array_combine_batch_dev(gsmcal_ctx* ctx, const double* d_x, long stride, int d, const int* rows, int G, const double* weights,
                                    int B, long out_len, double* d_out);
 
+/* ---- apply a calibration to any capture: raw bytes resampled and de-rotated ---------------------------------
+ * The project's own function: what the calibration chain measures on the GSM carrier (GSMCAL_T_TOTAL_SAMPLING_PPM, _CARRIER_PPM),
+ * this takes out of a capture of the same dongle at any centre frequency and sample rate.  raw: [d][2n] bytes, capture-major, I / Q
+ * interleaved (raw2iq.m:6); sample_rate > 0 and finite, Hz; params (host): [d][GSMCAL_APPLY_PARAMS] doubles, one row per capture
+ * {delay, slope_ppm, carrier_hz, phase, anchor, scale, dc_i, dc_q, gain, sin_phase} (GSMCAL_AP_*); out_len >= 1, out_stride >= out_len.
+ * With a_m, b_m the I and Q bytes of sample m, c = sqrt(1 - sin_phase^2) and h the interpolator of gsmcal_pair_align (GSMCAL_ALIGN_TAPS
+ * taps, the Blackman-windowed sinc), for n = 0 .. out_len-1, in fp64:
+ *   z[m] = (a_m - dc_i) + j ((b_m - dc_q)/gain - (a_m - dc_i) sin_phase)/c         (raw2iq's DC removal, then gsmcal_iq_correct's form)
+ *   x = (n + delay) + (slope_ppm 1e-6) (n - anchor),  base = floor(x),  mu = x - base   (every operation rounded on its own)
+ *   valid iff 0 <= base - 7 and base + 8 < n_samples
+ *   out[n] = scale exp(-j (phase + (2 pi carrier_hz / sample_rate) (n - anchor))) sum_{k=-7..8} h(k - mu) z[base + k]   where valid,
+ *   exactly 0 + 0j elsewhere.
+ * out: [d][out_stride] complex; the elements at and beyond out_len of a row are not touched.  info: [d][GSMCAL_APPLY_INFO_COLS]
+ * doubles {status, first_valid, end_valid, num_valid} (the GSMCAL_AI_* columns), 0 0 0 with no valid sample.  A row with a value
+ * that is not finite has status GSMCAL_S_ALIGN_SKIPPED and an all-zero output row: a dongle whose calibration failed (total ppm =
+ * Inf, an all-NaN row of gsmcal_apply_params) passes through a batch this way, and the call succeeds.
+ * GSMCAL_E_ARG, decided before anything is enqueued and with the outputs untouched: a NULL pointer; d < 1, n < 1, out_len < 1 or
+ * out_stride < out_len; sample_rate not finite or <= 0; in a row whose values are all finite |slope_ppm| > 1000, gain <= 0 or
+ * |sin_phase| >= 1; raw not 2-byte aligned in the resident form.  An output that overlaps raw is not supported.
+ * A capture's output row and info row depend on its bytes, its parameter row, n, sample_rate and out_len alone: they are the same
+ * bits alone, at any position of any batch, from call to call and between the two forms.  No float atomics; the call keeps no state
+ * between calls (the parameter rows are uploaded by every call).  The output rows are streams on one nominal time base, as
+ * gsmcal_array_covariance_batch and gsmcal_array_combine_batch take them.
+ * _resident: d_raw, d_out and d_info are device pointers (the outputs may be pinned host memory), params stays a host array; it
+ * only enqueues on the context's stream, behind whatever wrote d_raw there; the lanes and every answer about the calibrate / scan
+ * call before stay untouched. */
+#define GSMCAL_APPLY_PARAMS 10          /* one capture's parameter row of gsmcal_apply_calibration_batch */
+#define GSMCAL_APPLY_INFO_COLS 4        /* one row of its info table */
+#define GSMCAL_AP_DELAY 0               /* position of output sample `anchor` in the capture minus anchor, samples                */
+#define GSMCAL_AP_SLOPE_PPM 1           /* 1e6 * how much faster than the output index the position advances, |.| <= 1000          */
+#define GSMCAL_AP_CARRIER_HZ 2          /* carrier to take out, Hz of the OUTPUT time base                                         */
+#define GSMCAL_AP_PHASE 3               /* carrier phase to take out at output sample `anchor`, rad                                */
+#define GSMCAL_AP_ANCHOR 4              /* output index the drift and the carrier are counted from                                 */
+#define GSMCAL_AP_SCALE 5               /* real factor on the output                                                               */
+#define GSMCAL_AP_DC_I 6                /* DC of the I bytes (127.5: raw2iq's)                                                     */
+#define GSMCAL_AP_DC_Q 7                /* DC of the Q bytes                                                                       */
+#define GSMCAL_AP_GAIN 8                /* Q / I gain ratio to remove, > 0 (GSMCAL_Q_GAIN)                                         */
+#define GSMCAL_AP_SIN_PHASE 9           /* sine of the quadrature skew to remove, |.| < 1 (GSMCAL_Q_SIN_PHASE)                     */
+int gsmcal_apply_calibration_batch(gsmcal_ctx* ctx, const uint8_t* raw, int d, long n, double sample_rate, const double* params,
+                                   long out_len, long out_stride, double* out, double* info);
+int gsmcal_apply_calibration_batch_resident(gsmcal_ctx* ctx, const uint8_t* d_raw, int d, long n, double sample_rate,
+                                            const double* params, long out_len, long out_stride, double* d_out, double* d_info);
+
+/* One row of the calibration table -> the parameter row that undoes it on a capture tuned to tuned_freq Hz (pure host arithmetic;
+ * no context needed).  With e = 1e-6 TOTAL_SAMPLING_PPM and f_off = 1e-6 TOTAL_CARRIER_PPM tuned_freq:
+ *   slope_ppm = TOTAL_SAMPLING_PPM,  anchor = 0,  carrier_hz = f_off (1 + e),  delay, phase and scale as given.
+ * Why: the dongle samples at ideal time k/(1 + e) (in nominal sample periods) and its carrier error turns its sample k by
+ * 2 pi f_off k / sample_rate; output sample n of the nominal time base therefore sits at dongle index n (1 + e), and the angle to
+ * take out there is 2 pi f_off n (1 + e) / sample_rate (the reasoning of gsmcal_pair_align_params).
+ * iq_row (may be NULL): a GSMCAL_IQ_COLS row of gsmcal_iq_imbalance_batch taken on the capture to correct: dc_i, dc_q from
+ * GSMCAL_Q_DC_I / _DC_Q, gain and sin_phase from their columns, 1 and 0 at GSMCAL_IQ_FLAT / GSMCAL_IQ_SHORT.  Without it dc_i =
+ * dc_q = 127.5, gain = 1, sin_phase = 0.  A table row whose GSMCAL_T_STATUS is not 0, or whose totals are not finite, gives an
+ * all-NaN row (gsmcal_apply_calibration_batch then skips the capture) and the return value GSMCAL_S_ALIGN_SKIPPED; otherwise 0.
+ * GSMCAL_E_ARG: a NULL table_row or params_row. */
+int gsmcal_apply_params(const double* table_row, double tuned_freq, const double* iq_row, double delay, double phase, double scale,
+                        double* params_row);
+
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,
  * multi_rtl_sdr_gsm_FCCH_scanner.m:60-65,163), so ranks shard them block-contiguously and exchange only the result

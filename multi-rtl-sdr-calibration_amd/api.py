@@ -34,7 +34,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, PAIR_COLS, MAX_PAIR_BURSTS, ALIGN_PARAMS, ALIGN_INFO_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, PAIR_COLS, MAX_PAIR_BURSTS, ALIGN_PARAMS, ALIGN_INFO_COLS, APPLY_PARAMS, APPLY_INFO_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -1354,6 +1354,86 @@ def coherent_combine(r_correct, r_len, pos_info_raw, oversampling_ratio, sch_tab
         raise ValueError('weights: None or "max_ratio"')
     out.update({"pair_table": table, "params": params, "members": np.array([int(ref)] + ms)})
     return out
+
+
+APPLY_PARAM_FIELDS = ("delay", "slope_ppm", "carrier_hz", "phase", "anchor", "scale", "dc_i", "dc_q", "gain", "sin_phase")     # one capture's row of apply_calibration
+
+
+def apply_rows(info):
+    """(D, APPLY_INFO_COLS) info table of apply_calibration[_resident] -> dict of the ALIGN_INFO_FIELDS as (D,) columns: status 0,
+    or 17 = a value of the capture's parameter row is not finite (its output row is all zero); [first_valid, end_valid) the output
+    samples every tap of which lies inside the capture."""
+    t = np.asarray(info, dtype=np.float64).reshape(-1, APPLY_INFO_COLS)
+    return {k: t[:, i] for i, k in enumerate(ALIGN_INFO_FIELDS)}
+
+
+def apply_params(table, tuned_freq, iq_table=None, delay=0.0, phase=0.0, scale=1.0):
+    """Rows of a calibration table (calibrate_batch) -> (D, APPLY_PARAMS) parameter rows {delay, slope_ppm, carrier_hz, phase, anchor,
+    scale, dc_i, dc_q, gain, sin_phase} that undo each dongle's sampling clock error and carrier error on a capture tuned to
+    tuned_freq Hz (gsmcal_apply_params; pure host arithmetic, no context).  With e = 1e-6 total_sampling_ppm and f_off = 1e-6
+    total_carrier_ppm tuned_freq:
+        slope_ppm = total_sampling_ppm,  anchor = 0,  carrier_hz = f_off (1 + e);  delay, phase and scale as given.
+    Why: the dongle samples at ideal time k / (1 + e) and its carrier error turns its sample k by 2 pi f_off k / fs, so output sample
+    n of the nominal time base sits at dongle index n (1 + e) and the angle to take out there is 2 pi f_off n (1 + e) / fs.
+    iq_table: the (D, IQ_COLS) table of iq_imbalance_batch ON THE CAPTURE TO CORRECT (DC and imbalance change with the tuning): DC,
+    gain and sin_phase come from it (gain 1, sin_phase 0 where its status is not 0); without it DC = 127.5, 127.5 (raw2iq's) and no
+    I/Q correction.  tuned_freq, delay, phase and scale: scalars or one value per dongle.  A row whose status is not 0, or whose
+    totals are not finite, gives an all-NaN row; apply_calibration then skips that capture (status 17, zeros)."""
+    lib = _lib.load()
+    tab = np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, TABLE_COLS))
+    d = len(tab)
+    iq = None if iq_table is None else np.ascontiguousarray(np.asarray(iq_table, dtype=np.float64).reshape(-1, IQ_COLS))
+    if iq is not None and len(iq) != d:
+        raise ValueError("iq_table must have one row per row of table")
+    per = [np.broadcast_to(np.asarray(v, dtype=np.float64).ravel(), (d,)) for v in (tuned_freq, delay, phase, scale)]
+    out = np.empty((d, APPLY_PARAMS))
+    for i in range(d):
+        rc = lib.gsmcal_apply_params(_dp(tab[i]), float(per[0][i]), _dp(iq[i]) if iq is not None else None, float(per[1][i]),
+                                     float(per[2][i]), float(per[3][i]), _dp(out[i]))
+        if rc < 0:
+            raise GsmcalError(f"apply_params failed with {rc}")
+    return out
+
+
+def _apply_params_in(params, d):
+    pr = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1, APPLY_PARAMS))
+    if len(pr) != d:
+        raise ValueError("one parameter row per capture")
+    return pr
+
+
+def apply_calibration(raw, params, sample_rate, out_len=None, ctx=None):
+    """The project's own function (include/gsmcal.h): raw (D, 2N) uint8 captures of calibrated dongles at any
+    centre frequency and sample_rate -> (out, info): out (D, out_len) complex (default out_len = N), every capture with its DC and
+    I/Q imbalance removed, resampled at x(n) = (n + delay) + 1e-6 slope_ppm (n - anchor) by pair_align's 16-tap interpolator, turned
+    by exp(-j (phase + 2 pi carrier_hz (n - anchor) / sample_rate)) and scaled; samples a tap of which would fall outside the capture
+    are exactly 0.  params: (D, APPLY_PARAMS) rows (apply_params).  info: apply_rows of the (D, APPLY_INFO_COLS) table.  The rows
+    are streams on one nominal time base: array_covariance and array_combine take them as they are."""
+    ctx = ctx or default_context()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    if raw.ndim != 2 or raw.shape[1] % 2:
+        raise ValueError("raw must be (D, 2N) bytes")
+    d, two_n = raw.shape
+    n = two_n // 2
+    out_len = n if out_len is None else int(out_len)
+    pr = _apply_params_in(params, d)
+    out = np.empty((d, max(out_len, 0)), dtype=np.complex128)
+    info = np.empty((d, APPLY_INFO_COLS))
+    ctx.check(ctx.lib.gsmcal_apply_calibration_batch(ctx.h, raw.ctypes.data_as(_lib.c_u8_p), d, n, float(sample_rate), _dp(pr), out_len,
+                                                     out_len, _dp(out.view(np.float64)), _dp(info)), "apply_calibration_batch")
+    return out, apply_rows(info)
+
+
+def apply_calibration_resident(d_raw, d, n, params, sample_rate, out_len, out_stride, d_out, d_info, ctx=None):
+    """Device-pointer form of apply_calibration: only enqueues on the context's stream (ctx.sync() before reading), behind whatever
+    wrote d_raw there.  d_raw: [d][2n] bytes, 2-byte aligned; params: host rows; d_out: [d][out_stride] complex, out_stride >=
+    out_len, the tail of every row is not touched; d_info: [d][APPLY_INFO_COLS] doubles; the outputs in device or pinned host memory,
+    not overlapping d_raw."""
+    ctx = ctx or default_context()
+    pr = _apply_params_in(params, int(d))
+    ctx.check(ctx.lib.gsmcal_apply_calibration_batch_resident(ctx.h, C.c_void_p(d_raw), int(d), int(n), float(sample_rate), _dp(pr),
+                                                              int(out_len), int(out_stride), C.c_void_p(d_out), C.c_void_p(d_info)),
+              "apply_calibration_batch_resident")
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

@@ -1345,6 +1345,111 @@ int gsmcal_array_combine_batch(gsmcal_ctx* c, const double* x, long stride, int 
     return stage_down(c, io);
 }
 
+// ---- apply_calibration: raw bytes resampled and de-rotated by a calibration -------------------------------------------
+// k_apply_calibration (one workgroup per tile of PA_TILE output samples and capture) + k_apply_info (one lane per capture: the valid
+// interval).  The parameter rows change from call to call in the workload: every call turns them into the kernels' rows in the
+// context's staging vector and uploads those on the stream -- no cache, no state a later call could see.
+static_assert(gsmcal_ap::AP_PARAMS == GSMCAL_APPLY_PARAMS && gsmcal_ap::AP_SKIPPED == GSMCAL_S_ALIGN_SKIPPED && gsmcal_ap::AP_SIN_PHASE == GSMCAL_AP_SIN_PHASE &&
+              gsmcal_ap::AP_DELAY == GSMCAL_AP_DELAY && gsmcal_ap::AP_SCALE == GSMCAL_AP_SCALE && gsmcal_ap::AP_GAIN == GSMCAL_AP_GAIN &&
+              gsmcal_ap::T_TOTAL_SAMPLING_PPM == GSMCAL_T_TOTAL_SAMPLING_PPM && gsmcal_ap::T_TOTAL_CARRIER_PPM == GSMCAL_T_TOTAL_CARRIER_PPM &&
+              gsmcal_ap::T_STATUS == GSMCAL_T_STATUS && gsmcal_ap::Q_DC_I == GSMCAL_Q_DC_I && gsmcal_ap::Q_DC_Q == GSMCAL_Q_DC_Q &&
+              gsmcal_ap::Q_GAIN == GSMCAL_Q_GAIN && gsmcal_ap::Q_SIN_PHASE == GSMCAL_Q_SIN_PHASE && gsmcal_ap::Q_STATUS == GSMCAL_Q_STATUS &&
+              gsmcal_ap::IQ_OK == GSMCAL_IQ_OK && GSMCAL_APPLY_INFO_COLS == GSMCAL_ALIGN_INFO_COLS, "apply_params.h and include/gsmcal.h disagree");
+
+static int apply_args(gsmcal_ctx* c, const void* raw, int d, long n, double fs, const double* params, long out_len, long out_stride,
+                      const void* out, const void* info) {
+    if (!c) return GSMCAL_E_ARG;
+    const char* why = nullptr;
+    if (!raw || !params || !out || !info) why = "apply_calibration: no pointer may be NULL";
+    else if (d < 1 || n < 1) why = "apply_calibration: d and n must be at least 1";
+    else if (out_len < 1 || out_stride < out_len) why = "apply_calibration: out_len must be at least 1 and out_stride at least out_len";
+    else if (!std::isfinite(fs) || !(fs > 0.0)) why = "apply_calibration: sample_rate must be finite and > 0";
+    for (int i = 0; i < d && !why; ++i) {
+        const double* p = params + (size_t)i * GSMCAL_APPLY_PARAMS;
+        bool fin = true;
+        for (int k = 0; k < GSMCAL_APPLY_PARAMS; ++k) fin = fin && std::isfinite(p[k]);
+        if (!fin) continue;                                        // (the capture is skipped: GSMCAL_S_ALIGN_SKIPPED in its info row)
+        if (fabs(p[GSMCAL_AP_SLOPE_PPM]) > 1000.0) why = "apply_calibration: |slope_ppm| must be at most 1000";
+        else if (!(p[GSMCAL_AP_GAIN] > 0.0)) why = "apply_calibration: every gain must be > 0";
+        else if (!(fabs(p[GSMCAL_AP_SIN_PHASE]) < 1.0)) why = "apply_calibration: every |sin_phase| must be below 1";
+    }
+    if (why) { c->err = why; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+// the parameter rows -> the kernels' rows, in the context's staging vector
+static void apply_rows(gsmcal_ctx* c, int d, double fs, const double* params) {
+    c->ap_stage.resize((size_t)d);
+    for (int i = 0; i < d; ++i) {
+        const double* p = params + (size_t)i * GSMCAL_APPLY_PARAMS;
+        ApRow& a = c->ap_stage[(size_t)i];
+        bool fin = true;
+        for (int k = 0; k < GSMCAL_APPLY_PARAMS; ++k) fin = fin && std::isfinite(p[k]);
+        memset(&a, 0, sizeof(a));
+        if (!fin) continue;                                        // run = 0: nothing else of the row is read
+        const double sp = p[GSMCAL_AP_SIN_PHASE], cph = sqrt(1.0 - sp * sp);
+        a.delay = p[GSMCAL_AP_DELAY];
+        a.slope = p[GSMCAL_AP_SLOPE_PPM] * 1e-6;
+        a.w = 2.0 * PI_D * p[GSMCAL_AP_CARRIER_HZ] / fs;
+        a.phase = p[GSMCAL_AP_PHASE];
+        a.anchor = p[GSMCAL_AP_ANCHOR];
+        a.scale = p[GSMCAL_AP_SCALE];
+        a.dc_i = p[GSMCAL_AP_DC_I];
+        a.dc_q = p[GSMCAL_AP_DC_Q];
+        a.q_gain = 1.0 / (p[GSMCAL_AP_GAIN] * cph);
+        a.q_skew = sp / cph;
+        a.run = std::isfinite(a.w) && std::isfinite(a.q_gain) && std::isfinite(a.q_skew) ? 1.0 : 0.0;   // (a carrier_hz / sample_rate beyond fp64)
+    }
+}
+
+static int apply_enqueue(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n, double fs, const double* params, long out_len, long out_stride,
+                         double* d_out, double* d_info) {
+    c->cur = &c->lanes[0];                              // the context's stream; the lane's buffers are not touched
+    apply_rows(c, d, fs, params);
+    const size_t bytes = (size_t)d * sizeof(ApRow);
+    RET_IF(ensure(c, c->ap_rows, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->ap_rows.p, c->ap_stage.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    const ApRow* rows = (const ApRow*)c->ap_rows.p;
+    const long tiles = (out_len + PA_TILE - 1) / PA_TILE, per_launch = 1L << 30;                   // (grid.x holds 2^31 - 1)
+    for_capture_chunks(d, [&](long lo, int S) {
+        for (long t = 0; t < tiles; t += per_launch)
+            LAUNCH(c, k_apply_calibration, dim3((unsigned)std::min(per_launch, tiles - t), S), dim3(PA_TILE), 0, d_raw + (size_t)lo * 2 * n, n,
+                   rows + lo, out_len, out_stride, t * PA_TILE, (cplx*)d_out + (size_t)lo * out_stride);
+    });
+    LAUNCH(c, k_apply_info, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, rows, d, n, out_len, d_info);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_apply_calibration_batch_resident(gsmcal_ctx* c, const uint8_t* d_raw, int d, long n, double fs, const double* params, long out_len,
+                                            long out_stride, double* d_out, double* d_info) {
+    RET_IF(apply_args(c, d_raw, d, n, fs, params, out_len, out_stride, d_out, d_info));
+    if ((uintptr_t)d_raw & 1) { c->err = "apply_calibration: d_raw must be 2-byte aligned"; return GSMCAL_E_ARG; }
+    ENTER(c);
+    return apply_enqueue(c, d_raw, d, n, fs, params, out_len, out_stride, d_out, d_info);
+}
+
+int gsmcal_apply_calibration_batch(gsmcal_ctx* c, const uint8_t* raw, int d, long n, double fs, const double* params, long out_len,
+                                   long out_stride, double* out, double* info) {
+    RET_IF(apply_args(c, raw, d, n, fs, params, out_len, out_stride, out, info));
+    ENTER(c);
+    // the device rows are packed (stride out_len); a two-dimensional copy leaves the tail of every host row as it was
+    const size_t row = (size_t)out_len * sizeof(cplx);
+    const Stage io[] = {STAGE(stage_raw, (size_t)2 * n * d, raw, nullptr, 0),
+                        STAGE(ap_out, (size_t)d * row, nullptr, nullptr, 0),
+                        STAGE(ap_info, (size_t)d * GSMCAL_APPLY_INFO_COLS * sizeof(double), nullptr, info, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(apply_enqueue(c, (const uint8_t*)c->stage_raw.p, d, n, fs, params, out_len, out_len, (double*)c->ap_out.p, (double*)c->ap_info.p));
+    HIPCHK(c, hipMemcpy2DAsync(out, (size_t)out_stride * sizeof(cplx), c->ap_out.p, row, row, (size_t)d, hipMemcpyDeviceToHost, c->stream));
+    return stage_down(c, io);
+}
+
+int gsmcal_apply_params(const double* table_row, double tuned_freq, const double* iq_row, double delay, double phase, double scale,
+                        double* params_row) {
+    if (!table_row || !params_row) return GSMCAL_E_ARG;
+    return gsmcal_ap::apply_params(table_row, tuned_freq, iq_row, delay, phase, scale, params_row);
+}
+
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out) {
     if (!ppm_in || !ppm_out || n < 1) return GSMCAL_E_ARG;

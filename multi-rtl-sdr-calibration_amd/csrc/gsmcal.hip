@@ -37,7 +37,9 @@
 #include "kernels_pair.h"
 #include "kernels_align.h"
 #include "kernels_array.h"
+#include "kernels_apply.h"
 #include "combine_weights.h"
+#include "apply_params.h"
 #include "state.h"
 
 #define GSMCAL_VERSION "gsmcal-mi355x 0.1 (gfx950)"

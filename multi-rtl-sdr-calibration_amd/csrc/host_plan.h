@@ -82,12 +82,15 @@ struct CtxBufs {
     // optimal combining (gsmcal_array_covariance_batch*, gsmcal_array_combine_batch*): the row indices, the window table {start, len,
     // first partial}, the chunk partials, the weights, and the host wrappers' staging of x, the matrices and the beams
     DevBuf ac_rows, ac_win, ac_part, ac_w, ac_x, ac_cov, ac_out;
+    // apply_calibration (gsmcal_apply_calibration_batch*): the kernels' rows of this call, and the host wrapper's staging of the
+    // output rows and the info table (its bytes go through stage_raw)
+    DevBuf ap_rows, ap_out, ap_info;
     ALL_BUFS(CtxBufs, &coef, &ts, &cf, &table, &snrhit, &arr_in, &arr_out, &posinfo, &rlen, &misc, &tw, &csum_head, &tw_sch, &stage_raw,
              &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &bc_ts, &bc_corr, &bc_flag, &bc_out,
              &bc_corr_out, &bc_r, &bc_rlen, &sd_part, &sd_out, &sd_soft, &sd_u, &bd_part, &bd_tsc, &bd_out, &bd_oct, &bd_soft, &sb_taps, &sb_idx,
              &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r, &iq_part, &iq_in, &iq_par, &pc_pairs, &pc_part,
              &pc_out, &pc_corr, &pa_members, &pa_params, &pa_aligned, &pa_combined, &pa_info, &ac_rows, &ac_win, &ac_part, &ac_w, &ac_x,
-             &ac_cov, &ac_out)
+             &ac_cov, &ac_out, &ap_rows, &ap_out, &ap_info)
 };
 
 struct gsmcal_ctx : CtxBufs {
@@ -201,6 +204,7 @@ struct gsmcal_ctx : CtxBufs {
     std::vector<double> h_bp_coef, h_fd_cf, h_bc_ts, h_sb_coef, h_sb_w, h_sb_rows, h_iq_par, h_pa_params, h_ac_w;
     std::vector<int> h_sb_idx, h_bd_tsc, h_pc_pairs, h_pa_members, h_ac_rows;
     std::vector<long> h_ac_win;
+    std::vector<ApRow> ap_stage;             // apply_calibration: the rows of the call being enqueued (written and uploaded by every call; no cache)
     int fd_tw_n = 0;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream

@@ -221,3 +221,36 @@ def check_front_end(ring, slot, d, n, ctx=None):
     finally:
         ctx.lib.gsmcal_dev_free(ctx.h, d_out)
     return api.iq_rows(out)
+
+
+def apply_calibration_slot(ring, slot, d, n, params, sample_rate, out_len=None, ctx=None):
+    """api.apply_calibration on a ring slot that has been submitted: the slot's d captures of n samples each (dongle-major bytes, as
+    capture_all fills them) corrected by the (d, APPLY_PARAMS) rows of api.apply_params on the device copy -- resampled onto the
+    nominal time base, the carrier error, DC and I/Q imbalance taken out -- and returned as (out, info): out (d, out_len) complex
+    (default out_len = n), info api.apply_rows.  The slot is acquired and released here; the call returns when the rows are on
+    the host."""
+    from . import api
+    ctx = ctx or ring.ctx
+    d, n = int(d), int(n)
+    if 2 * n * d > ring.bytes:
+        raise ValueError("the slot holds fewer than d captures of n samples")
+    out_len = n if out_len is None else int(out_len)
+    out = np.empty((d, max(out_len, 0)), dtype=np.complex128)
+    info = np.empty((d, api.APPLY_INFO_COLS))
+    d_out, d_info = C.c_void_p(), C.c_void_p()
+    ctx.check(ctx.lib.gsmcal_dev_alloc(ctx.h, max(out.nbytes, 16), C.byref(d_out)), "gsmcal_dev_alloc")
+    try:
+        ctx.check(ctx.lib.gsmcal_dev_alloc(ctx.h, info.nbytes, C.byref(d_info)), "gsmcal_dev_alloc")
+        try:
+            d_raw = ring.acquire(slot)
+            try:
+                api.apply_calibration_resident(d_raw, d, n, params, sample_rate, out_len, out_len, d_out.value, d_info.value, ctx=ctx)
+                ctx.check(ctx.lib.gsmcal_memcpy_d2h(ctx.h, out.ctypes.data_as(C.c_void_p), d_out, out.nbytes), "gsmcal_memcpy_d2h")
+                ctx.check(ctx.lib.gsmcal_memcpy_d2h(ctx.h, info.ctypes.data_as(C.c_void_p), d_info, info.nbytes), "gsmcal_memcpy_d2h")
+            finally:
+                ring.release(slot)
+        finally:
+            ctx.lib.gsmcal_dev_free(ctx.h, d_info)
+    finally:
+        ctx.lib.gsmcal_dev_free(ctx.h, d_out)
+    return out, api.apply_rows(info)
