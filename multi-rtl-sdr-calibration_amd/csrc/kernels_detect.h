@@ -15,6 +15,7 @@
 #pragma once
 #include "state.h"
 #include "kernels_frontend.h"
+#include "fc_layout.h"
 
 // ---- per-window SNR (move_fft_snr_runtime_avg.m:18-27) ------------------------------------------
 // 16-point FFT, radix-2 decimation in frequency, in place and fully unrolled in registers (fp64); the trivial
@@ -1555,7 +1556,6 @@ __global__ void k_make_twiddles(cplx* tw, int n) {
 }
 
 #define FFT_THREADS 512
-#define FC_NB 8        /* k_fine_cert: candidate bins around the tone */
 template <int MODE>
 __global__ void __launch_bounds__(FFT_THREADS) k_fft_burst(const StreamState* __restrict__ sts,
                                                            const cplx* __restrict__ win, long win_stream_stride,
@@ -1633,7 +1633,7 @@ __global__ void __launch_bounds__(FFT_THREADS) k_fft_burst(const StreamState* __
 // GSMCAL_CERT=0 opens every chunk of every window; GSMCAL_PRESCREEN=0 runs k_fine_search, the plain all-bin
 // fp64 sweep, as the cross-check of the whole scheme.
 // ------------------------------------------------------------------------------------------------
-#define FS_CHUNK 64
+// (FS_CHUNK = 64 and FC_NB: fc_layout.h)
 #define FS_ERR_SCALE_CHUNK 0.0001220703125   /* 2^-13 */
 
 // X_k at one shift by a direct fp64 DFT over the nfft samples xw[0..nfft), executed by one wave: lane l sums
@@ -2037,17 +2037,7 @@ __device__ __forceinline__ float fc_group8_sum(float v) {     // sum over the 8 
     return v;
 }
 
-__host__ __device__ constexpr int fc_gcd64(int n) { int b = 64; while (n % b) b >>= 1; return b; }
-// threads of k_fine_cert: 8 per chunk, at least 256.  (320 would save the nearly empty third round of the level-1 phase --
-// 69 blocks handed out 32 at a time -- but five-wave workgroups no longer sit three to a CU: measured 77 us against 59.)
-__host__ __device__ constexpr int fc_threads(int nshift) {
-    return ((nshift - 1) / FS_CHUNK * FC_NB + 63) / 64 * 64 < 256 ? 256 : ((nshift - 1) / FS_CHUNK * FC_NB + 63) / 64 * 64;
-}
-// One element of padding after every 128: lane groups that work 64 shifts apart (the chunks of the slide phase) would
-// otherwise all hit the same LDS banks (8-way; the SQ counters showed 4 bank-conflict cycles per LDS instruction in this
-// kernel); this leaves them 2-way.  (Padding every 64 would clear them entirely but costs the third workgroup per CU: the
-// kernel sits 100 bytes under the 53 760-byte line.)
-#define FC_XP(p) ((p) + ((p) >> 7))
+// (threads, FC_XP padding: fc_layout.h)
 // k_fine_cert building its window from the raw bytes itself (raw == nullptr: read it from `win`)
 struct FusedGather {
     const uint8_t* raw; long raw_stride;
@@ -2062,45 +2052,8 @@ __host__ inline size_t fc_stage_bytes(int per, int ntaps) {
     return (size_t)(span8 + span8 / 4 + 1) * sizeof(cplx) + (size_t)fir_taps_padded(ntaps) * sizeof(double);
 }
 
-// k_fine_cert's geometry and its dynamic LDS, written down once: the kernel's pointers, the size of the launch and run_fine()'s
-// fit test of a staging pass all come from here.  Byte offsets from the base of the dynamic LDS:
-//   xs    the window, FC_XP(wlen) samples
-//   reg1  Sp[FC_NB][nM], the S partials (level 1 -> level 2); from the E/C scans on Et[t], t = 0..nstep
-//   reg2  tw1[FC_NB][ld1] = W^(k_j b) and tw2[nA][FC_NB] = W^(k_j B a) (twiddles -> level 2); from the slides on sumS[t] (the sum
-//         over S of P(t,k), later s(t)) and Cs[t] (C(t) = sum_{q<t} |d_q|, the slack of the recurrence), FC_XP(nstep + 2) floats
-//         each, and behind them the 2 x 8 scan partials sh_scan / sh_scan2 (block scan, certificate)
-// Before the tone estimate regions 1 and 2 are free: the bin choice keeps its 148-point spectrum at reg1, and a window built from
-// the raw bytes stages its passes there (`stage` bytes: what is left of the launch behind the window, less 16).
-struct FcCarve {
-    int nstep, wlen, B, nA, nM, nchunk, ld1;
-    size_t xs, reg1, reg2;
-    size_t Sp, Et, tw1, tw2, sumS, Cs, sh_scan, sh_scan2;
-    size_t total, launch, stage;     // bytes used | dynamic LDS of the launch (whole 16 bytes) | room of a staging pass
-};
-__host__ __device__ constexpr FcCarve fc_carve(int nshift, int nfft) {
-    FcCarve c{};
-    c.nstep = nshift - 1; c.wlen = c.nstep + nfft;
-    c.B = fc_gcd64(nfft); c.nA = nfft / c.B; c.nM = c.wlen / c.B; c.nchunk = c.nstep / FS_CHUNK;
-    c.ld1 = c.B + 2;                                      // plane stride of tw1: spreads the 8 bins over the banks
-    const int xp = FC_XP(c.nstep + 2);
-    const size_t r1 = (size_t)FC_NB * c.nM * sizeof(cplx), e1 = (size_t)(c.nstep + 2) * sizeof(double);
-    const size_t r2 = (size_t)FC_NB * (c.B + 2 + nfft / c.B) * sizeof(cplx), e2 = (size_t)2 * (size_t)(xp + 1) * sizeof(float) + 16 * sizeof(double);
-    c.xs = 0;
-    c.reg1 = (size_t)FC_XP(c.wlen) * sizeof(cplx);
-    c.reg2 = c.reg1 + (r1 > e1 ? r1 : e1);
-    c.Sp = c.Et = c.reg1;
-    c.tw1 = c.reg2;
-    c.tw2 = c.tw1 + (size_t)(FC_NB * c.ld1) * sizeof(cplx);
-    c.sumS = c.reg2;
-    c.Cs = c.sumS + (size_t)xp * sizeof(float);
-    c.sh_scan = c.Cs + (size_t)(xp + (xp & 1)) * sizeof(float);
-    c.sh_scan2 = c.sh_scan + 8 * sizeof(double);
-    c.total = c.reg2 + (r2 > e2 ? r2 : e2);
-    c.launch = (c.total + 15) & ~(size_t)15;
-    c.stage = c.launch - c.reg1 - 16;
-    return c;
-}
-static_assert(fc_carve(1025, 1184).total == 53520, "reference geometry: with the 144 bytes of static LDS, 100 bytes under the 53 760-byte line (three workgroups per CU)");
+// k_fine_cert's geometry, its dynamic LDS (FcCarve, fc_carve()) and its lane maps: fc_layout.h
+static_assert(sizeof(cplx) == FC_CPLX_BYTES, "fc_carve() counts samples of 16 bytes");
 // a pointer into the carve (every phase forms its pointers from the one base)
 template <typename T>
 __device__ __forceinline__ T* fc_at(size_t off) {
@@ -2355,55 +2308,70 @@ __device__ __forceinline__ double fc_slack_term(const cplx& a1, const cplx& b1) 
     return (double)(__fsqrt_rn((float)(dr * dr + di * di)) * 1.00000095367431640625f);
 }
 
-// Role-split form: this wave alone forms E(t) (we) or C(t), t = 0..nstep.
-// a contiguous range of shifts per lane, an inclusive wave scan of the lane totals, a second pass with the running values
-template <int OV>
-__device__ __forceinline__ void fc_scan_role(const FcCarve& cv, const FcThread& th, int nfft, bool we) {
+// A double moved between lanes by DPP, one 32-bit half at a time (vector ALU: no LDS instruction, unlike __shfl_up's
+// ds_bpermute).  Lanes that the pattern gives no source, and rows outside ROW_MASK, read 0.0.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double fc_dpp_f64(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, ROW_MASK == 0xF);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, ROW_MASK == 0xF);
+    return __hiloint2double(hi, lo);
+}
+// inclusive prefix sum over the 64 lanes of a wave (all of them active): inside each row of 16, then across the rows
+__device__ __forceinline__ double fc_wave_scan(double v) {
+    v += fc_dpp_f64<0x111, 0xF>(v);               // row_shr:1
+    v += fc_dpp_f64<0x112, 0xF>(v);               // row_shr:2
+    v += fc_dpp_f64<0x114, 0xF>(v);               // row_shr:4
+    v += fc_dpp_f64<0x118, 0xF>(v);               // row_shr:8
+    v += fc_dpp_f64<0x142, 0xA>(v);               // row_bcast:15 -> rows 1 and 3: + the row in front
+    v += fc_dpp_f64<0x143, 0xC>(v);               // row_bcast:31 -> rows 2 and 3: + the first half
+    return v;
+}
+
+// Role-split form: this wave alone forms E(t) (WE) or C(t), t = 0..nstep.
+// In round u lane l takes shift l + 64 u (fc_scan_shift): the two reads and the store of a round touch consecutive slots across
+// the wave, so no two lanes of a lane group meet on a bank.  (A contiguous range of shifts per lane -- the form before -- needs one
+// wave scan instead of one per round, but its lanes sit 256 bytes apart: reads up to 6-way, Et stores 16-way, Cs stores 4-way.)  The prefix sums
+// run across the lanes, one DPP scan per round; the rounds' totals are carried in order.
+// (The role is a template argument so that each is one straight run of code: the reads of all rounds can go out ahead of the scans.)
+// The E wave writes E(t) - E(0): the start window's energy E(0) -- 19 more LDS round trips and a wave reduction -- is formed by the
+// C wave behind its scan (it has the shorter terms and reaches the join first) and left in *e0; the certificate adds it as it reads Et.
+template <int OV, bool WE>
+__device__ __forceinline__ void fc_scan_role(const FcCarve& cv, const FcThread& th, int nfft, double* e0) {
     const int lane = th.lane, nstep = cv.nstep;
     cplx* xs = fc_at<cplx>(cv.xs);
     double* Et = fc_at<double>(cv.Et);
     float* Cs = fc_at<float>(cv.Cs);
-    const int per = OV > 0 ? 2 * OV : (nstep + 63) >> 6;
-    const int i0 = lane * per < nstep ? lane * per : nstep, i1 = i0 + per < nstep ? i0 + per : nstep;
-    auto term = [&](int q) -> double {
+    double run = 0.0;                             // the value at the round's first shift, the same in every lane
+    auto term = [&](int u) -> double {            // the round's step in this lane (0 past the last shift)
+        const int q = fc_scan_shift(lane, u);
+        if (OV == 0 && q >= nstep) return 0.0;    // (nstep = 64 * rounds in the reference geometry: every round is whole)
         const cplx a1 = xs[FC_XP(q + nfft)], b1 = xs[FC_XP(q)];
-        if (we) return fc_energy_term(a1, b1);
-        return fc_slack_term(a1, b1);
+        return WE ? fc_energy_term(a1, b1) : fc_slack_term(a1, b1);
     };
-    double run = 0.0;
-    if (we) {                                     // E(0), in every lane
-        for (int i = lane; i < nfft; i += 64) { const cplx v = xs[FC_XP(i)]; run += v.x * v.x + v.y * v.y; }
-        for (int off = 32; off > 0; off >>= 1) run += __shfl_down(run, off, 64);
-        run = __shfl(run, 0, 64);
-    }
-    double g[OV > 0 ? 2 * OV : 1];                // reference geometry: the range's terms stay in registers for the second pass
-    double loc = 0.0;
+    auto scan = [&](int u, double g) {            // (outside any divergent branch: the DPP moves need every lane)
+        const int q = fc_scan_shift(lane, u);
+        const double inc = fc_wave_scan(g);
+        const double at = run + fc_dpp_f64<0x138, 0xF>(inc);     // wave_shr:1: the sum of the lanes in front
+        if (OV > 0 || q < nstep) { if (WE) Et[q] = at; else Cs[FC_XP(q)] = (float)at; }
+        run += __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(inc), 63), __builtin_amdgcn_readlane(__double2loint(inc), 63));
+    };
     if (OV > 0) {
+        double g[OV > 0 ? 2 * OV : 1];            // all reads first: the scans' stores would otherwise hold back the next round's reads
 #pragma unroll
-        for (int u = 0; u < 2 * OV; ++u) { g[u] = term(i0 + u); loc += g[u]; }   // (nstep = 64 * per: every range is whole)
-    } else {
-        for (int q = i0; q < i1; ++q) loc += term(q);
-    }
-    double inc = loc;
-    for (int off = 1; off < 64; off <<= 1) {
-        const double o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    const double exc = __shfl_up(inc, 1, 64);
-    if (lane > 0) run += exc;
-    if (OV > 0) {
+        for (int u = 0; u < 2 * OV; ++u) g[u] = term(u);
 #pragma unroll
-        for (int u = 0; u < 2 * OV; ++u) {
-            if (we) Et[i0 + u] = run; else Cs[FC_XP(i0 + u)] = (float)run;
-            run += g[u];
-        }
+        for (int u = 0; u < 2 * OV; ++u) scan(u, g[u]);
     } else {
-        for (int q = i0; q < i1; ++q) {
-            if (we) Et[q] = run; else Cs[FC_XP(q)] = (float)run;
-            run += term(q);
-        }
+        const int rounds = fc_scan_rounds(nstep);
+        for (int u = 0; u < rounds; ++u) scan(u, term(u));
     }
-    if (i1 == nstep && i0 < nstep) { if (we) Et[nstep] = run; else Cs[FC_XP(nstep)] = (float)run; }
+    if (lane == 0) { if (WE) Et[nstep] = run; else Cs[FC_XP(nstep)] = (float)run; }
+    if (!WE) {                                    // E(0)
+        double e = 0.0;
+        for (int i = lane; i < nfft; i += 64) { const cplx v = xs[FC_XP(i)]; e += v.x * v.x + v.y * v.y; }
+        for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
+        if (lane == 0) *e0 = e;
+    }
 }
 
 // Block form: E(0) by a block reduction, then a block scan of both terms (one barrier in the middle)
@@ -2473,7 +2441,8 @@ __device__ __forceinline__ void fc_block_best(const FcThread& th, FcShared& sh, 
 // when U(t) < sqrt(P*).  fp32 group sums: each of the 8 terms and 7 additions errs by <= 2^-24 relative, all
 // terms are <= N*E(t), so |sumS - exact| < 2e-6 * N*E(t); the margins cover that, the fp32 storage of s and C
 // and the fp64 rounding of E and P.  Narrows sh.a / sh.b to the certified range around t* = bt (two barriers).
-__device__ __forceinline__ void fc_certificate(const FcCarve& cv, const FcThread& th, int nfft, FcShared& sh, double best, int bt) {
+// e0: what has to be added to Et[t] to give E(t) (the role split keeps E(0) apart, see fc_scan_role; 0 behind the block scan).
+__device__ __forceinline__ void fc_certificate(const FcCarve& cv, const FcThread& th, int nfft, FcShared& sh, double best, int bt, double e0) {
     const int tid = th.tid, lane = th.lane, wave = th.wave, nthr = th.nthr, nwave = th.nwave, nstep = cv.nstep;
     double* Et = fc_at<double>(cv.Et);
     float* sumS = fc_at<float>(cv.sumS);
@@ -2486,7 +2455,7 @@ __device__ __forceinline__ void fc_certificate(const FcCarve& cv, const FcThread
     const int u0 = tid * per < nstep + 1 ? tid * per : nstep + 1, u1 = u0 + per < nstep + 1 ? u0 + per : nstep + 1;
     double mf = INF, mb = INF;
     for (int t = u0; t < u1; ++t) {
-        const double NE = (double)nfft * Et[t];
+        const double NE = (double)nfft * (Et[t] + e0);
         const float ss = sumS[FC_XP(t)];
         const double R = NE - (double)ss + 4e-6 * NE;
         // (fp32 square root: s(t) is stored in fp32 anyway; the 1e-6 margin covers both roundings, < 2^-22 together)
@@ -2586,12 +2555,15 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
     FC_PRIO(2, 1, 0)                                      // choice of S and the anchors: oldest first
     const int lo = fc_choose_bins(cv, th, nfft, tw_g, sh);
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 2);
-    const int j = th.tid & (FC_NB - 1), c = th.tid / FC_NB;
-    const bool act = c < cv.nchunk;                       // lanes beyond the last chunk only help with the shared phases
+    // lane (c, j): bin j of chunk c in the anchors and the slides -- the chunks dealt round the slide waves, see fc_slide_chunk();
+    // c1: this group's first block of level 1
+    const int nslide = fc_nslide(cv.nchunk);              // waves that hold slide lanes
+    const int j = th.tid & (FC_NB - 1), c1 = th.tid / FC_NB, c = fc_slide_chunk(th.tid, nslide);
+    const bool act = c < cv.nchunk;                       // the other lanes only help with the shared phases
     const int k = ((lo + j) % nfft + nfft) % nfft;
     fc_twiddles(cv, th, nfft, lo, tw_g);
     __syncthreads();
-    fc_level1(cv, th, j, c);
+    fc_level1(cv, th, j, c1);
     __syncthreads();
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 3);
     double xr = 0.0, xi = 0.0;
@@ -2604,14 +2576,16 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
     // form the two scans meanwhile, each on its own -- no barrier and no exchange before the join in front of the block
     // reduction.  (Before: all four waves scanned together, then waves 2 and 3 sat out the slides.)  Only the association
     // of the fp64 sums differs (~1e-13 relative in E and C, far inside the certificate's margins); P*, t*, k* are untouched.
-    const int nslide = (FC_NB * cv.nchunk + 63) >> 6;     // waves that hold slide lanes
     const bool split = th.nwave - nslide >= 2;
     if (split) {
         DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 5);
-        if (th.wave == nslide || th.wave == nslide + 1) { // (wave-uniform) the E wave and the C wave
-            const bool we = th.wave == nslide;
-            fc_scan_role<OV>(cv, th, nfft, we);
-            FC_ROLE_STAMP(th.wave, we ? 12 : 13);
+        const int role = __builtin_amdgcn_readfirstlane(th.wave) - nslide;     // 0: the E wave, 1: the C wave
+        if (role == 0) {
+            fc_scan_role<OV, true>(cv, th, nfft, nullptr);
+            FC_ROLE_STAMP(th.wave, 12);
+        } else if (role == 1) {
+            fc_scan_role<OV, false>(cv, th, nfft, fc_at<double>(cv.sh_scan2) + 7);
+            FC_ROLE_STAMP(th.wave, 13);
         }
     } else {
         fc_scan_block(cv, th, nfft, sh);
@@ -2663,7 +2637,10 @@ __global__ void __launch_bounds__(512) k_fine_cert(const StreamState* __restrict
     __syncthreads();                                      // the join of the roles (without the split: red_p was E(0) until here)
     DEV_STAMP(KID_CERT, blockIdx.y * gridDim.x + blockIdx.x, 6);
     fc_block_best(th, sh, best, bt, bk);
-    fc_certificate(cv, th, nfft, sh, best, bt);
+    // E(0) of the role split waits in the last slot of sh_scan2: the certificate writes its partials only behind its first barrier,
+    // after every read of Et
+    const double e0 = split ? fc_at<double>(cv.sh_scan2)[7] : 0.0;
+    fc_certificate(cv, th, nfft, sh, best, bt, e0);
     __syncthreads();
 #ifdef GSMCAL_AB_LAZY_WIN
     if (fg.raw && OV > 0 && NTAPS == 47 && fg.sym47 != 0 && (sh.a != 0 || sh.b < cv.nstep)) {      // (block-uniform) chunks stay open: k_fine_chunk / the exact pass read the window
