@@ -2093,8 +2093,8 @@ __device__ __forceinline__ uint4 fc_raw_chunk(const unsigned short* base, long n
     const long g0 = first_al + 8L * tid;
     return g0 < first + span ? ffast_chunk(base, g0, n0) : make_uint4(0, 0, 0, 0);
 }
-// The window straight from the raw bytes (raw2iq.m:6-8 + filter(coef,1,.), gather_core's level 0 with the same
-// order of operations), in passes of fg.per outputs staged through regions 1/2 (free until the tone estimate):
+// The window straight from the raw bytes (raw2iq.m:6-8 + filter(coef,1,.): gather_core's level 0, through the same
+// functions of chain_ops.h), in passes of fg.per outputs staged through regions 1/2 (free until the tone estimate):
 // the window never makes the trip through HBM before the first use, and the k_gather launch in front of this
 // kernel is gone.  It is still written out for k_fine_chunk / k_fine_verify.  (Stamps 8 .. 11 and the A/B build's store sit
 // between the passes' own barriers, in here.)
@@ -2133,7 +2133,7 @@ __device__ __forceinline__ void fc_window_raw(const FcCarve& cv, const FcThread&
             pre = fc_raw_chunk(base, n0, ao, first + per, ncnt + ntp - 1, tid, first_al);
         }
         for (int i0 = 4 * tid; i0 < cnt; i0 += 4 * nthr) {
-            cplx y0, y1, y2, y3;              // gather_core's loop: every accumulator takes its taps oldest first
+            cplx y0, y1, y2, y3;              // (chain_ops.h: every accumulator takes its taps oldest first)
             if (OV > 0 && NTAPS == 47 && sym47) {   // same sums, bit for bit: 50 LDS reads per four outputs instead of 72
                 cplx y[4];
                 fir4_sym47(xq, cf, i0, y);

@@ -74,9 +74,9 @@ __device__ __forceinline__ PeakOut merge_peaks_coherent(const PeakOut* p, int NB
 // ------------------------------------------------------------------------------------------------
 // burst_gather_fast: gather_core for the case k_post_chain_r's burst stages nearly always see -- the stream's state is
 // this workgroup's LDS copy, level 0 of the burst lies inside a window the fine search filtered (a.l0), and the chain
-// above it is LERP (level 1) or LERP | MIX | LERP-or-COPY (level 3).  Same arithmetic per sample as gather_core (same
-// expressions in the same order: the two give identical bits), organised around what bounds a workgroup here, the
-// number of barrier-separated phases and of round trips to L2:
+// above it is LERP (level 1) or LERP | MIX | LERP-or-COPY (level 3).  Same arithmetic per sample as gather_core (both call
+// chain_ops.h: lerp_src_range, fine_window_holding, lerp_tap / lerp_blend, rot_table_fill / rot_at), organised around what
+// bounds a workgroup here, the number of barrier-separated phases and of round trips to L2:
 //   * every wave works the plan out itself from LDS (no plan phase);
 //   * level 1 is interpolated straight from the window buffer (no LDS copy of level 0), with the loads of the burst
 //     stage's nfft-point twiddle table in flight at the same time;
@@ -122,41 +122,23 @@ __device__ __forceinline__ int burst_gather_fast(const StreamState* __restrict__
     const long lo3 = uni_l(v_ws), hi3 = lo3 + L - 1;
     long lo1 = lo3, hi1 = hi3;                                   // level 1 (and 2: a MIX keeps the range)
     if (level == 3 && t3 == OP_LERP) {
-        lo1 = (long)floor((double)lo3 * f3);
-        const long h = (long)floor((double)hi3 * f3) + 1, n2 = uni_l(v_n2);
-        hi1 = h > n2 - 1 ? n2 - 1 : h;
+        const LerpRange r = lerp_src_range(lo3, hi3, f3, uni_l(v_n2));
+        lo1 = r.lo; hi1 = r.hi;
     }
-    const long lo0 = (long)floor((double)lo1 * f1);
-    long hi0 = (long)floor((double)hi1 * f1) + 1;
-    {
-        const long n0 = uni_l(v_n0);
-        hi0 = hi0 > n0 - 1 ? n0 - 1 : hi0;
-    }
+    const LerpRange r0 = lerp_src_range(lo1, hi1, f1, uni_l(v_n0));
+    const long lo0 = r0.lo, hi0 = r0.hi;
     const int cnt1 = (int)(hi1 - lo1 + 1);
     const GatherCarve gc = gather_carve(a.len, a.level, a.src_kind, a.ntaps, true, a.pad != 0);
     if (level == 3 && (cnt1 > 32 * GC_ROT_A || cnt1 > (int)gc.bufn || cnt1 <= 0)) return 0;
     // the fine window holding [lo0, hi0] (every wave finds it itself)
-    int h0;
-    long off0;
-    {
-        const bool in = lane < uni_i(v_nf) && lane < MAXH;
-        const unsigned long long m = __ballot(in && fw <= lo0 && hi0 < fw + a.l0_len);
-        if (!m) return 0;
-        h0 = __ffsll((long long)m) - 1;
-        off0 = lo0 - uni_l(__shfl(fw, h0, 64));
-    }
-    const cplx* __restrict__ x = a.l0 + (size_t)s * a.l0_stream_stride + (size_t)h0 * a.l0_win_stride + off0;   // x[i]: level-0 sample lo0+i
+    const FineWin w0 = fine_window_holding(fw, uni_i(v_nf), lo0, hi0, a.l0_len, lane);
+    if (w0.h < 0) return 0;
+    const cplx* __restrict__ x = a.l0 + (size_t)s * a.l0_stream_stride + (size_t)w0.h * a.l0_win_stride + uni_l(w0.off);   // x[i]: level-0 sample lo0+i
     cplx* buf0 = (cplx*)smem;
     cplx* buf1 = (cplx*)(smem + gc.off_region1);
-    auto lerp1 = [&](int i) {                                    // level-1 sample lo1+i
-        const long k = lo1 + i;
-        const double xq = lerp_pos((double)k, f1);               // interp_seq = (0:max_len-1)'.*(1+e)
-        const long i0 = (long)floor(xq);
-        const long i1 = i0 + 1 > hi0 ? hi0 : i0 + 1;             // beyond the last sample the weight is 0
-        const double t = xq - (double)i0;
-        const cplx v0 = x[i0 - lo0], v1 = x[i1 - lo0];
-        return make_double2(v0.x + t * (v1.x - v0.x), v0.y + t * (v1.y - v0.y));
-    };
+    const double dlo0 = (double)lo0, dlo1 = (double)lo1;
+    const int last0 = (int)(hi0 - lo0), last1 = (int)(hi1 - lo1);
+    auto lerp1 = [&](int i) { return lerp_at(x, (double)(lo1 + i), f1, dlo0, last0); };   // level-1 sample lo1+i
     DEV_STAMP(KID, blockIdx.y * gridDim.x + blockIdx.x, 5);
     if (level == 1) {
         for (int n = tid; n < nfft; n += NT) buf1[n] = tw_g[n];
@@ -165,15 +147,9 @@ __device__ __forceinline__ int burst_gather_fast(const StreamState* __restrict__
         return 1;
     }
     // level 3
-    cplx* T = (cplx*)(smem + gc.off_rot);                        // S | A[] | B[] of the level-2 rotator (gather_core's table)
-    const int na = (cnt1 + 31) >> 5;
+    cplx* T = (cplx*)(smem + gc.off_rot);                        // S | A[] | B[] of the level-2 rotator (rot_table_fill)
     for (int i = tid; i < cnt1; i += NT) buf1[i] = lerp1(i);
-    for (int i = tid; i < 1 + na + 32; i += NT) {
-        const double arg = i == 0 ? (double)lo1 * c2 : (i <= na ? (double)(32 * (i - 1)) * c2 : (double)(i - 1 - na) * c2);
-        double sn, cs;
-        sincos_large(arg, &sn, &cs);
-        T[i == 0 ? 0 : (i <= na ? i : 1 + GC_ROT_A + (i - 1 - na))] = make_double2(cs, sn);
-    }
+    rot_table_fill(T, lo1, c2, cnt1, tid, NT);
     DEV_STAMP(KID, blockIdx.y * gridDim.x + blockIdx.x, 6);
     __syncthreads();
     DEV_STAMP(KID, blockIdx.y * gridDim.x + blockIdx.x, 7);
@@ -181,19 +157,12 @@ __device__ __forceinline__ int burst_gather_fast(const StreamState* __restrict__
     // unconditional loads: with the three loads predicated the register allocator spills 150 vector registers to scratch,
     // 880 B/lane, and a frame that size halves the speed of every kernel on the queue.)
     const cplx tw0 = tw_g[min(tid, nfft - 1)], tw1 = tw_g[min(tid + NT, nfft - 1)], tw2 = tw_g[min(tid + 2 * NT, nfft - 1)];
-    auto lvl2 = [&](int i) {                                     // level-2 sample lo1+i: exp(1i*k*comp_phase_rotate) from the table
-        return cmul(buf1[i], cmul(cmul(T[0], T[1 + (i >> 5)]), T[1 + GC_ROT_A + (i & 31)]));
-    };
+    auto lvl2 = [&](int i) { return cmul(buf1[i], rot_at(T, i)); };   // level-2 sample lo1+i: exp(1i*k*comp_phase_rotate) from the table
     if (t3 == OP_LERP) {
 #pragma unroll 1
         for (int i = tid; i < L; i += NT) {
-            const long k = lo3 + i;
-            const double xq = lerp_pos((double)k, f3);
-            const long i0 = (long)floor(xq);
-            const long i1 = i0 + 1 > hi1 ? hi1 : i0 + 1;
-            const double t = xq - (double)i0;
-            const cplx v0 = lvl2((int)(i0 - lo1)), v1 = lvl2((int)(i1 - lo1));
-            buf0[i] = make_double2(v0.x + t * (v1.x - v0.x), v0.y + t * (v1.y - v0.y));
+            const LerpTap p = lerp_tap((double)(lo3 + i), f3, dlo1, last1);
+            buf0[i] = lerp_blend(lvl2(p.j0), lvl2(p.j1), p.t);
         }
     } else {
         for (int i = tid; i < L; i += NT) buf0[i] = lvl2(i);
@@ -207,15 +176,15 @@ __device__ __forceinline__ int burst_gather_fast(const StreamState* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // sch_gather_fast: gather_core for the SCH search window of the reference chain -- raw source, level 2 = LERP | MIX, the
-// stream's state in this workgroup's LDS copy.  Same arithmetic per sample as gather_core (same expressions in the same
-// order: identical bits), in three barrier-separated phases where gather_core has seven:
-//   1. every wave works the plan out itself from LDS (gather_core's backward range propagation, the n0 - 1 clamp
-//      included).  The lanes of the first waves fetch one 16-byte-aligned raw chunk each (eight samples, zero outside
-//      [0, n0)) straight into registers, issued before anything that can wait; the waves WITHOUT a chunk meanwhile build
-//      the MIX rotator table S | A[] | B[] (where gather_core stages the raw bytes: free here) and stage the taps; the
-//      chunk lanes then convert their registers into the padded FIR input (raw2iq.m:6-8);
-//   2. filter(coef,1,.) -> buf0: gather_core's loop (fir4_lds, every accumulator oldest tap first);
-//   3. one pass that interpolates level 1 from buf0 and applies (T[0]*A[i>>5])*B[i&31] as it goes -> region 1.
+// stream's state in this workgroup's LDS copy.  Same arithmetic per sample as gather_core (both call chain_ops.h), in
+// three barrier-separated phases where gather_core has seven:
+//   1. every wave works the plan out itself from LDS (lerp_src_range).  The lanes of the first waves fetch one
+//      16-byte-aligned raw chunk each (ffast_chunk) straight into registers, issued before anything that can wait; the
+//      waves WITHOUT a chunk meanwhile build the MIX rotator table (rot_table_fill; where gather_core stages the raw bytes:
+//      free here) and stage the taps; the chunk lanes then convert their registers into the padded FIR input
+//      (raw_chunk_to_lds);
+//   2. filter(coef,1,.) -> buf0: fir4_lds, fir4_store;
+//   3. one pass that interpolates level 1 from buf0 (lerp_at) and applies rot_at as it goes -> region 1.
 // gather_core's shortcut for level 0 -- a copy from a fine-search window (a.l0) that holds all of [lo0, hi0] -- is
 // deliberately not taken: run_sch hands no such buffer over (the SCH windows lie a frame behind the fine windows), and
 // where one is given the raw bytes are filtered all the same: the same taps in the same order, the same bits.
@@ -239,9 +208,8 @@ __device__ __forceinline__ int sch_gather_fast(const StreamState* __restrict__ s
     const double f1 = uni_d(v_f1), c2 = uni_d(v_c2);
     const long n0 = uni_l(v_n0);
     const long lo1 = uni_l(v_ws), hi1 = lo1 + L - 1;             // levels 2 and 1 (a MIX keeps the range)
-    const long lo0 = (long)floor((double)lo1 * f1);
-    long hi0 = (long)floor((double)hi1 * f1) + 1;
-    hi0 = hi0 > n0 - 1 ? n0 - 1 : hi0;
+    const LerpRange r0 = lerp_src_range(lo1, hi1, f1, n0);
+    const long lo0 = r0.lo, hi0 = r0.hi;
     if (hi0 < lo0 || hi0 - lo0 + 1 > (long)L + 8) return 0;      // (the staged span has to fit the carve; a LERP factor far from 1 goes the generic way)
     const int cnt0 = (int)(hi0 - lo0 + 1);
     const GatherCarve gc = gather_carve(L, 2, SRC_RAW, a.ntaps, true, false);
@@ -255,76 +223,33 @@ __device__ __forceinline__ int sch_gather_fast(const StreamState* __restrict__ s
     const int ntp = a.ntaps;
     const long first = lo0 - (ntp - 1);
     const int span = cnt0 + ntp - 1;
-    const long ao = (long)(((uintptr_t)base >> 1) & 7);          // stage_raw's alignment: sample first_al sits on a 16-byte boundary
-    long m = (first + ao) % 8;
-    if (m < 0) m += 8;
-    const long first_al = first - m;
-    const int nchunk = (int)((m + span + 8 + 7) >> 3);           // chunks that cover staged entries 0 .. span+7 (<= (7 + L+8+46 + 15) / 8 < NT)
+    const long first_al = raw_first_al(first, raw_align_off(base));
+    const int nchunk = raw_nchunk(first, span + 8, first_al);    // chunks that cover staged entries 0 .. span+7 (<= (7 + L+8+46 + 15) / 8 < NT)
     const int nwc = (nchunk + 63) >> 6;                          // waves that hold a chunk
     if (nchunk > NT - 128) return 0;                             // (one chunk per lane, and two waves left for the table and the taps)
     if (tid < 64 * nwc) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        const long g0 = first_al + 8L * tid;
         if (tid < nchunk) {
-            if (g0 >= 0 && g0 + 8 <= n0) {
-                v = *(const uint4*)(base + g0);
-            } else {
-                unsigned short t[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) t[i] = (g0 + i >= 0 && g0 + i < n0) ? base[g0 + i] : (unsigned short)0;
-                v.x = t[0] | ((unsigned)t[1] << 16); v.y = t[2] | ((unsigned)t[3] << 16);
-                v.z = t[4] | ((unsigned)t[5] << 16); v.w = t[6] | ((unsigned)t[7] << 16);
-            }
-            // raw2iq.m:6-8 from the registers: staged entry i = 8*tid - m + u is sample g0 + u; (I - mean) + 1i (Q - mean), zero
-            // before the stream starts (filter()'s zero initial state), past its end, and in entries span .. span+7
-            const double mr = uni_d(v_mr), mi = uni_d(v_mi);
-            const int i_base = 8 * tid - (int)m;
-            const unsigned wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i_base + u;
-                const long g = g0 + u;
-                const unsigned q = (wv[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
-                cplx x = make_double2(0.0, 0.0);
-                if (i < span && g >= 0 && g < n0) x = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
-                if (i >= 0 && i < span + 8) xs[xs_pad(i)] = x;
-            }
+            const uint4 v = ffast_chunk(base, first_al + 8L * tid, n0);
+            // raw2iq.m:6-8 from the registers; zeros in entries span .. span+7
+            raw_chunk_to_lds(xs, v, tid, (int)(first - first_al), first, span, span + 8, n0, uni_d(v_mr), uni_d(v_mi));
         }
     } else {
         const int t = tid - 64 * nwc, nh = NT - 64 * nwc;
-        const int na = (L + 31) >> 5;
         if (t >= 64) fir_stage_taps(c_s, a.coef, ntp, t - 64, nh - 64);
-        else {
-            for (int i = t; i < 1 + na + 32; i += 64) {
-                const double arg = i == 0 ? (double)lo1 * c2 : (i <= na ? (double)(32 * (i - 1)) * c2 : (double)(i - 1 - na) * c2);
-                double sn, cs;
-                sincos_large(arg, &sn, &cs);
-                T[i == 0 ? 0 : (i <= na ? i : 1 + GC_ROT_A + (i - 1 - na))] = make_double2(cs, sn);
-            }
-        }
+        else rot_table_fill(T, lo1, c2, L, t, 64);
     }
     __syncthreads();
     // ---- phase 2: filter(coef,1,.), four consecutive outputs per lane ----
     for (int i0 = 4 * tid; i0 < cnt0; i0 += 4 * NT) {
         cplx y0, y1, y2, y3;
         fir4_lds<0, true, FIR_UNR>(xs, c_s, i0, ntp, &y0, &y1, &y2, &y3);
-        buf0[i0] = y0;
-        if (i0 + 1 < cnt0) buf0[i0 + 1] = y1;
-        if (i0 + 2 < cnt0) buf0[i0 + 2] = y2;
-        if (i0 + 3 < cnt0) buf0[i0 + 3] = y3;
+        fir4_store(buf0, i0, cnt0, y0, y1, y2, y3);
     }
     __syncthreads();
     // ---- phase 3: level 1 (interp1) and level 2 (the derotation from the table) in one pass ----
-    for (int i = tid; i < L; i += NT) {
-        const long k = lo1 + i;
-        const double xq = lerp_pos((double)k, f1);               // interp_seq = (0:max_len-1)'.*(1+e)
-        const long i0 = (long)floor(xq);
-        const long i1 = i0 + 1 > hi0 ? hi0 : i0 + 1;             // beyond the last sample the weight is 0
-        const double t = xq - (double)i0;
-        const cplx v0 = buf0[i0 - lo0], v1 = buf0[i1 - lo0];
-        const cplx l1 = make_double2(v0.x + t * (v1.x - v0.x), v0.y + t * (v1.y - v0.y));
-        buf1[i] = cmul(l1, cmul(cmul(T[0], T[1 + (i >> 5)]), T[1 + GC_ROT_A + (i & 31)]));
-    }
+    const double dlo0 = (double)lo0;
+    const int last0 = cnt0 - 1;
+    for (int i = tid; i < L; i += NT) buf1[i] = cmul(lerp_at(buf0, (double)(lo1 + i), f1, dlo0, last0), rot_at(T, i));
     return 1;
 }
 #define BT_STAMP(i) DEV_STAMP(GATE ? KID_BT1 : KID_BT0, blockIdx.y * gridDim.x + blockIdx.x, i)

@@ -10,23 +10,14 @@
 //   k_fir_arr       filter(coef,1,s) (+ r(1:decim:end,:)) on a complex array (chn_filter_8x_4x.m:13-15)
 //   k_gather        evaluates a window (or every tile) of a stream at any level of the lazy chain
 //                   (state.h) through LDS: raw -> FIR -> lerp -> mix -> lerp -> mix
+//   k_stream_tile<NT>, k_stream_tile_s47   the whole corrected stream, tile by tile
+// The chain's per-sample arithmetic -- raw chunks, raw2iq, the FIR of four outputs, interp1, the rotator tables -- is written in
+// chain_ops.h and nowhere else; the kernels here call it.
 #pragma once
 #include "state.h"
+#include "chain_ops.h"
 
-typedef double2 cplx;
 #define NAN_D __longlong_as_double(0x7ff8000000000000LL)   /* MATLAB's NaN: quiet, sign clear, payload 0 */
-
-// sin/cos of a LARGE fp64 argument t (|t| up to ~1e6 rad: t = k*comp_phase_rotate, k up to 1e6) with the
-// accuracy of a correctly reduced argument, several times cheaper than the library's general path:
-// n = round(t/2pi); y = t - n*2pi with 2pi = C1 + C2 split so that the first fma is EXACT (t and n*C1 are
-// both multiples of 2^-50 and the difference is < 8, so it fits a double), the second adds n*C2 <= 4e-11
-// with an error <= ulp(y); then the library routine on |y| <= pi (its cheap small-argument path).
-__device__ __forceinline__ void sincos_large(double t, double* sn, double* cs) {
-    const double n = rint(t * 0.15915494309189535);            // 1/(2*pi)
-    double y = fma(-n, 6.28318530717958623e+00, t);            // C1 = fl(2*pi)
-    y = fma(-n, 2.44929359829470641e-16, y);                   // C2 = 2*pi - C1
-    sincos(y, sn, cs);
-}
 
 // Sum of v over the 64 lanes of the wave, returned in every lane (wave-uniform).  Data-parallel-primitive moves instead of
 // LDS-crossbar shuffles: xor 1, xor 2, half-row mirror, row mirror give every lane its 16-lane row total; row_bcast15 /
@@ -74,42 +65,20 @@ __device__ __forceinline__ double wave_scan_incl(double v) {
     return v;
 }
 
-__device__ __forceinline__ cplx cmul(cplx a, cplx b) {
-    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Stage raw samples [first, first+span) of one stream (I | Q<<8 per ushort) into LDS with 16-byte
 // global loads.  Returns `first_al` <= first: sample g lives at r_s[g - first_al].  Samples outside
 // [0, n) read as 0 (filter()'s zero initial state is applied by the callers through g < 0 tests).
 // r_s must hold span + 16 ushorts and be 16-byte aligned.
 // ------------------------------------------------------------------------------------------------
-// PAD: insert 8 ushorts (16 B) after every 64 samples so that lanes whose samples are 64 apart (the
-// decimate-by-64 FIR) do not all hit the same LDS bank; use lds_pad() to index.
-__device__ __forceinline__ int lds_pad(int rel) { return rel + ((rel >> 6) << 3); }
-
+// PAD: the LDS copy is laid out with lds_pad() (chain_ops.h); use it to index.
 template <bool PAD = false>
 __device__ __forceinline__ long stage_raw(unsigned short* r_s, const unsigned short* base, long n, long first,
                                           int span, int tid, int nthreads) {
-    const long ao = (long)(((uintptr_t)base >> 1) & 7);          // samples past a 16-byte boundary at g = 0
-    long m = (first + ao) % 8;
-    if (m < 0) m += 8;
-    const long first_al = first - m;                             // address of sample first_al is 16-byte aligned
-    const int nchunk = (int)((first + span - first_al + 7) >> 3);
-    for (int c = tid; c < nchunk; c += nthreads) {
-        const long g0 = first_al + 8L * c;
-        uint4 v;
-        if (g0 >= 0 && g0 + 8 <= n) {
-            v = *(const uint4*)(base + g0);
-        } else {
-            unsigned short t[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) t[i] = (g0 + i >= 0 && g0 + i < n) ? base[g0 + i] : (unsigned short)0;
-            v.x = t[0] | ((unsigned)t[1] << 16); v.y = t[2] | ((unsigned)t[3] << 16);
-            v.z = t[4] | ((unsigned)t[5] << 16); v.w = t[6] | ((unsigned)t[7] << 16);
-        }
-        *(uint4*)(r_s + (PAD ? lds_pad(8 * c) : 8 * c)) = v;
-    }
+    const long first_al = raw_first_al(first, raw_align_off(base));   // address of sample first_al is 16-byte aligned
+    const int nchunk = raw_nchunk(first, span, first_al);
+    for (int c = tid; c < nchunk; c += nthreads)
+        *(uint4*)(r_s + (PAD ? lds_pad(8 * c) : 8 * c)) = ffast_chunk(base, first_al + 8L * c, n);
     return first_al;
 }
 
@@ -280,11 +249,8 @@ __global__ void __launch_bounds__(256) k_front_fused(const uint8_t* __restrict__
     const int t = threadIdx.x;
     // stage [first, first+span) into LDS with 16-byte loads, FF_INFLIGHT in flight per lane, and take the integer
     // I/Q sums (raw2iq.m:8) of the owned samples straight from the registers (v_sad_u8)
-    const long ao = (long)(((uintptr_t)base >> 1) & 7);
-    long mm = (first + ao) % 8;
-    if (mm < 0) mm += 8;
-    const long first_al = first - mm;                       // 16-byte aligned in memory
-    const int nchunk = (int)((first + span - first_al + 7) >> 3);
+    const long first_al = raw_first_al(first, raw_align_off(base));   // 16-byte aligned in memory
+    const int nchunk = raw_nchunk(first, span, first_al);
     const long o0 = j0 * decim;
     unsigned int si = 0, sq = 0;
     for (int c0 = t; c0 < nchunk; c0 += 256 * FF_INFLIGHT) {
@@ -294,17 +260,7 @@ __global__ void __launch_bounds__(256) k_front_fused(const uint8_t* __restrict__
             const int c = c0 + 256 * u;
             const long g0 = first_al + 8L * c;
             v[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (c < nchunk) {
-                if (g0 >= 0 && g0 + 8 <= n) {
-                    v[u] = *(const uint4*)(base + g0);
-                } else {
-                    unsigned short q[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) q[i] = (g0 + i >= 0 && g0 + i < n) ? base[g0 + i] : (unsigned short)0;
-                    v[u].x = q[0] | ((unsigned)q[1] << 16); v[u].y = q[2] | ((unsigned)q[3] << 16);
-                    v[u].z = q[4] | ((unsigned)q[5] << 16); v[u].w = q[6] | ((unsigned)q[7] << 16);
-                }
-            }
+            if (c < nchunk) v[u] = ffast_chunk(base, g0, n);
         }
 #pragma unroll
         for (int u = 0; u < FF_INFLIGHT; ++u) {
@@ -417,61 +373,6 @@ __device__ __forceinline__ void st_stream16(cplx* p, const cplx v) {
     o.x = v.x; o.y = v.y;
     __builtin_nontemporal_store(o, (f64x2_t*)p);
 }
-__device__ __forceinline__ uint4 ffast_chunk(const unsigned short* __restrict__ base, long g0, long n) {
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);                   // 8 samples from g0, zeros outside [0, n)
-    if (g0 >= 0 && g0 + 8 <= n) {
-        v = *(const uint4*)(base + g0);
-    } else if (g0 + 8 > 0 && g0 < n) {                      // straddles an end of the stream
-        unsigned short q[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) q[i] = (g0 + i >= 0 && g0 + i < n) ? base[g0 + i] : (unsigned short)0;
-        v.x = q[0] | ((unsigned)q[1] << 16); v.y = q[2] | ((unsigned)q[3] << 16);
-        v.z = q[4] | ((unsigned)q[5] << 16); v.w = q[6] | ((unsigned)q[7] << 16);
-    }
-    return v;
-}
-// Staging a span [first, first + span) of raw samples by whole 16-byte chunks, one chunk per lane (k_fine_cert's window build,
-// k_stream_tile_s47): `ao` = samples past a 16-byte boundary at g = 0; raw_first_al() <= first is the sample the first chunk
-// starts at (its address is 16-byte aligned), so chunk `tid` is ffast_chunk(base, first_al + 8 * tid, n).
-__device__ __forceinline__ long raw_align_off(const unsigned short* base) { return (long)(((uintptr_t)base >> 1) & 7); }
-__device__ __forceinline__ long raw_first_al(long first, long ao) {
-    long m = (first + ao) % 8;
-    if (m < 0) m += 8;
-    return first - m;
-}
-__device__ __forceinline__ int xs_pad(int p);
-// raw2iq.m:6-8 from the registers: the eight samples of chunk `tid` (in `pre`) go to the xs_pad layout at xq, staged entry
-// i = 8*tid + u - off with off = first - first_al; (I - mean) + 1i (Q - mean), zeros outside the span and outside the stream [0, n).
-// Entries below 0 are never written, entries from `hi` on neither (the caller's bound: the zeros it wants behind the span).
-__device__ __forceinline__ void raw_chunk_to_lds(cplx* xq, const uint4 pre, int tid, int off, long first, int span, int hi, long n,
-                                                 double mr, double mi) {
-    const int i_base = 8 * tid - off;
-    const long g_base = first + i_base;
-    const unsigned wv[4] = {pre.x, pre.y, pre.z, pre.w};
-    if (i_base >= 0 && i_base + 8 <= span && g_base >= 0 && g_base + 8 <= n) {
-        // the usual chunk: all eight samples inside the span and the stream -- no per-sample tests (they were most of this loop).
-        // xs_pad(i_base + u) = xs_pad(i_base) + u + ((r + u) >> 2) with r = i_base & 3 = (-off) & 3, the same in every lane: the
-        // eight slots are one lane address plus scalar offsets (three vector instructions per slot before)
-        const int r = __builtin_amdgcn_readfirstlane((-off) & 3);
-        cplx* xp = xq + xs_pad(i_base);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const unsigned q = wv[u >> 1] >> (16 * (u & 1));
-            xp[u + ((r + u) >> 2)] = make_double2((double)(q & 0xFFu) - mr, (double)((q >> 8) & 0xFFu) - mi);
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i_base + u;
-            const long g = first + i;
-            const unsigned q = (wv[u >> 1] >> (16 * (u & 1))) & 0xFFFFu;
-            cplx v = make_double2(0.0, 0.0);
-            if (i < span && g >= 0 && g < n) v = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
-            if (i >= 0 && i < hi) xq[xs_pad(i)] = v;
-        }
-    }
-}
-
 template <int NT, bool SYM>
 __global__ void __launch_bounds__(256) k_front_fast(const uint8_t* __restrict__ raw, long stream_bytes,
                                                     unsigned long long* __restrict__ partial,
@@ -682,81 +583,12 @@ __device__ __forceinline__ long level_len(const StreamState* st, int level) {
     return level == 0 ? st->n0 : st->op[level].n;
 }
 
-// LDS position of staged input sample p: one 16-byte pad after every 4 samples, so that lanes reading
-// samples 4 apart (the 4-outputs-per-lane FIR below) hit distinct banks with ds_read_b128.
-__device__ __forceinline__ int xs_pad(int p) { return p + (p >> 2); }
-
-// Query position k*(1+e) of interp1 (interp_seq, FCCH_fine_correction.m:123, SCH_corr_rate_correction.m:126), ROUNDED to
-// double as the reference rounds it before interp1 sees it.  Contraction must stay off here: left to the compiler, the
-// weight xq - floor(xq) behind it becomes fma(k, f, -floor(xq)) -- the weight of the UNROUNDED product, up to an ulp of xq
-// (1.2e-10 at k = 6e5) away from the reference's.  On unfiltered samples that moved the tone estimate by 2e-11 ppm and the
-// end of the corrected stream by 4e-8 rad (tests/test_gpu_general_taps.py, the one-tap filter).
-__device__ __forceinline__ double lerp_pos(double k, double f) {
-#pragma clang fp contract(off)
-    return k * f;
-}
-
-// ------------------------------------------------------------------------------------------------
-// filter(coef,1,.) for FOUR consecutive outputs i0 .. i0+3 from the padded LDS copy xq (xs_pad indexing; i0 a multiple of
-// 4): y[i] = sum_k coef[k] x[i-k], every accumulator taking its taps oldest first (transposed direct-form order) -- the
-// one FIR loop of gather_core and of k_fine_cert's fused window build, so both give bit-identical level-0 samples.
-// NTP > 0: the tap count is a compile-time constant (the production fir1(46) filter): two trips per iteration with known
-// bounds.  (Unrolled completely the compiler hoists every coefficient and sample load: 256 registers and scratch.)
-// Tried and dropped (round 3): the taps through scalar loads from constant-address-space memory instead of LDS -- a third
-// of this loop's LDS bytes are coefficient broadcasts, and the 1024-stream step gained 2.5 % -- but SMEM shares the LDS
-// counter (lgkmcnt), every wait for a tap became a wait for the sample reads in flight, and the 64-stream step lost 3 us;
-// pipelining it by hand (next trip's samples and taps requested before this trip's FMAs) cost registers the 80-register
-// burst kernels do not have (scratch in the loop).
-// PAD = false: the input is staged without xs_pad's bank padding (gather_carve's compact_xs).
-// ------------------------------------------------------------------------------------------------
-// UNR: trips of the four-tap loop the compiler may overlap (2: the next trip's LDS reads under this trip's FMAs, ~20 more
-// registers; 1 where the caller has none to spare).
-// taps of fir4_lds in LDS: rev[j] = coef[ntaps-1-j] (oldest tap first), zero-padded to a multiple of four
-__host__ __device__ inline int fir_taps_padded(int ntaps) { return (ntaps + 3) & ~3; }
-__device__ __forceinline__ void fir_stage_taps(double* c_s, const double* __restrict__ coef, int ntaps, int first, int step) {
-    for (int i = first; i < fir_taps_padded(ntaps); i += step) c_s[i] = i < ntaps ? coef[ntaps - 1 - i] : 0.0;
-}
-template <int NTP, bool PAD = true, int UNR = 2>
-__device__ __forceinline__ void fir4_lds(const cplx* __restrict__ xq, const double* __restrict__ c_s, int i0, int ntp_rt,
-                                         cplx* y0, cplx* y1, cplx* y2, cplx* y3) {
-#define XSP(p_) (PAD ? xs_pad(p_) : (p_))
-    const int ntp = NTP > 0 ? NTP : ntp_rt;
-    const int ntp4 = (ntp + 3) & ~3;
-    double ar0 = 0.0, ai0 = 0.0, ar1 = 0.0, ai1 = 0.0, ar2 = 0.0, ai2 = 0.0, ar3 = 0.0, ai3 = 0.0;
-    cplx w0 = xq[XSP(i0)], w1 = xq[XSP(i0 + 1)], w2 = xq[XSP(i0 + 2)], w3 = xq[XSP(i0 + 3)];
-#define GSMCAL_FIR_TAP(C, A, B, D, E)                                   \
-    ar0 = fma(C, A.x, ar0); ai0 = fma(C, A.y, ai0);                     \
-    ar1 = fma(C, B.x, ar1); ai1 = fma(C, B.y, ai1);                     \
-    ar2 = fma(C, D.x, ar2); ai2 = fma(C, D.y, ai2);                     \
-    ar3 = fma(C, E.x, ar3); ai3 = fma(C, E.y, ai3);
-    // four taps per trip: the next four samples are one aligned, contiguous 64-byte group (i0 is a multiple of 4),
-    // fetched together, and so are the four taps (c_s holds them REVERSED -- oldest tap first -- and zero-padded to a multiple
-    // of four: fir_stage_taps; two 16-byte reads per trip instead of four 8-byte ones, and no remainder loop:
-    // fma(0, x, acc) = acc for the finite samples the callers stage behind the span).  Every accumulator still takes its
-    // taps in the same order (oldest first), so the sums are bit-identical to a one-tap loop.
-#pragma unroll UNR
-    for (int t = 0; t < ntp4; t += 4) {
-        const cplx* nx = xq + XSP(i0 + t + 4);
-        const double c0 = c_s[t], c1 = c_s[t + 1], c2 = c_s[t + 2], c3 = c_s[t + 3];   // (before the samples: LDS returns in order, and the first taps need only these)
-        const cplx n0s = nx[0], n1s = nx[1], n2s = nx[2], n3s = nx[3];
-        GSMCAL_FIR_TAP(c0, w0, w1, w2, w3)
-        GSMCAL_FIR_TAP(c1, w1, w2, w3, n0s)
-        GSMCAL_FIR_TAP(c2, w2, w3, n0s, n1s)
-        GSMCAL_FIR_TAP(c3, w3, n0s, n1s, n2s)
-        w0 = n0s; w1 = n1s; w2 = n2s; w3 = n3s;
-    }
-#undef GSMCAL_FIR_TAP
-#undef XSP
-    *y0 = make_double2(ar0, ai0); *y1 = make_double2(ar1, ai1); *y2 = make_double2(ar2, ai2); *y3 = make_double2(ar3, ai3);
-}
-
 // LDS layout of gather_core (byte offsets from the dynamic LDS base); also used by the host to size launches.
 struct GatherCarve {
     size_t bufn;          // elements per window buffer (0: none)
     size_t off_region1;   // buf1 / xs
     size_t off_coef, off_raw, off_rot, total;
 };
-#define GC_ROT_A 72                     /* rotator table: S | A[0..GC_ROT_A) | B[0..32): windows of up to 32*GC_ROT_A samples */
 // compact_xs: the complex input of the raw-source FIR is staged without bank-conflict padding (5 KB less for a burst window;
 // k_post_chain's burst stages, where that path is the rare fallback for a burst outside every fine window)
 __host__ __device__ inline GatherCarve gather_carve(int len, int level, int kind, int ntaps, bool to_lds, bool compact_xs = false) {
@@ -774,7 +606,7 @@ __host__ __device__ inline GatherCarve gather_carve(int len, int level, int kind
     // the rotator table of a derotation level lives where the raw bytes were (dead once level 0 exists); array sources
     // have no raw region, so it is appended there
     g.off_rot = g.off_raw;
-    const size_t rot_end = g.off_rot + (size_t)(1 + GC_ROT_A + 32) * 16;
+    const size_t rot_end = g.off_rot + (size_t)GC_ROT_N * 16;
     if (level >= 2 && rot_end > g.total) g.total = (rot_end + 15) & ~(size_t)15;
     return g;
 }
@@ -847,11 +679,8 @@ __device__ __forceinline__ cplx* gather_core(const StreamState* __restrict__ sts
             if (j <= level) {
                 if (tid == 0) { pl_lo[j] = clo; pl_hi[j] = chi; }
                 if (op_type[j] == OP_LERP) {
-                    const double f = op_param[j];
-                    const long nprev = lvl_n[j - 1];
-                    clo = (long)floor((double)clo * f);
-                    const long h = (long)floor((double)chi * f) + 1;
-                    chi = h > nprev - 1 ? nprev - 1 : h;
+                    const LerpRange r = lerp_src_range(clo, chi, op_param[j], lvl_n[j - 1]);
+                    clo = r.lo; chi = r.hi;
                 }
             }
         }
@@ -861,11 +690,8 @@ __device__ __forceinline__ cplx* gather_core(const StreamState* __restrict__ sts
         if (a.l0 && a.src_kind == SRC_RAW && L > 0) {
             const int nf = st_i32(&st->n_fine_ws);
             const long fw = (tid < nf && tid < MAXH) ? st_i64(&st->fine_ws[tid]) : 0;
-            const unsigned long long m = __ballot(tid < nf && tid < MAXH && fw <= clo && chi < fw + a.l0_len);
-            if (m) {
-                l0h = __ffsll((long long)m) - 1;
-                l0off = clo - __shfl(fw, l0h, 64);
-            }
+            const FineWin w = fine_window_holding(fw, nf, clo, chi, a.l0_len, tid);
+            l0h = w.h; l0off = w.off;
         }
         if (tid == 0) {
             pl_l0h = l0h; pl_l0off = l0off;
@@ -910,19 +736,7 @@ __device__ __forceinline__ cplx* gather_core(const StreamState* __restrict__ sts
         const long first_al = stage_raw(r_s, base, n0, first, span, tid, NT);
         __syncthreads();
         GC_STAMP(10);
-        // raw2iq.m:6-8 on the staged span: (I - mean) + 1i (Q - mean); zero before the stream starts
-        // (filter()'s zero initial state) and past its end
-        const double mr = pre_mr, mi = pre_mi;
-        const int off = (int)(first - first_al);
-        for (int i = tid; i < span + 8; i += NT) {
-            const long g = first + i;
-            cplx v = make_double2(0.0, 0.0);
-            if (i < span && g >= 0 && g < n0) {
-                const unsigned short q = r_s[off + i];
-                v = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
-            }
-            xs[compact ? i : xs_pad(i)] = v;
-        }
+        raw_span_to_lds(xs, r_s, (int)(first - first_al), first, span, 8, n0, pre_mr, pre_mi, compact, tid, NT);
         __syncthreads();
         GC_STAMP(11);
         // filter(coef,1,.) : y[i] = sum_k coef[k] x[i-k], accumulated oldest tap first (transposed
@@ -934,10 +748,7 @@ __device__ __forceinline__ cplx* gather_core(const StreamState* __restrict__ sts
             // k_fine_cert, at 108 registers, uses fir4_lds<47>)
             if (compact) fir4_lds<0, false, FIR_UNR>(xs, c_s, i0, ntp, &y0, &y1, &y2, &y3);
             else fir4_lds<0, true, FIR_UNR>(xs, c_s, i0, ntp, &y0, &y1, &y2, &y3);
-            out0[i0] = y0;
-            if (i0 + 1 < cnt0) out0[i0 + 1] = y1;
-            if (i0 + 2 < cnt0) out0[i0 + 2] = y2;
-            if (i0 + 3 < cnt0) out0[i0 + 3] = y3;
+            fir4_store(out0, i0, cnt0, y0, y1, y2, y3);
         }
     }
     GC_STAMP(12);
@@ -953,31 +764,15 @@ __device__ __forceinline__ cplx* gather_core(const StreamState* __restrict__ sts
         const double p = pl_param[j];
         const long plo = pl_lo[j - 1], phi_ = pl_hi[j - 1];
         if (type == OP_LERP) {
-            for (int i = threadIdx.x; i < cnt; i += NT) {
-                const long k = lo_j + i;
-                const double xq = lerp_pos((double)k, p);   // interp_seq = (0:max_len-1)'.*(1+e)
-                const long i0 = (long)floor(xq);
-                const long i1 = i0 + 1 > phi_ ? phi_ : i0 + 1;  // beyond the last sample the weight is 0
-                const double t = xq - (double)i0;
-                const cplx v0 = src[i0 - plo], v1 = src[i1 - plo];
-                o[i] = make_double2(v0.x + t * (v1.x - v0.x), v0.y + t * (v1.y - v0.y));
-            }
+            const double dplo = (double)plo;
+            const int last = (int)(phi_ - plo);
+            for (int i = threadIdx.x; i < cnt; i += NT) o[i] = lerp_at(src, (double)(lo_j + i), p, dplo, last);
         } else if (type == OP_MIX && cnt <= 32 * GC_ROT_A) {
-            // exp(1i*(0:len-1)'*comp_phase_rotate) from a two-level rotator table of the window:
-            // exp(1i*k*c) = S * A[(k-k0)>>5] * B[(k-k0)&31], S = exp(1i*fl(k0*c)), A[q] = exp(1i*fl(32q*c)), B[m] = exp(1i*fl(m*c))
-            // -- 1 + ceil(cnt/32) + 32 accurate sincos per window instead of one per sample.  The reference rounds k*c once;
-            // the three rounded pieces differ from that by < 2 ulp(k*c) ~ 3e-11 rad at k = 1e6 (see k_stream_tile).
+            // exp(1i*(0:len-1)'*comp_phase_rotate) from the window's two-level rotator table (chain_ops.h)
             cplx* T = (cplx*)(smem + gc.off_rot);
-            const int na = (cnt + 31) >> 5;
-            for (int i = threadIdx.x; i < 1 + na + 32; i += NT) {
-                const double arg = i == 0 ? (double)lo_j * p : (i <= na ? (double)(32 * (i - 1)) * p : (double)(i - 1 - na) * p);
-                double sn, cs;
-                sincos_large(arg, &sn, &cs);
-                T[i == 0 ? 0 : (i <= na ? i : 1 + GC_ROT_A + (i - 1 - na))] = make_double2(cs, sn);
-            }
+            rot_table_fill(T, lo_j, p, cnt, threadIdx.x, NT);
             __syncthreads();
-            for (int i = threadIdx.x; i < cnt; i += NT)
-                o[i] = cmul(src[i], cmul(cmul(T[0], T[1 + (i >> 5)]), T[1 + GC_ROT_A + (i & 31)]));
+            for (int i = threadIdx.x; i < cnt; i += NT) o[i] = cmul(src[i], rot_at(T, i));
         } else if (type == OP_MIX) {
             for (int i = threadIdx.x; i < cnt; i += NT) {
                 const long k = lo_j + i;
@@ -998,12 +793,12 @@ __device__ __forceinline__ cplx* gather_core(const StreamState* __restrict__ sts
 
 // ------------------------------------------------------------------------------------------------
 // k_stream_tile: the corrected stream r_correct (gsm_sync_demod.m:118-120 hands it on to SCH_demod), one tile of
-// ST_TILE output samples per workgroup -- the 18 B/sample mode of the batch path.  Same arithmetic per sample as
-// gather_core at level 4 (raw -> raw2iq -> filter -> interp1 -> exp derotation -> interp1 -> exp derotation), organised
-// for throughput instead of generality:
+// ST_TILE output samples per workgroup -- the 18 B/sample mode of the batch path.  The chain of gather_core at level 4
+// (raw -> raw2iq -> filter -> interp1 -> exp derotation -> interp1 -> exp derotation; both call chain_ops.h for every
+// step but the rotator product), organised for throughput instead of generality:
 //   * three passes through LDS instead of five: FIR | lerp + derotation | lerp + derotation -> global;
 //   * the derotation exp(1i*k*c) (FCCH_fine_correction.m:165, carrier_correct_post_SCH.m:83) comes from a per-tile
-//     two-level rotator table, exp(1i*k*c) = S * A[(k-k0)>>5] * B[(k-k0)&31] with S = exp(1i*fl(k0*c)),
+//     two-level rotator table (tile_rot_fill, tile_rot_s), exp(1i*k*c) = S * A[(k-k0)>>5] * B[(k-k0)&31] with S = exp(1i*fl(k0*c)),
 //     A[j] = exp(1i*fl(32j*c)), B[m] = exp(1i*fl(m*c)) -- 66 accurate sincos per tile instead of two per sample.  The
 //     reference rounds k*c once; the three rounded pieces differ from that by < 2 ulp(k*c) ~ 3e-11 rad at k = 1e6,
 //     far inside the 2e-8 stream tolerance (the argument of the reference's own exp carries the same uncertainty
@@ -1028,12 +823,6 @@ __host__ __device__ inline size_t stream_tile_lds(int ntaps) {
            2 * (68 + 34) * sizeof(cplx);     // (taps padded to a multiple of four; per derotation S|A|B and the tile's S*A[q])
 }
 
-// T[0], T[1] = S of the current / next tile, T[2..35] = A[0..33], T[36..67] = B[0..31]
-__device__ __forceinline__ cplx st_rot(const cplx* T, int sidx, int m) {     // exp(1i*(k0+m)*c), 0 <= m < 34*32
-    const cplx sa = cmul(T[sidx], T[2 + (m >> 5)]);
-    return cmul(sa, T[36 + (m & 31)]);
-}
-
 struct StRange { long lo0, hi0, lo2, hi2, lo3; int L4, cnt0, cnt2; };
 template <int TILE = ST_TILE>
 __device__ __forceinline__ StRange st_range(long tile, long nq, long n0, long n2, double f1, double f3) {
@@ -1041,12 +830,9 @@ __device__ __forceinline__ StRange st_range(long tile, long nq, long n0, long n2
     r.lo3 = tile * TILE;
     r.L4 = (int)(nq - r.lo3 < TILE ? nq - r.lo3 : TILE);
     const long hi3 = r.lo3 + r.L4 - 1;
-    r.lo2 = (long)floor((double)r.lo3 * f3);
-    r.hi2 = (long)floor((double)hi3 * f3) + 1;
-    if (r.hi2 > n2 - 1) r.hi2 = n2 - 1;
-    r.lo0 = (long)floor((double)r.lo2 * f1);
-    r.hi0 = (long)floor((double)r.hi2 * f1) + 1;
-    if (r.hi0 > n0 - 1) r.hi0 = n0 - 1;
+    const LerpRange r2 = lerp_src_range(r.lo3, hi3, f3, n2), r0 = lerp_src_range(r2.lo, r2.hi, f1, n0);
+    r.lo2 = r2.lo; r.hi2 = r2.hi;
+    r.lo0 = r0.lo; r.hi0 = r0.hi;
     r.cnt0 = (int)(r.hi0 - r.lo0 + 1);
     r.cnt2 = (int)(r.hi2 - r.lo2 + 1);
     return r;
@@ -1057,17 +843,10 @@ template <int NTAPS>
 __global__ void __launch_bounds__(ST_THREADS) k_stream_tile(const StreamState* __restrict__ sts, StreamTileArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int s = blockIdx.y, tid = threadIdx.x;
-    const StreamState* st = sts + s;
-    // ---- chain (all fields fetched up front) ----
-    const long n0 = st->n0;
-    const double mr = st->mean_re, mi = st->mean_im;
-    int ty[NLEVELS]; double pa[NLEVELS]; long ln[NLEVELS];
-    ty[0] = OP_NONE; pa[0] = 0.0; ln[0] = n0;
-#pragma unroll
-    for (int j = 1; j < NLEVELS; ++j) { ty[j] = st->op[j].type; pa[j] = st->op[j].param; ln[j] = st->op[j].n; }
-    if (ty[1] != OP_LERP || ty[2] != OP_MIX || (ty[3] != OP_LERP && ty[3] != OP_COPY) || ty[4] != OP_MIX) return;
-    const double f1 = pa[1], c2 = pa[2], f3 = ty[3] == OP_COPY ? 1.0 : pa[3], c4 = pa[4];
-    const long nq = ln[4];
+    const StChain ch = st_chain(sts + s);
+    if (!ch.ok) return;
+    const long n0 = ch.n0, n2 = ch.n2, nq = ch.nq;
+    const double mr = ch.mr, mi = ch.mi, f1 = ch.f1, c2 = ch.c2, f3 = ch.f3, c4 = ch.c4;
     const long ntile = (nq + ST_TILE - 1) / ST_TILE;
     long tile = (long)blockIdx.x * ST_TPB;
     if (tile >= ntile) return;
@@ -1079,29 +858,19 @@ __global__ void __launch_bounds__(ST_THREADS) k_stream_tile(const StreamState* _
     cplx* buf0 = (cplx*)smem;                                   // level 0 (FIR output)
     cplx* buf1 = buf0 + bufn;                                   // level 2 (after lerp + derotation); aliases xs
     cplx* xs = buf1;
-    double* c_s = (double*)(buf1 + (xs_n > bufn ? xs_n : bufn));   // rev[j] = coef[ntp-1-j] (oldest tap first), zero-padded to ntp4
-    const int ntp4 = (ntp + 3) & ~3;
+    double* c_s = (double*)(buf1 + (xs_n > bufn ? xs_n : bufn));   // the taps as fir_stage_taps leaves them
     unsigned short* r_s = (unsigned short*)(c_s + ((ntp + 7) & ~3));
     cplx* T2 = (cplx*)(r_s + ((span_max + 7) & ~(size_t)7));
-    cplx* T4 = T2 + 68;
-    cplx* SA2 = T4 + 68;                                        // S*A[q] of the current tile, q < 34, per derotation
+    cplx* T4 = T2 + TR_N;
+    cplx* SA2 = T4 + TR_N;                                      // S*A[q] of the current tile, q < 34, per derotation
     cplx* SA4 = SA2 + 34;
     const unsigned short* base = (const unsigned short*)(a.raw + (size_t)s * a.raw_stride);
-    const long ao = (long)(((uintptr_t)base >> 1) & 7);         // samples past a 16-byte boundary at g = 0
+    const long ao = raw_align_off(base);
     // ---- once per workgroup: taps, the stream's A/B rotator tables, the first tile's S and raw bytes ----
-    for (int i = tid; i < ntp4; i += ST_THREADS) c_s[i] = i < ntp ? a.coef[ntp - 1 - i] : 0.0;
-    StRange rg = st_range(tile, nq, n0, ln[2], f1, f3);
-    if (tid >= 64 && tid < 64 + 2 * 66) {                       // A[j] = exp(1i*fl(32j*c)), B[m] = exp(1i*fl(m*c)) for both derotations
-        const int i = (tid - 64) % 66, which = (tid - 64) / 66;
-        const double c = which ? c4 : c2;
-        double sn, cs;
-        sincos_large(i < 34 ? (double)(32 * i) * c : (double)(i - 34) * c, &sn, &cs);
-        (which ? T4 : T2)[2 + i] = make_double2(cs, sn);
-    } else if (tid < 2) {                                       // S = exp(1i*fl(k0*c)) of the first tile
-        double sn, cs;
-        sincos_large(tid ? (double)rg.lo3 * c4 : (double)rg.lo2 * c2, &sn, &cs);
-        (tid ? T4 : T2)[0] = make_double2(cs, sn);
-    }
+    fir_stage_taps(c_s, a.coef, ntp, tid, ST_THREADS);
+    StRange rg = st_range(tile, nq, n0, n2, f1, f3);
+    if (tid >= 64 && tid < 64 + 2 * 66) tile_rot_fill(T2, T4, c2, c4, tid - 64);      // A and B of both derotations
+    else if (tid < 2) (tid ? T4 : T2)[0] = tile_rot_s(tid, rg.lo2, rg.lo3, c2, c4);   // S of the first tile
     long first = rg.lo0 - (ntp - 1);
     long first_al = stage_raw(r_s, base, n0, first, rg.cnt0 + ntp - 1, tid, ST_THREADS);
     __syncthreads();
@@ -1109,18 +878,8 @@ __global__ void __launch_bounds__(ST_THREADS) k_stream_tile(const StreamState* _
     for (; tile < tile_end; ++tile) {
         const int cnt0 = rg.cnt0, cnt2 = rg.cnt2, L4 = rg.L4;
         const long lo0 = rg.lo0, lo2 = rg.lo2, lo3 = rg.lo3;
-        {   // raw2iq.m:6-8 on the staged span
-            const int span = cnt0 + ntp - 1, off = (int)(first - first_al);
-            for (int i = tid; i < span + 12; i += ST_THREADS) {       // (+12: finite zeros behind the span for the padding taps)
-                const long g = first + i;
-                cplx v = make_double2(0.0, 0.0);
-                if (i < span && g >= 0 && g < n0) {
-                    const unsigned short q = r_s[off + i];
-                    v = make_double2((double)(q & 0xFF) - mr, (double)(q >> 8) - mi);
-                }
-                xs[xs_pad(i)] = v;
-            }
-        }
+        // raw2iq.m:6-8 on the staged span (12 finite zeros behind it for the padding taps)
+        raw_span_to_lds(xs, r_s, (int)(first - first_al), first, cnt0 + ntp - 1, 12, n0, mr, mi, false, tid, ST_THREADS);
         __syncthreads();                                        // xs complete; r_s is free again
         // ---- the next tile's raw bytes (one 16-byte chunk per lane) and S: issued now, they land under the FIR ----
         StRange nx = rg;
@@ -1129,94 +888,41 @@ __global__ void __launch_bounds__(ST_THREADS) k_stream_tile(const StreamState* _
         int nchunk = 0;
         const bool more = tile + 1 < tile_end;
         if (more) {
-            nx = st_range(tile + 1, nq, n0, ln[2], f1, f3);
+            nx = st_range(tile + 1, nq, n0, n2, f1, f3);
             nfirst = nx.lo0 - (ntp - 1);
-            long m = (nfirst + ao) % 8;
-            if (m < 0) m += 8;
-            nfirst_al = nfirst - m;
-            nchunk = (int)((nfirst + nx.cnt0 + ntp - 1 - nfirst_al + 7) >> 3);
-            if (tid < nchunk) {
-                const long g0 = nfirst_al + 8L * tid;
-                if (g0 >= 0 && g0 + 8 <= n0) pre = *(const uint4*)(base + g0);
-                else {
-                    unsigned short q[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) q[i] = (g0 + i >= 0 && g0 + i < n0) ? base[g0 + i] : (unsigned short)0;
-                    pre.x = q[0] | ((unsigned)q[1] << 16); pre.y = q[2] | ((unsigned)q[3] << 16);
-                    pre.z = q[4] | ((unsigned)q[5] << 16); pre.w = q[6] | ((unsigned)q[7] << 16);
-                }
-            }
+            nfirst_al = raw_first_al(nfirst, ao);
+            nchunk = raw_nchunk(nfirst, nx.cnt0 + ntp - 1, nfirst_al);
+            if (tid < nchunk) pre = ffast_chunk(base, nfirst_al + 8L * tid, n0);
         }
-        // ---- pass 1: filter(coef,1,.) -> buf0, four consecutive outputs per lane, oldest tap first (gather_core's loop).
-        // (Two outputs per lane with twice the threads ran 40 % slower: the LDS reads per FMA double.) ----
-        // The taps sit in LDS reversed and zero-padded to a multiple of four: no remainder loop (fma(0, x, acc) = acc for the
-        // finite samples staged behind the span, so the sums are those of the ntp-term loop bit for bit), and two trips per
-        // iteration let the sliding window rotate by renaming instead of eight register moves per trip.
+        // ---- pass 1: filter(coef,1,.) -> buf0, four consecutive outputs per lane, oldest tap first: fir4_lds, two trips per
+        // iteration.  (Two outputs per lane with twice the threads ran 40 % slower: the LDS reads per FMA double.) ----
         for (int i0 = 4 * tid; i0 < cnt0; i0 += 4 * ST_THREADS) {
-            double ar0 = 0.0, ai0 = 0.0, ar1 = 0.0, ai1 = 0.0, ar2 = 0.0, ai2 = 0.0, ar3 = 0.0, ai3 = 0.0;
-            cplx w0 = xs[xs_pad(i0)], w1 = xs[xs_pad(i0 + 1)], w2 = xs[xs_pad(i0 + 2)], w3 = xs[xs_pad(i0 + 3)];
-#define ST_FIR_TAP(C, A, B, D, E)                                   \
-            ar0 = fma(C, A.x, ar0); ai0 = fma(C, A.y, ai0);         \
-            ar1 = fma(C, B.x, ar1); ai1 = fma(C, B.y, ai1);         \
-            ar2 = fma(C, D.x, ar2); ai2 = fma(C, D.y, ai2);         \
-            ar3 = fma(C, E.x, ar3); ai3 = fma(C, E.y, ai3);
-#pragma unroll 2
-            for (int t = 0; t < ntp4; t += 4) {
-                const cplx* nxs = xs + xs_pad(i0 + t + 4);
-                const cplx n0s = nxs[0], n1s = nxs[1], n2s = nxs[2], n3s = nxs[3];
-                const double c0 = c_s[t], c1 = c_s[t + 1], c2_ = c_s[t + 2], c3 = c_s[t + 3];
-                ST_FIR_TAP(c0, w0, w1, w2, w3)
-                ST_FIR_TAP(c1, w1, w2, w3, n0s)
-                ST_FIR_TAP(c2_, w2, w3, n0s, n1s)
-                ST_FIR_TAP(c3, w3, n0s, n1s, n2s)
-                w0 = n0s; w1 = n1s; w2 = n2s; w3 = n3s;
-            }
-#undef ST_FIR_TAP
-            buf0[i0] = make_double2(ar0, ai0);
-            if (i0 + 1 < cnt0) buf0[i0 + 1] = make_double2(ar1, ai1);
-            if (i0 + 2 < cnt0) buf0[i0 + 2] = make_double2(ar2, ai2);
-            if (i0 + 3 < cnt0) buf0[i0 + 3] = make_double2(ar3, ai3);
+            cplx y0, y1, y2, y3;
+            fir4_lds<NTAPS, true, 2>(xs, c_s, i0, ntp, &y0, &y1, &y2, &y3);
+            fir4_store(buf0, i0, cnt0, y0, y1, y2, y3);
         }
         if (more) {                                             // the prefetched bytes go to LDS; the next tile's S to the other slot
             if (tid < nchunk) *(uint4*)(r_s + 8 * tid) = pre;
-            for (int cch = tid + ST_THREADS; cch < nchunk; cch += ST_THREADS) {   // (spans beyond 2048 samples: long filters)
-                const long g0 = nfirst_al + 8L * cch;
-                unsigned short q[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) q[i] = (g0 + i >= 0 && g0 + i < n0) ? base[g0 + i] : (unsigned short)0;
-                uint4 v;
-                v.x = q[0] | ((unsigned)q[1] << 16); v.y = q[2] | ((unsigned)q[3] << 16);
-                v.z = q[4] | ((unsigned)q[5] << 16); v.w = q[6] | ((unsigned)q[7] << 16);
-                *(uint4*)(r_s + 8 * cch) = v;
-            }
+            for (int cch = tid + ST_THREADS; cch < nchunk; cch += ST_THREADS)     // (spans beyond 2048 samples: long filters)
+                *(uint4*)(r_s + 8 * cch) = ffast_chunk(base, nfirst_al + 8L * cch, n0);
             if (tid >= ST_THREADS - 2) {
-                double sn, cs;
-                sincos_large(tid == ST_THREADS - 1 ? (double)nx.lo3 * c4 : (double)nx.lo2 * c2, &sn, &cs);
-                (tid == ST_THREADS - 1 ? T4 : T2)[sidx ^ 1] = make_double2(cs, sn);
+                const int which = tid == ST_THREADS - 1;
+                (which ? T4 : T2)[sidx ^ 1] = tile_rot_s(which, nx.lo2, nx.lo3, c2, c4);
             }
         }
         // S * A[q] of this tile for both derotations (34 + 34 products), so that a sample's rotator is one product, SA[m>>5]*B[m&31]:
-        // the same three factors as st_rot(), associated the same way ((S*A)*B), bit-identical
+        // the three factors associated (S*A)*B
         if (tid >= 128 && tid < 128 + 68) {
             const int q = (tid - 128) % 34, which = (tid - 128) / 34;
             const cplx* T = which ? T4 : T2;
-            (which ? SA4 : SA2)[q] = cmul(T[sidx], T[2 + q]);
+            (which ? SA4 : SA2)[q] = cmul(T[sidx], T[TR_A + q]);
         }
         __syncthreads();                                        // (xs is dead: buf1 may be written)
         // ---- pass 2: level 1 = interp1 (FCCH_fine_correction.m:123-125), level 2 = .* exp(1i*k*c2) (:165) -> buf1 ----
         {
-            const double dlo2 = (double)lo2, dlo0 = (double)lo0;    // (indices < 2^53: the double sums and differences below are exact)
-            const int last0 = cnt0 - 1;
-            for (int i = tid; i < cnt2; i += ST_THREADS) {
-                const double xq = lerp_pos(dlo2 + (double)i, f1);   // interp_seq = (0:max_len-1)'.*(1+e)
-                const double j0f = floor(xq);
-                const int j0 = (int)(j0f - dlo0);
-                const int j1 = j0 + 1 > last0 ? last0 : j0 + 1; // beyond the last sample the weight is 0
-                const double t = xq - j0f;
-                const cplx v0 = buf0[j0], v1 = buf0[j1];
-                const cplx v = make_double2(v0.x + t * (v1.x - v0.x), v0.y + t * (v1.y - v0.y));
-                buf1[i] = cmul(v, cmul(SA2[i >> 5], T2[36 + (i & 31)]));
-            }
+            const double dlo2 = (double)lo2, dlo0 = (double)lo0;    // (indices < 2^53: the double sums are exact)
+            for (int i = tid; i < cnt2; i += ST_THREADS)
+                buf1[i] = cmul(lerp_at(buf0, dlo2 + (double)i, f1, dlo0, cnt0 - 1), cmul(SA2[i >> 5], T2[TR_B + (i & 31)]));
         }
         __syncthreads();
         // ---- pass 3: level 3 = interp1 (SCH_corr_rate_correction.m:126-127), level 4 = .* exp(1i*k*c4)
@@ -1224,17 +930,8 @@ __global__ void __launch_bounds__(ST_THREADS) k_stream_tile(const StreamState* _
         cplx* dst = a.dst + (size_t)s * a.dst_stream_stride + lo3;
         {
             const double dlo3 = (double)lo3, dlo2 = (double)lo2;
-            const int last2 = cnt2 - 1;
-            for (int i = tid; i < L4; i += ST_THREADS) {
-                const double xq = lerp_pos(dlo3 + (double)i, f3);
-                const double j0f = floor(xq);
-                const int j0 = (int)(j0f - dlo2);
-                const int j1 = j0 + 1 > last2 ? last2 : j0 + 1;
-                const double t = xq - j0f;
-                const cplx v0 = buf1[j0], v1 = buf1[j1];
-                const cplx v = make_double2(v0.x + t * (v1.x - v0.x), v0.y + t * (v1.y - v0.y));
-                st_stream16(dst + i, cmul(v, cmul(SA4[i >> 5], T4[36 + (i & 31)])));
-            }
+            for (int i = tid; i < L4; i += ST_THREADS)
+                st_stream16(dst + i, cmul(lerp_at(buf1, dlo3 + (double)i, f3, dlo2, cnt2 - 1), cmul(SA4[i >> 5], T4[TR_B + (i & 31)])));
         }
         __syncthreads();                                        // buf1 (= xs) and the tables' S slot may be rewritten
         rg = nx; first = nfirst; first_al = nfirst_al; sidx ^= 1;
@@ -1269,48 +966,6 @@ __host__ __device__ inline size_t stream_tile_s47_lds(int tile = ST47_TILE) {
     const size_t xs_n = st47_xs_n(tile), buf = st47_buf_n(tile);
     return (buf + (xs_n > buf ? xs_n : buf)) * sizeof(cplx) + 2 * 68 * sizeof(cplx);
 }
-// four consecutive outputs i0 .. i0+3 (i0 a multiple of 4) of the 47-tap symmetric filter from the padded copy xq; c[t] = coef[t], t < 24
-template <int S0, int G>
-__device__ __forceinline__ void fir4_sym47_load(const cplx* __restrict__ x0, cplx (&v)[G]) {
-#pragma unroll
-    for (int u = 0; u < G; ++u) { constexpr int dummy = 0; (void)dummy; const int sn = S0 + u; v[u] = x0[sn + (sn >> 2)]; }
-}
-template <int S0, int G>
-__device__ __forceinline__ void fir4_sym47_mac(const cplx (&v)[G], const double (&c)[24], double (&ar)[4], double (&ai)[4]) {
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-        const int s = S0 + u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int t = s - j;                          // output i0+j takes sample i0+s with tap rev[t] = coef[46-t] = coef[t]
-            if (t >= 0 && t < 47) {
-                const double cc = c[t < 24 ? t : 46 - t];
-                ar[j] = fma(cc, v[u].x, ar[j]);
-                ai[j] = fma(cc, v[u].y, ai[j]);
-            }
-        }
-    }
-}
-__device__ __forceinline__ void fir4_sym47(const cplx* __restrict__ xq, const double (&c)[24], int i0, cplx* y) {
-    double ar[4] = {0.0, 0.0, 0.0, 0.0}, ai[4] = {0.0, 0.0, 0.0, 0.0};
-    const cplx* x0 = xq + xs_pad(i0);                    // i0 % 4 == 0: xs_pad(i0 + s) = xs_pad(i0) + s + (s >> 2)
-    // ten groups of five samples in two register sets: the next group's LDS reads are issued ahead of this group's FMAs, and a
-    // scheduling barrier per group keeps the compiler from hoisting all fifty reads to the top (255 registers, one wave per SIMD)
-    constexpr int G = 5;
-    cplx A[G], B[G];
-    fir4_sym47_load<0, G>(x0, A);
-#define FIR47_PAIR(g)                                                   \
-    fir4_sym47_load<G * ((g) + 1), G>(x0, B);                           \
-    fir4_sym47_mac<G * (g), G>(A, c, ar, ai);                           \
-    __builtin_amdgcn_sched_barrier(0);                                  \
-    if ((g) + 2 < 50 / G) fir4_sym47_load<G * ((g) + 2), G>(x0, A);     \
-    fir4_sym47_mac<G * ((g) + 1), G>(B, c, ar, ai);                     \
-    __builtin_amdgcn_sched_barrier(0);
-    FIR47_PAIR(0) FIR47_PAIR(2) FIR47_PAIR(4) FIR47_PAIR(6) FIR47_PAIR(8)
-#undef FIR47_PAIR
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = make_double2(ar[j], ai[j]);
-}
 
 // what a tile needs to know about itself: worked out ONCE per workgroup for its ST_TPB tiles, one tile per lane, and read back
 // from LDS -- the ranges are floors of double products and 64-bit index arithmetic, which every lane of every wave would
@@ -1324,16 +979,10 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
     __shared__ cplx S2[ST_TPB], S4[ST_TPB];                     // exp(1i*fl(k0*c)) per tile and derotation
     constexpr int ntp = 47;
     const int s = blockIdx.y, tid = threadIdx.x;
-    const StreamState* st = sts + s;
-    const long n0 = st->n0;
-    const double mr = st->mean_re, mi = st->mean_im;
-    int ty[NLEVELS]; double pa[NLEVELS]; long ln[NLEVELS];
-    ty[0] = OP_NONE; pa[0] = 0.0; ln[0] = n0;
-#pragma unroll
-    for (int j = 1; j < NLEVELS; ++j) { ty[j] = st->op[j].type; pa[j] = st->op[j].param; ln[j] = st->op[j].n; }
-    if (ty[1] != OP_LERP || ty[2] != OP_MIX || (ty[3] != OP_LERP && ty[3] != OP_COPY) || ty[4] != OP_MIX) return;
-    const double f1 = pa[1], c2 = pa[2], f3 = ty[3] == OP_COPY ? 1.0 : pa[3], c4 = pa[4];
-    const long nq = ln[4];
+    const StChain ch = st_chain(sts + s);
+    if (!ch.ok) return;
+    const long n0 = ch.n0, n2 = ch.n2, nq = ch.nq;
+    const double mr = ch.mr, mi = ch.mi, f1 = ch.f1, c2 = ch.c2, f3 = ch.f3, c4 = ch.c4;
     const long ntile = (nq + TILE - 1) / TILE;
     const long tile0 = (long)blockIdx.x * ST_TPB;
     if (tile0 >= ntile) return;
@@ -1343,8 +992,8 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
     cplx* buf0 = (cplx*)smem;
     cplx* buf1 = buf0 + bufn;
     cplx* xs = buf1;
-    cplx* T2 = buf1 + (xs_n > bufn ? xs_n : bufn);              // T[2..35] = A[0..33], T[36..67] = B[0..31] (k_stream_tile's layout)
-    cplx* T4 = T2 + 68;
+    cplx* T2 = buf1 + (xs_n > bufn ? xs_n : bufn);              // tile_rot_fill's A | B per derotation (k_stream_tile's layout)
+    cplx* T4 = T2 + TR_N;
     const unsigned short* base = (const unsigned short*)(a.raw + (size_t)s * a.raw_stride);
     double cf[24];                                              // the taps (uniform addresses: scalar loads)
 #pragma unroll
@@ -1352,32 +1001,24 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
     // ---- once per workgroup: the tiles' ranges (lanes 0..), their S rotators (lanes 32..), the stream's A/B tables (lanes 64..) ----
     if (tid < ST_TPB) {
         if (tid < ntl) {
-            const StRange r = st_range<TILE>(tile0 + tid, nq, n0, ln[2], f1, f3);
+            const StRange r = st_range<TILE>(tile0 + tid, nq, n0, n2, f1, f3);
             StTile t;
             t.lo0 = r.lo0; t.lo2 = r.lo2; t.lo3 = r.lo3; t.cnt0 = r.cnt0; t.cnt2 = r.cnt2; t.L4 = r.L4;
             t.first = r.lo0 - (ntp - 1);
             t.first_al = raw_first_al(t.first, raw_align_off(base));
-            t.nchunk = (int)((t.first + r.cnt0 + ntp - 1 - t.first_al + 7) >> 3);
+            t.nchunk = raw_nchunk(t.first, r.cnt0 + ntp - 1, t.first_al);
             tl[tid] = t;
         }
     } else if (tid >= 32 && tid < 32 + 2 * ST_TPB) {
         const int t = (tid - 32) % ST_TPB, which = (tid - 32) / ST_TPB;
         if (t < ntl) {
-            const StRange r = st_range<TILE>(tile0 + t, nq, n0, ln[2], f1, f3);
-            double sn, cs;
-            sincos_large(which ? (double)r.lo3 * c4 : (double)r.lo2 * c2, &sn, &cs);
-            (which ? S4 : S2)[t] = make_double2(cs, sn);
+            const StRange r = st_range<TILE>(tile0 + t, nq, n0, n2, f1, f3);
+            (which ? S4 : S2)[t] = tile_rot_s(which, r.lo2, r.lo3, c2, c4);
         }
-    } else if (tid >= 64 && tid < 64 + 2 * 66) {
-        const int i = (tid - 64) % 66, which = (tid - 64) / 66;
-        const double c = which ? c4 : c2;
-        double sn, cs;
-        sincos_large(i < 34 ? (double)(32 * i) * c : (double)(i - 34) * c, &sn, &cs);
-        (which ? T4 : T2)[2 + i] = make_double2(cs, sn);
-    }
+    } else if (tid >= 64 && tid < 64 + 2 * 66) tile_rot_fill(T2, T4, c2, c4, tid - 64);
     __syncthreads();
     // B[m] of a lane's samples: i = tid + 256 k, so i & 31 = tid & 31 for every k -- one read per workgroup instead of one per sample
-    const cplx b2 = T2[36 + (tid & 31)], b4 = T4[36 + (tid & 31)];
+    const cplx b2 = T2[TR_B + (tid & 31)], b4 = T4[TR_B + (tid & 31)];
     // ... and so is A[i >> 5] for the lane's k-th sample of a pass, (tid >> 5) + 8 k: the products A*B of the lane's (up to) four
     // samples per pass live in registers for the whole workgroup, and a sample's rotator is S(tile) * (A*B) -- one product per
     // sample, no per-tile S*A table in LDS and no read of it per sample (stream mode 0.608 -> 0.594 ms).  (S*(A*B) instead of
@@ -1387,8 +1028,8 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
     cplx ab2[4], ab4[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        ab2[k] = cmul(T2[2 + (tid >> 5) + 8 * k], b2);
-        ab4[k] = cmul(T4[2 + (tid >> 5) + 8 * k], b4);
+        ab2[k] = cmul(T2[TR_A + (tid >> 5) + 8 * k], b2);
+        ab4[k] = cmul(T4[TR_A + (tid >> 5) + 8 * k], b4);
     }
     // the first tile's raw bytes: chunk `tid` (8 samples, 16-byte aligned) of [first_al, first + span)
     uint4 pre = make_uint4(0u, 0u, 0u, 0u);
@@ -1426,20 +1067,10 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
         // ---- pass 2: level 1 = interp1 (FCCH_fine_correction.m:123-125), level 2 = .* exp(1i*k*c2) (:165) -> buf1 ----
         {
             const double dlo0 = (double)lo0, p2 = (double)lo2 + (double)tid;   // (integers below 2^53: every sum here is exact)
-            const int last0 = cnt0 - 1;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                       // (cnt2 <= 4 * ST_THREADS: static register indices for ab2)
                 const int i = tid + k * ST_THREADS;
-                if (i < cnt2) {
-                    const double xq = lerp_pos(p2 + (double)(k * ST_THREADS), f1);
-                    const double j0f = floor(xq);
-                    const int j0 = (int)(j0f - dlo0);
-                    const int j1 = j0 + 1 > last0 ? last0 : j0 + 1;
-                    const double tt = xq - j0f;
-                    const cplx v0 = buf0[j0], v1 = buf0[j1];
-                    const cplx v = make_double2(v0.x + tt * (v1.x - v0.x), v0.y + tt * (v1.y - v0.y));
-                    buf1[i] = cmul(v, cmul(s2t, ab2[k]));
-                }
+                if (i < cnt2) buf1[i] = cmul(lerp_at(buf0, p2 + (double)(k * ST_THREADS), f1, dlo0, cnt0 - 1), cmul(s2t, ab2[k]));
             }
         }
         __syncthreads();
@@ -1447,20 +1078,10 @@ __global__ void __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu
         cplx* dst = a.dst + (size_t)s * a.dst_stream_stride + lo3;
         {
             const double dlo2 = (double)lo2, p3 = (double)lo3 + (double)tid;
-            const int last2 = cnt2 - 1;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int i = tid + k * ST_THREADS;
-                if (i < L4) {
-                    const double xq = lerp_pos(p3 + (double)(k * ST_THREADS), f3);
-                    const double j0f = floor(xq);
-                    const int j0 = (int)(j0f - dlo2);
-                    const int j1 = j0 + 1 > last2 ? last2 : j0 + 1;
-                    const double tt = xq - j0f;
-                    const cplx v0 = buf1[j0], v1 = buf1[j1];
-                    const cplx v = make_double2(v0.x + tt * (v1.x - v0.x), v0.y + tt * (v1.y - v0.y));
-                    st_stream16(dst + i, cmul(v, cmul(s4t, ab4[k])));
-                }
+                if (i < L4) st_stream16(dst + i, cmul(lerp_at(buf1, p3 + (double)(k * ST_THREADS), f3, dlo2, cnt2 - 1), cmul(s4t, ab4[k])));
             }
         }
         __syncthreads();                                        // buf1 (= xs) may be rewritten

@@ -84,7 +84,7 @@ def launches(names, part):
 @pytest.mark.parametrize("name,unaligned", CASES, ids=CASE_IDS)
 def test_batch_chain_against_the_oracle(g, streams, ts, profiled, name, unaligned):
     """Every row through parity.compare_stream, every corrected stream within 2e-8 of its peak.  (The one-tap case is the
-    one that found the contracted interpolation weight -- kernels_frontend.h lerp_pos: on unfiltered samples an ulp of the
+    one that found the contracted interpolation weight -- chain_ops.h lerp_pos: on unfiltered samples an ulp of the
     query position k*(1+e) moved the tone estimate by 2e-11 ppm and the end of r_correct by 4.3e-8 of its peak.)"""
     raw = gt.cut(streams, unaligned)
     coef = gt.FILTERS[name]
