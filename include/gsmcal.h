@@ -937,6 +937,89 @@ int gsmcal_apply_calibration_batch_resident(gsmcal_ctx* ctx, const uint8_t* d_ra
 int gsmcal_apply_params(const double* table_row, double tuned_freq, const double* iq_row, double delay, double phase, double scale,
                         double* params_row);
 
+/* ---- row_coherence: delay, phase and drift between any rows on one nominal time base -----------------------
+ * The project's own function: gsmcal_pair_coherence's estimator without the GSM carrier -- on any rows x: [d][stride] complex (the
+ * output rows of gsmcal_apply_calibration_batch, for instance), over a caller's list of windows of one length.  valid (host, may be
+ * NULL): [d][2] longs {first, end} per row, NULL = [0, stride) -- the first_valid, end_valid of apply_calibration's info table:
+ * outside them a row is exact zeros and is not correlated.  pairs (host): [P][2] row indices (a, b); lag0 (host): [P] ints, the
+ * expected offset of b's content against a's; starts (host): [W] longs, window starts in a's index, >= 0 and strictly ascending,
+ * 1 <= W <= GSMCAL_MAX_ROW_WINDOWS; 16 <= win_len <= 65536, Ls = floor(win_len / 4), K = 4: the 4 Ls first samples of a window
+ * are used; 1 <= max_lag M <= GSMCAL_MAX_ROW_LAG; min_coherence in [0, 1]; max_gap >= 0, samples; sample_rate fs finite and > 0.
+ * Per (pair, window), p = the window's start:
+ *   evaluated iff first_a <= p, p + 4 Ls <= end_a, first_b <= p + lag0 - M and p + lag0 + M + 4 Ls <= end_b (decided before a sample
+ *   is read; otherwise every column of the window is NaN, no error);
+ *   c[m][k], Ea[k], Eb[m][k], y[m], m*, edge, delay, theta, freq = theta fs / (2 pi Ls), phase and coherence: gsmcal_pair_coherence's
+ *   formulas with this Ls and this fs.
+ * Per pair, over the used windows (evaluated, not edge, coherence >= min_coherence), t = start - start of the first used window:
+ * gsmcal_pair_coherence's summaries, the phase steps taken between consecutive used windows at most max_gap samples apart.  Fewer
+ * than two used windows: GSMCAL_S_PAIR_FEW, the summaries NaN.
+ * out: [P][GSMCAL_ROW_COLS] doubles: columns 0..15 with the meaning of GSMCAL_P_* (column 1 is W), then win_len, sample_rate,
+ * min_coherence, max_gap, then GSMCAL_MAX_ROW_WINDOWS entries each of start, delay, phase, freq, coherence, edge (GSMCAL_R_*); entries
+ * at and beyond W are NaN.  corr (NULL to skip): [P][W][2M+1][4] complex, NaN where not evaluated.
+ * Order of the sums: a segment is cut into chunks of GSMCAL_ROW_CHUNK samples counted from its start; inside a chunk four interleaved
+ * partial sums over the samples = 0, 1, 2, 3 mod 4, each ascending with explicit fused multiply-adds, combined (s0 + s1) + (s2 + s3);
+ * the chunk sums are added in chunk order.  No atomics.  For Ls <= GSMCAL_ROW_CHUNK this is gsmcal_pair_coherence's own order: at
+ * win_len = 148 ov the correlations are its correlations bit for bit.
+ * A pair's row and corr block depend on its two rows, their valid intervals and the arguments alone: the same bits alone, at any
+ * place of any pair list (also when the pair is listed twice), from call to call, with or without corr and between the two forms.
+ * GSMCAL_E_ARG, decided before anything is enqueued and with the outputs untouched: a NULL required pointer; d, P, W, stride, win_len,
+ * M or sample_rate outside its range; a pair index outside [0, d); starts negative or not strictly ascending; a valid row with
+ * first < 0, end > stride or first > end; min_coherence outside [0, 1]; max_gap < 0 (or NaN).  The call keeps no state between calls
+ * (pairs, starts and valid are uploaded by every call).
+ * _resident: d_x, d_out and d_corr are device pointers (the outputs may be pinned host memory), everything else is a host array; it
+ * only enqueues on the context's stream; the lanes and every answer about the calibrate / scan call before stay untouched. */
+#define GSMCAL_MAX_ROW_WINDOWS 128      /* windows of one gsmcal_row_coherence_batch call */
+#define GSMCAL_MAX_ROW_LAG 64           /* its largest max_lag */
+#define GSMCAL_ROW_CHUNK 512            /* samples of one partial sum of a segment */
+#define GSMCAL_ROW_COLS (20 + 6 * GSMCAL_MAX_ROW_WINDOWS)   /* one row of gsmcal_row_coherence_batch[_resident]: 788 doubles */
+#define GSMCAL_R_STATUS 0               /* 0 or GSMCAL_S_PAIR_FEW                                                                  */
+#define GSMCAL_R_NUM_WINDOWS 1          /* W                                                                                       */
+#define GSMCAL_R_NUM_EVAL 2             /* windows both of whose spans lie inside the rows' valid intervals                        */
+#define GSMCAL_R_NUM_USED 3             /* evaluated, not at the edge of the lag range, coherence >= min_coherence                 */
+#define GSMCAL_R_NUM_ADJACENT 4         /* steps between consecutive used windows at most max_gap samples apart                    */
+#define GSMCAL_R_LAG0 5                 /* the pair's lag0, as given                                                               */
+#define GSMCAL_R_DELAY0 6               /* delay of b against a at the first used window, samples (the fitted line at t = 0)       */
+#define GSMCAL_R_REL_SAMPLING_PPM 7     /* 1e6 * slope of that line                                                                */
+#define GSMCAL_R_DELAY_RMS 8            /* rms of the delays about the line, samples                                               */
+#define GSMCAL_R_REL_CARRIER_HZ 9       /* carrier of b against a: window_carrier_hz refined by the adjacent phase steps           */
+#define GSMCAL_R_WINDOW_CARRIER_HZ 10   /* mean of freq[] over the used windows                                                    */
+#define GSMCAL_R_PHASE0 11              /* phase of b against a at the centre of the first used window, rad                        */
+#define GSMCAL_R_PHASE_RMS 12           /* rms of the used windows' phases about phase0 + 2 pi rel_carrier_hz t / fs, rad          */
+#define GSMCAL_R_MEAN_COHERENCE 13      /* mean of coherence[] over the used windows                                               */
+#define GSMCAL_R_MIN_COHERENCE_SEEN 14  /* ... and the smallest                                                                    */
+#define GSMCAL_R_MAX_LAG 15             /* M, as given                                                                             */
+#define GSMCAL_R_WIN_LEN 16             /* win_len, as given                                                                       */
+#define GSMCAL_R_SAMPLE_RATE 17         /* sample_rate, as given                                                                   */
+#define GSMCAL_R_MIN_COHERENCE 18       /* min_coherence, as given                                                                 */
+#define GSMCAL_R_MAX_GAP 19             /* max_gap, as given                                                                       */
+#define GSMCAL_R_START 20                                   /* [GSMCAL_MAX_ROW_WINDOWS] the window's start (NaN: not evaluated)    */
+#define GSMCAL_R_DELAY (20 + GSMCAL_MAX_ROW_WINDOWS)        /* [..] lag0 + m* + the parabola's offset, samples                     */
+#define GSMCAL_R_PHASE (20 + 2 * GSMCAL_MAX_ROW_WINDOWS)    /* [..] phase of b against a at the centre of the 4 Ls samples, rad    */
+#define GSMCAL_R_FREQ (20 + 3 * GSMCAL_MAX_ROW_WINDOWS)     /* [..] segment-to-segment phase step as a frequency, Hz               */
+#define GSMCAL_R_COH (20 + 4 * GSMCAL_MAX_ROW_WINDOWS)      /* [..] sum |c_k| / sqrt(sum Ea sum Eb), <= 1                          */
+#define GSMCAL_R_EDGE (20 + 5 * GSMCAL_MAX_ROW_WINDOWS)     /* [..] 1: the maximum sits at -M or +M (delay .. coherence NaN); 0    */
+int gsmcal_row_coherence_batch(gsmcal_ctx* ctx, const double* x, long stride, int d, const long* valid, const int* pairs, const int* lag0,
+                               int P, const long* starts, int W, int win_len, int max_lag, double min_coherence, double max_gap,
+                               double sample_rate, double* out, double* corr);
+int gsmcal_row_coherence_batch_resident(gsmcal_ctx* ctx, const double* d_x, long stride, int d, const long* valid, const int* pairs,
+                                        const int* lag0, int P, const long* starts, int W, int win_len, int max_lag, double min_coherence,
+                                        double max_gap, double sample_rate, double* d_out, double* d_corr);
+
+/* One row of the row_coherence table of the pair (reference, b), measured on the output rows of a first gsmcal_apply_calibration_batch
+ * pass, composed into the parameter row that produced row b: a second pass over the same bytes with params_out lands on the
+ * reference row's time base, carrier and phase (pure host arithmetic; no context needed).  With d1, s1 = 1e-6 slope_ppm, f1, phi1,
+ * A1 = delay, slope, carrier_hz, phase, anchor of params_in; s = 1e-6 rel_sampling_ppm, f = rel_carrier_hz, fs, Ls of coh_row; p0 =
+ * the start of its first used window (start not NaN, edge 0, coherence >= the row's min_coherence), n_c = p0 + (4 Ls - 1)/2 and
+ * Du = delay0 + s (A1 - p0):
+ *   delay' = d1 + Du (1 + s1),  slope_ppm' = 1e6 (s + s1 + s s1),  anchor' = A1,  carrier_hz' = (f1 + f)(1 + s),
+ *   phase' = phi1 + (2 pi f1 / fs) Du + phase0 + (2 pi f (1 + s) / fs)(A1 - n_c);  scale, dc and imbalance copied.
+ * (The second pass reads the capture at x1(u(n)), u(n) = n + delay0 + s (n - p0) the position in the first pass's row that belongs
+ * at n: the composition of two affine maps; the first pass's carrier was taken out at u, not at n, hence the term f1 Du; the
+ * (1 + s) is gsmcal_pair_align_params' reasoning.)  A coh_row whose status is not 0 or without a used window, or a value of
+ * params_in that is not finite: every value of params_out NaN but the copied scale, returns GSMCAL_S_ALIGN_SKIPPED; otherwise 0.
+ * GSMCAL_E_ARG: a NULL pointer, or |slope_ppm'| > 1000 (params_out is then all NaN but the scale). */
+int gsmcal_apply_params_refine(const double* coh_row, const double* params_in, double* params_out);
+
 /* ---- multi-GPU: one process per GPU, ONE collective ---------------------------------------------------------------
  * The reference has no distributed layer; units (dongle streams, ARFCN captures) are independent (gsm_sync_demod.m:112,
  * multi_rtl_sdr_gsm_FCCH_scanner.m:60-65,163), so ranks shard them block-contiguously and exchange only the result

@@ -9,7 +9,7 @@ valid Python identifier).  Sub-modules:
     build  -- hipcc build of csrc/ -> lib/libgsmcal.so
 """
 from . import build, ingest, synth  # noqa: F401
-from ._lib import GsmcalError, MAX_HITS, MAX_POS_ROWS, MAX_SUBBANDS, TABLE_COLS, DEMOD_COLS, MAX_BCCH, BCCH_COLS, SCH_COLS, SI_COLS, BLOCK_OCTETS, BLOCK_CODED, MAX_PAIR_BURSTS, PAIR_COLS, S_PAIR_FEW, MAX_ALIGN_MEMBERS, ALIGN_PARAMS, ALIGN_INFO_COLS, S_ALIGN_SKIPPED, MAX_COV_WINDOWS, COV_CHUNK, MAX_BEAMS, WEIGHTS_INFO_COLS, S_WEIGHTS_SINGULAR, APPLY_PARAMS, APPLY_INFO_COLS, HYPERFRAME, CW_MAX_EVENTS, CW_COLS, CW_TILE, CW_OK, CW_SHORT, CW_ZERO, IQ_COLS, IQ_TILE, IQ_MAX_N, IQ_OK, IQ_SHORT, IQ_FLAT, SIGNATURES, lib_path, load  # noqa: F401
+from ._lib import GsmcalError, MAX_HITS, MAX_POS_ROWS, MAX_SUBBANDS, TABLE_COLS, DEMOD_COLS, MAX_BCCH, BCCH_COLS, SCH_COLS, SI_COLS, BLOCK_OCTETS, BLOCK_CODED, MAX_PAIR_BURSTS, PAIR_COLS, S_PAIR_FEW, MAX_ALIGN_MEMBERS, ALIGN_PARAMS, ALIGN_INFO_COLS, S_ALIGN_SKIPPED, MAX_COV_WINDOWS, COV_CHUNK, MAX_BEAMS, WEIGHTS_INFO_COLS, S_WEIGHTS_SINGULAR, APPLY_PARAMS, APPLY_INFO_COLS, ROW_COLS, MAX_ROW_WINDOWS, MAX_ROW_LAG, ROW_CHUNK, HYPERFRAME, CW_MAX_EVENTS, CW_COLS, CW_TILE, CW_OK, CW_SHORT, CW_ZERO, IQ_COLS, IQ_TILE, IQ_MAX_N, IQ_OK, IQ_SHORT, IQ_FLAT, SIGNATURES, lib_path, load  # noqa: F401
 from .api import (  # noqa: F401
     Context, default_context, raw2iq, filter, chn_filter_8x_4x, chn_filter_4x, move_fft_snr_runtime_avg,
     specific_fft_snr_fix_avg, FCCH_coarse_position, FCCH_fine_correction, SCH_corr_rate_correction,
@@ -26,4 +26,6 @@ from .api import (  # noqa: F401
     pair_align, pair_align_batch, pair_align_batch_dev, pair_align_params, align_rows, coherent_combine, ALIGN_PARAM_FIELDS,
     ALIGN_INFO_FIELDS, array_covariance, array_covariance_dev, combine_weights, array_combine, array_combine_dev, burst_windows,
     WEIGHTS_INFO_FIELDS, apply_params, apply_calibration, apply_calibration_resident, apply_rows, APPLY_PARAM_FIELDS,
+    row_coherence, row_coherence_resident, row_rows, ROW_FIELDS, ROW_WINDOW_FIELDS, valid_of, apply_params_refine, row_lag_search,
+    retune_align,
 )

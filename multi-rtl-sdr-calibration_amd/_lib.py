@@ -44,6 +44,8 @@ MAX_COV_WINDOWS, COV_CHUNK = 256, 512   # windows of one array_covariance call; 
 MAX_BEAMS, WEIGHTS_INFO_COLS = 16, 4    # weight vectors of one array_combine call; info of combine_weights: status, lambda_1, lambda_2, sweeps
 S_WEIGHTS_SINGULAR = 18
 APPLY_PARAMS, APPLY_INFO_COLS = 10, 4   # one capture's parameter row of apply_calibration (api.APPLY_PARAM_FIELDS); one row of its info table
+MAX_ROW_WINDOWS, MAX_ROW_LAG, ROW_CHUNK = 128, 64, 512   # windows and largest max_lag of one row_coherence call; samples of one partial sum (GSMCAL_MAX_ROW_WINDOWS, ..)
+ROW_COLS = 20 + 6 * MAX_ROW_WINDOWS     # one row of row_coherence: twenty scalars (api.ROW_FIELDS), then start[], delay[], phase[], freq[], coherence[], edge[]
 HYPERFRAME = 2715648               # TDMA frames per GSM hyperframe: frame numbers wrap here
 
 # every extern "C" symbol include/gsmcal.h declares: (restype, argtypes)
@@ -134,6 +136,11 @@ SIGNATURES = {
     "gsmcal_apply_calibration_batch_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_double, c_double_p, C.c_long,
                                                           C.c_long, C.c_void_p, C.c_void_p]),
     "gsmcal_apply_params": (C.c_int, [c_double_p, C.c_double, c_double_p, C.c_double, C.c_double, C.c_double, c_double_p]),
+    "gsmcal_row_coherence_batch": (C.c_int, [C.c_void_p, c_double_p, C.c_long, C.c_int, c_long_p, c_int_p, c_int_p, C.c_int, c_long_p, C.c_int,
+                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, c_double_p, c_double_p]),
+    "gsmcal_row_coherence_batch_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, c_long_p, c_int_p, c_int_p, C.c_int, c_long_p,
+                                                      C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "gsmcal_apply_params_refine": (C.c_int, [c_double_p, c_double_p, c_double_p]),
     "gsmcal_total_ppm_calculation": (C.c_int, [c_double_p, C.c_int, c_double_p]),
     "gsmcal_frontend_batch": (C.c_int, [C.c_void_p, c_u8_p, C.c_int, C.c_long, c_double_p, C.c_int, C.c_int,
                                         c_double_p]),

@@ -34,7 +34,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, PAIR_COLS, MAX_PAIR_BURSTS, ALIGN_PARAMS, ALIGN_INFO_COLS, APPLY_PARAMS, APPLY_INFO_COLS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
+from ._lib import BCCH_COLS, SCH_COLS, SI_COLS, PAIR_COLS, MAX_PAIR_BURSTS, ALIGN_PARAMS, ALIGN_INFO_COLS, APPLY_PARAMS, APPLY_INFO_COLS, ROW_COLS, MAX_ROW_WINDOWS, BLOCK_OCTETS, BLOCK_CODED, CW_COLS, CW_MAX_EVENTS, IQ_COLS, DEMOD_COLS, MAX_BCCH, MAX_HITS, MAX_POS_ROWS, TABLE_COLS, GsmcalError
 
 _CTX = {}
 
@@ -1434,6 +1434,134 @@ def apply_calibration_resident(d_raw, d, n, params, sample_rate, out_len, out_st
     ctx.check(ctx.lib.gsmcal_apply_calibration_batch_resident(ctx.h, C.c_void_p(d_raw), int(d), int(n), float(sample_rate), _dp(pr),
                                                               int(out_len), int(out_stride), C.c_void_p(d_out), C.c_void_p(d_info)),
               "apply_calibration_batch_resident")
+
+
+ROW_FIELDS = ("status", "num_windows", "num_eval", "num_used", "num_adjacent", "lag0", "delay0", "rel_sampling_ppm", "delay_rms",
+              "rel_carrier_hz", "window_carrier_hz", "phase0", "phase_rms", "mean_coherence", "min_coherence_seen", "max_lag",
+              "win_len", "sample_rate", "min_coherence", "max_gap")                                   # columns 0..19 (GSMCAL_R_*)
+ROW_WINDOW_FIELDS = ("start", "delay", "phase", "freq", "coherence", "edge")
+
+
+def row_rows(table):
+    """(P, ROW_COLS) table of row_coherence[_resident] -> dict of its columns (start, delay, phase, freq, coherence, edge:
+    (P, MAX_ROW_WINDOWS), NaN at and beyond W and for windows that were not evaluated)."""
+    return _table_rows(table, ROW_COLS, ROW_FIELDS, ROW_WINDOW_FIELDS, MAX_ROW_WINDOWS)
+
+
+def _row_args_in(pairs, lag0, starts, win_len, max_gap, valid, d):
+    pr, lg, npairs = _pairs_in(pairs, lag0, d)
+    st = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).ravel())
+    if len(st) < 1:
+        raise ValueError("starts must hold at least one window start")
+    gap = 8.0 * int(win_len) if max_gap is None else float(max_gap)
+    va = None
+    if valid is not None:
+        va = np.ascontiguousarray(np.asarray(valid, dtype=np.int64).reshape(-1, 2))
+        if len(va) != d:
+            raise ValueError("valid must be (D, 2): {first, end} per row")
+    return pr, lg, npairs, st, gap, va
+
+
+def valid_of(info):
+    """apply_calibration's info (apply_rows' dict or the (D, APPLY_INFO_COLS) table) -> the (D, 2) int64 {first_valid, end_valid} that
+    row_coherence takes as `valid`"""
+    t = info if isinstance(info, dict) else apply_rows(info)
+    return np.stack([t["first_valid"], t["end_valid"]], axis=1).astype(np.int64)
+
+
+def row_coherence(x, pairs, starts, win_len, sample_rate, lag0=0, max_lag=16, min_coherence=0.5, max_gap=None, valid=None, want_corr=False,
+                  ctx=None):
+    """row_coherence -- the project's own function (include/gsmcal.h): pair_coherence's estimator on any rows
+    x (D, N) complex on one nominal time base (apply_calibration's output rows), over the windows starts (W,), 1 .. 128 of them,
+    ascending, each win_len samples (16 .. 65536) of which the 4 floor(win_len / 4) first are used.  pairs: (P, 2) row indices (a, b);
+    lag0: one int or one per pair, the expected offset of b's content against a's; max_lag M in 1 .. 64; max_gap (default 8 win_len):
+    the phase steps between consecutive used windows at most this many samples apart refine the carrier; valid: (D, 2) {first, end}
+    per row (valid_of(info) of apply_calibration), None = whole rows.  Returns the (P, ROW_COLS) table (row_rows names its columns;
+    status 0, or 16 = fewer than two used windows) -- or, with want_corr, a dict: "table", "corr" (P, W, 2M+1, 4) complex, NaN
+    where a window was not evaluated."""
+    ctx = ctx or default_context()
+    xa = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.complex128)))
+    d, stride = xa.shape
+    pr, lg, npairs, st, gap, va = _row_args_in(pairs, lag0, starts, win_len, max_gap, valid, d)
+    m = int(max_lag)
+    out = np.empty((npairs, ROW_COLS))
+    corr = np.empty((npairs, len(st), 2 * max(m, 0) + 1, 4), dtype=np.complex128) if want_corr else None
+    ctx.check(ctx.lib.gsmcal_row_coherence_batch(ctx.h, _dp(xa), stride, d, va.ctypes.data_as(_lib.c_long_p) if va is not None else None,
+                                                 pr.ctypes.data_as(_lib.c_int_p), lg.ctypes.data_as(_lib.c_int_p), npairs,
+                                                 st.ctypes.data_as(_lib.c_long_p), len(st), int(win_len), m, float(min_coherence), gap,
+                                                 float(sample_rate), _dp(out), _dp(corr) if want_corr else None), "row_coherence_batch")
+    if not want_corr:
+        return out
+    return {"table": out, "corr": corr}
+
+
+def row_coherence_resident(d_x, stride, d, pairs, starts, win_len, sample_rate, d_out, lag0=0, max_lag=16, min_coherence=0.5, max_gap=None,
+                           valid=None, d_corr=None, ctx=None):
+    """Device-pointer form of row_coherence: only enqueues on the context's stream, e.g. directly behind apply_calibration_resident on
+    its d_out (ctx.sync() before reading).  pairs, lag0, starts, valid: host arrays.  d_out: [P][ROW_COLS] doubles; optional d_corr:
+    [P][W][2M+1][4] complex.  Device or pinned host memory."""
+    ctx = ctx or default_context()
+    pr, lg, npairs, st, gap, va = _row_args_in(pairs, lag0, starts, win_len, max_gap, valid, int(d))
+    ctx.check(ctx.lib.gsmcal_row_coherence_batch_resident(ctx.h, C.c_void_p(d_x), int(stride), int(d),
+                                                          va.ctypes.data_as(_lib.c_long_p) if va is not None else None,
+                                                          pr.ctypes.data_as(_lib.c_int_p), lg.ctypes.data_as(_lib.c_int_p), npairs,
+                                                          st.ctypes.data_as(_lib.c_long_p), len(st), int(win_len), int(max_lag),
+                                                          float(min_coherence), gap, float(sample_rate), C.c_void_p(d_out), _opt(d_corr)),
+              "row_coherence_batch_resident")
+
+
+def apply_params_refine(coh_table, params):
+    """Rows of a row_coherence table of the pairs (reference, b), measured on the output rows of a first apply_calibration pass,
+    composed into the parameter rows that produced the rows b (gsmcal_apply_params_refine; pure host arithmetic, no context): a second
+    pass over the same bytes with the returned rows lands on the reference's time base, carrier and phase.  coh_table: (D, ROW_COLS),
+    params: (D, APPLY_PARAMS), row for row.  A coherence row whose status is not 0 gives an all-NaN row but the scale
+    (apply_calibration then skips that capture).  The reference's own row is refined by a coherence row of (ref, ref), which leaves it
+    unchanged up to rounding -- or keep its first-pass row."""
+    lib = _lib.load()
+    coh = np.ascontiguousarray(np.asarray(coh_table, dtype=np.float64).reshape(-1, ROW_COLS))
+    pr = _apply_params_in(params, len(coh))
+    out = np.empty_like(pr)
+    for i in range(len(coh)):
+        rc = lib.gsmcal_apply_params_refine(_dp(coh[i]), _dp(pr[i]), _dp(out[i]))
+        if rc < 0:
+            raise GsmcalError(f"apply_params_refine failed with {rc} ")
+    return out
+
+
+def row_lag_search(x, a, b, starts, win_len, sample_rate, lo, hi, max_lag=64, min_coherence=0.5, valid=None, ctx=None):
+    """The whole-sample offset of row b's content against row a's, searched over [lo, hi] by ONE row_coherence call: the pair (a, b)
+    repeated with lag0 tiled in steps of 2 max_lag - 1 (a maximum on a tile's edge lag is not used, so neighbouring tiles share their
+    edge lags).  Returns round(delay0) of the status-0 tile with the largest mean coherence, or None when no tile has status 0."""
+    m = int(max_lag)
+    lo, hi = int(lo), int(hi)
+    if hi < lo:
+        raise ValueError("row_lag_search: hi must be at least lo")
+    step = max(2 * m - 1, 1)
+    lags = np.arange(lo + m - 1, hi + m, step, dtype=np.int64)       # tile j covers the inner lags lag0 - (M - 1) .. lag0 + (M - 1)
+    t = row_rows(row_coherence(x, [(int(a), int(b))] * len(lags), starts, win_len, sample_rate, lag0=lags, max_lag=m,
+                               min_coherence=min_coherence, valid=valid, ctx=ctx))
+    ok = t["status"] == 0
+    if not ok.any():
+        return None
+    best = int(np.argmax(np.where(ok, t["mean_coherence"], -1.0)))
+    return int(np.floor(t["delay0"][best] + 0.5))
+
+
+def retune_align(raw, params, sample_rate, ref, starts, win_len, lag0=0, max_lag=16, min_coherence=0.5, max_gap=None, out_len=None, ctx=None):
+    """After a retune: apply_calibration(raw, params) -> row_coherence of every row against row `ref` over the windows `starts` ->
+    apply_params_refine -> apply_calibration again with the refined rows.  Returns (out, info, refined params, coherence table): out
+    and info of the second pass, the rows on ref's time base, carrier and phase; the coherence table (D, ROW_COLS) is the first
+    pass's, row i for the pair (ref, i).  The reference keeps its first-pass parameter row.  A row whose coherence status is not 0
+    is skipped by the second pass (info status 17, zeros)."""
+    ctx = ctx or default_context()
+    out, info = apply_calibration(raw, params, sample_rate, out_len=out_len, ctx=ctx)
+    d = out.shape[0]
+    table = row_coherence(out, [(int(ref), i) for i in range(d)], starts, win_len, sample_rate, lag0=lag0, max_lag=max_lag,
+                          min_coherence=min_coherence, max_gap=max_gap, valid=valid_of(info), ctx=ctx)
+    refined = apply_params_refine(table, params)
+    refined[int(ref)] = _apply_params_in(params, d)[int(ref)]
+    out2, info2 = apply_calibration(raw, refined, sample_rate, out_len=out_len, ctx=ctx)
+    return out2, info2, refined, table
 
 
 def split_spectrum_scan(s_all, start_freq, end_freq, freq_step, num_dongle, gain=0, observe_time=0.1, sample_rate=2.048e6,

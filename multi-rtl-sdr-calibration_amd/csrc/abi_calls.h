@@ -1450,6 +1450,101 @@ int gsmcal_apply_params(const double* table_row, double tuned_freq, const double
     return gsmcal_ap::apply_params(table_row, tuned_freq, iq_row, delay, phase, scale, params_row);
 }
 
+// ---- row_coherence: delay, phase and drift between any rows on one nominal time base --------------------------------------
+// k_row_xcorr (one workgroup per window and pair, one wave per segment, tiled over the segment) + k_row_finish (one wave per pair), in
+// rc_part.  valid, starts and pairs go through the context's staging vector and are uploaded by every call: no cache, no state a
+// later call could see.
+static_assert(gsmcal_ar::R_STATUS == GSMCAL_R_STATUS && gsmcal_ar::R_DELAY0 == GSMCAL_R_DELAY0 && gsmcal_ar::R_REL_SAMPLING_PPM == GSMCAL_R_REL_SAMPLING_PPM &&
+              gsmcal_ar::R_REL_CARRIER_HZ == GSMCAL_R_REL_CARRIER_HZ && gsmcal_ar::R_PHASE0 == GSMCAL_R_PHASE0 && gsmcal_ar::R_WIN_LEN == GSMCAL_R_WIN_LEN &&
+              gsmcal_ar::R_SAMPLE_RATE == GSMCAL_R_SAMPLE_RATE && gsmcal_ar::R_MIN_COHERENCE == GSMCAL_R_MIN_COHERENCE &&
+              gsmcal_ar::R_WINDOWS == GSMCAL_MAX_ROW_WINDOWS && gsmcal_ar::R_START == GSMCAL_R_START && gsmcal_ar::R_COH == GSMCAL_R_COH &&
+              gsmcal_ar::R_EDGE == GSMCAL_R_EDGE && gsmcal_ar::AP_PARAMS == GSMCAL_APPLY_PARAMS && gsmcal_ar::AP_SCALE == GSMCAL_AP_SCALE &&
+              gsmcal_ar::AP_ANCHOR == GSMCAL_AP_ANCHOR && gsmcal_ar::AR_SKIPPED == GSMCAL_S_ALIGN_SKIPPED && gsmcal_ar::AR_E_ARG == GSMCAL_E_ARG,
+              "apply_refine.h and include/gsmcal.h disagree");
+
+static int row_coherence_args(gsmcal_ctx* c, const void* x, long stride, int d, const long* valid, const int* pairs, const int* lag0, int P,
+                              const long* starts, int W, int win_len, int M, double min_coh, double max_gap, double fs, const void* out) {
+    if (!c) return GSMCAL_E_ARG;
+    const char* why = nullptr;
+    if (!x || !pairs || !lag0 || !starts || !out) why = "row_coherence: x, pairs, lag0, starts and out may not be NULL";
+    else if (d < 1 || P < 1 || stride < 1) why = "row_coherence: d, P and stride must be at least 1";
+    else if (W < 1 || W > GSMCAL_MAX_ROW_WINDOWS) why = "row_coherence: 1 .. GSMCAL_MAX_ROW_WINDOWS windows";
+    else if (win_len < 16 || win_len > 65536) why = "row_coherence: win_len must be 16 .. 65536";
+    else if (M < 1 || M > GSMCAL_MAX_ROW_LAG) why = "row_coherence: max_lag must be 1 .. GSMCAL_MAX_ROW_LAG";
+    else if (!std::isfinite(fs) || !(fs > 0.0)) why = "row_coherence: sample_rate must be finite and > 0";
+    else if (!(min_coh >= 0.0 && min_coh <= 1.0)) why = "row_coherence: min_coherence must be in [0, 1]";
+    else if (!(max_gap >= 0.0)) why = "row_coherence: max_gap must be >= 0";
+    for (int i = 0; i < 2 * P && !why; ++i)
+        if (pairs[i] < 0 || pairs[i] >= d) why = "row_coherence: a pair names a row outside the batch";
+    for (int i = 0; i < W && !why; ++i)
+        if (starts[i] < 0 || (i > 0 && starts[i] <= starts[i - 1])) why = "row_coherence: starts must be >= 0 and strictly ascending";
+    for (int i = 0; i < d && valid && !why; ++i)
+        if (valid[2 * i] < 0 || valid[2 * i + 1] > stride || valid[2 * i] > valid[2 * i + 1]) why = "row_coherence: a valid interval must be 0 <= first <= end <= stride";
+    if (why) { c->err = why; return GSMCAL_E_ARG; }
+    return 0;
+}
+
+static int row_coherence_enqueue(gsmcal_ctx* c, const double* d_x, long stride, int d, const long* valid, const int* pairs, const int* lag0, int P,
+                                 const long* starts, int W, int win_len, int M, double min_coh, double max_gap, double fs, double* d_out,
+                                 double* d_corr) {
+    c->cur = &c->lanes[0];                              // the context's stream; the lane's buffers are not touched
+    std::vector<long>& h = c->rc_stage;
+    h.resize((size_t)2 * d + W + (size_t)3 * P);
+    for (int i = 0; i < d; ++i) { h[2 * i] = valid ? valid[2 * i] : 0; h[2 * i + 1] = valid ? valid[2 * i + 1] : stride; }
+    for (int i = 0; i < W; ++i) h[(size_t)2 * d + i] = starts[i];
+    long* hp = h.data() + (size_t)2 * d + W;
+    for (int i = 0; i < P; ++i) { hp[3 * i] = pairs[2 * i]; hp[3 * i + 1] = pairs[2 * i + 1]; hp[3 * i + 2] = lag0[i]; }
+    const size_t bytes = h.size() * sizeof(long);
+    RET_IF(ensure(c, c->rc_in, bytes));
+    RET_IF(ensure(c, c->rc_part, (size_t)P * W * PX_PART * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(c->rc_in.p, h.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    const long* dev = (const long*)c->rc_in.p;
+    double* part = (double*)c->rc_part.p;
+    const int Ls = win_len / 4, NL = 2 * M + 1, nj = (NL + 15) / 16;
+    for_capture_chunks(P, [&](long lo, int S) {
+        const RowIn in{dev, dev + (size_t)2 * d, dev + (size_t)2 * d + W + (size_t)3 * lo};
+        double* pp = part + (size_t)lo * W * PX_PART;
+        cplx* cc = d_corr ? (cplx*)d_corr + (size_t)lo * W * NL * PX_K : nullptr;
+        if (nj <= 1) row_xcorr_launch<1>(c, (const cplx*)d_x, stride, in, W, S, Ls, M, pp, cc);
+        else if (nj <= 2) row_xcorr_launch<2>(c, (const cplx*)d_x, stride, in, W, S, Ls, M, pp, cc);
+        else if (nj <= 3) row_xcorr_launch<3>(c, (const cplx*)d_x, stride, in, W, S, Ls, M, pp, cc);
+        else if (nj <= 5) row_xcorr_launch<5>(c, (const cplx*)d_x, stride, in, W, S, Ls, M, pp, cc);
+        else row_xcorr_launch<RX_MAX_NJ>(c, (const cplx*)d_x, stride, in, W, S, Ls, M, pp, cc);
+    });
+    const RowIn in{dev, dev + (size_t)2 * d, dev + (size_t)2 * d + W};
+    const RowPar par{(double)win_len, fs, min_coh, max_gap};
+    LAUNCH(c, k_row_finish, dim3((unsigned)P), dim3(64), 0, in, W, Ls, M, par, (const double*)part, d_out);
+    CHECK_LAUNCH(c);
+    return 0;
+}
+
+int gsmcal_row_coherence_batch_resident(gsmcal_ctx* c, const double* d_x, long stride, int d, const long* valid, const int* pairs, const int* lag0,
+                                        int P, const long* starts, int W, int win_len, int max_lag, double min_coh, double max_gap, double fs,
+                                        double* d_out, double* d_corr) {
+    RET_IF(row_coherence_args(c, d_x, stride, d, valid, pairs, lag0, P, starts, W, win_len, max_lag, min_coh, max_gap, fs, d_out));
+    ENTER(c);
+    return row_coherence_enqueue(c, d_x, stride, d, valid, pairs, lag0, P, starts, W, win_len, max_lag, min_coh, max_gap, fs, d_out, d_corr);
+}
+
+int gsmcal_row_coherence_batch(gsmcal_ctx* c, const double* x, long stride, int d, const long* valid, const int* pairs, const int* lag0, int P,
+                               const long* starts, int W, int win_len, int max_lag, double min_coh, double max_gap, double fs, double* out,
+                               double* corr) {
+    RET_IF(row_coherence_args(c, x, stride, d, valid, pairs, lag0, P, starts, W, win_len, max_lag, min_coh, max_gap, fs, out));
+    ENTER(c);
+    const Stage io[] = {STAGE(rc_x, (size_t)d * stride * sizeof(cplx), x, nullptr, 0),
+                        STAGE(rc_out, (size_t)P * GSMCAL_ROW_COLS * sizeof(double), nullptr, out, 0),
+                        STAGE(rc_corr, corr ? (size_t)P * W * (2 * max_lag + 1) * PX_K * sizeof(cplx) : 0, nullptr, corr, 0)};
+    RET_IF(stage_up(c, io));
+    RET_IF(row_coherence_enqueue(c, (const double*)c->rc_x.p, stride, d, valid, pairs, lag0, P, starts, W, win_len, max_lag, min_coh, max_gap, fs,
+                                 (double*)c->rc_out.p, corr ? (double*)c->rc_corr.p : nullptr));
+    return stage_down(c, io);
+}
+
+int gsmcal_apply_params_refine(const double* coh_row, const double* params_in, double* params_out) {
+    if (!coh_row || !params_in || !params_out) return GSMCAL_E_ARG;
+    return gsmcal_ar::apply_params_refine(coh_row, params_in, params_out);
+}
+
 // ---- a9 total_ppm_calculation ---------------------------------------------------------------------------
 int gsmcal_total_ppm_calculation(const double* ppm_in, int n, double* ppm_out) {
     if (!ppm_in || !ppm_out || n < 1) return GSMCAL_E_ARG;

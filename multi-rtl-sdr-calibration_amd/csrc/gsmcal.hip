@@ -38,8 +38,10 @@
 #include "kernels_align.h"
 #include "kernels_array.h"
 #include "kernels_apply.h"
+#include "kernels_rowcoh.h"
 #include "combine_weights.h"
 #include "apply_params.h"
+#include "apply_refine.h"
 #include "state.h"
 
 #define GSMCAL_VERSION "gsmcal-mi355x 0.1 (gfx950)"

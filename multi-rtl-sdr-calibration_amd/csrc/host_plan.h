@@ -85,12 +85,15 @@ struct CtxBufs {
     // apply_calibration (gsmcal_apply_calibration_batch*): the kernels' rows of this call, and the host wrapper's staging of the
     // output rows and the info table (its bytes go through stage_raw)
     DevBuf ap_rows, ap_out, ap_info;
+    // row_coherence (gsmcal_row_coherence_batch*): what this call uploads (valid intervals, starts, pairs), the per-window records, and
+    // the host wrapper's staging of x, the table and the correlations
+    DevBuf rc_in, rc_part, rc_x, rc_out, rc_corr;
     ALL_BUFS(CtxBufs, &coef, &ts, &cf, &table, &snrhit, &arr_in, &arr_out, &posinfo, &rlen, &misc, &tw, &csum_head, &tw_sch, &stage_raw,
              &stage_out, &bp_coef, &bp_state, &bp_part, &fd_tw, &fd_cf, &fd_part, &fd_in, &fd_len, &fd_pos, &fd_out, &bc_ts, &bc_corr, &bc_flag, &bc_out,
              &bc_corr_out, &bc_r, &bc_rlen, &sd_part, &sd_out, &sd_soft, &sd_u, &bd_part, &bd_tsc, &bd_out, &bd_oct, &bd_soft, &sb_taps, &sb_idx,
              &sb_state, &sb_part, &cw_state, &cw_part, &cw_rec, &cw_mean, &cw_in, &cw_r, &iq_part, &iq_in, &iq_par, &pc_pairs, &pc_part,
              &pc_out, &pc_corr, &pa_members, &pa_params, &pa_aligned, &pa_combined, &pa_info, &ac_rows, &ac_win, &ac_part, &ac_w, &ac_x,
-             &ac_cov, &ac_out, &ap_rows, &ap_out, &ap_info)
+             &ac_cov, &ac_out, &ap_rows, &ap_out, &ap_info, &rc_in, &rc_part, &rc_x, &rc_out, &rc_corr)
 };
 
 struct gsmcal_ctx : CtxBufs {
@@ -205,6 +208,7 @@ struct gsmcal_ctx : CtxBufs {
     std::vector<int> h_sb_idx, h_bd_tsc, h_pc_pairs, h_pa_members, h_ac_rows;
     std::vector<long> h_ac_win;
     std::vector<ApRow> ap_stage;             // apply_calibration: the rows of the call being enqueued (written and uploaded by every call; no cache)
+    std::vector<long> rc_stage;              // row_coherence: valid, starts and pairs of the call being enqueued (as ap_stage: no cache)
     int fd_tw_n = 0;
     int last_S = 0;
     // gsmcal_allgather_table_async: the collective on a side stream, behind / ahead of events on the context's stream
@@ -1468,3 +1472,8 @@ int positive_status(const StreamState& st, int stage) {
 
 }  // namespace
 
+// row_coherence: k_row_xcorr with NJ compile-time lag rounds per lane (abi_calls.h picks the smallest instantiation that holds 2 M + 1 lags)
+template <int NJ>
+void row_xcorr_launch(gsmcal_ctx* c, const cplx* d_x, long stride, const RowIn& in, int W, int S, int Ls, int M, double* part, cplx* corr) {
+    LAUNCH(c, (k_row_xcorr<NJ>), dim3((unsigned)W, (unsigned)S), dim3(PX_THREADS), 0, d_x, stride, in, Ls, M, part, corr);
+}

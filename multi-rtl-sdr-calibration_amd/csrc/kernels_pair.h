@@ -222,6 +222,73 @@ __device__ __forceinline__ PxBurst px_burst(const double* __restrict__ rec, bool
     return u;
 }
 
+// The per-pair summaries over the used bursts (windows) of one pair, shared by k_pair_finish and k_row_finish (kernels_rowcoh.h): one
+// wave, lane l holds the entries l (u0) and l + 64 (u1); k0, k1: the ballots of their `used`, at least two of them set; gap_limit:
+// the largest distance in samples between two consecutive used entries whose phase step refines the carrier; up, uph: LDS for the
+// used entries' p and phase in table order (one slot per entry).  Every sum over the entries is wave_sum: one fixed order.
+struct PxSummary {
+    double delay0 = NAN_D, ppm = NAN_D, drms = NAN_D, rel = NAN_D, fc = NAN_D, phase0 = NAN_D, prms = NAN_D, cmean = NAN_D, cmin = NAN_D;
+    int nadj = 0;
+};
+__device__ __forceinline__ PxSummary px_summaries(const PxBurst& u0, const PxBurst& u1, unsigned long long k0, unsigned long long k1,
+                                                  double gap_limit, double fs, int lane, double* up, double* uph) {
+    PxSummary s;
+    const int n = __popcll(k0) + __popcll(k1);
+    const double dn = (double)n;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int r0 = __popcll(k0 & below), r1 = __popcll(k0) + __popcll(k1 & below);      // ranks among the used bursts
+    if (u0.used) { up[r0] = u0.p; uph[r0] = u0.phase; }
+    if (u1.used) { up[r1] = u1.p; uph[r1] = u1.phase; }
+    __syncthreads();
+    const double p_first = up[0];
+    const double t0 = u0.p - p_first, t1 = u1.p - p_first;
+    // ---- the line of delay on t, two passes ----
+    const double tbar = wave_sum((u0.used ? t0 : 0.0) + (u1.used ? t1 : 0.0)) / dn;
+    const double dbar = wave_sum((u0.used ? u0.delay : 0.0) + (u1.used ? u1.delay : 0.0)) / dn;
+    const double a0 = t0 - tbar, a1 = t1 - tbar;
+    const double sxx = wave_sum((u0.used ? a0 * a0 : 0.0) + (u1.used ? a1 * a1 : 0.0));
+    const double sxy = wave_sum((u0.used ? a0 * (u0.delay - dbar) : 0.0) + (u1.used ? a1 * (u1.delay - dbar) : 0.0));
+    const double slope = sxy / sxx;
+    s.delay0 = dbar - slope * tbar;
+    s.ppm = 1e6 * slope;
+    const double q0 = u0.delay - (s.delay0 + slope * t0), q1 = u1.delay - (s.delay0 + slope * t1);
+    s.drms = sqrt(wave_sum((u0.used ? q0 * q0 : 0.0) + (u1.used ? q1 * q1 : 0.0)) / dn);
+    const double fc = wave_sum((u0.used ? u0.freq : 0.0) + (u1.used ? u1.freq : 0.0)) / dn;
+    s.fc = fc;
+    // ---- the phase steps between adjacent used bursts: lane l takes the steps l -> l + 1 and l + 64 -> l + 65 ----
+    double zr = 0.0, zi = 0.0, gs = 0.0;
+    int na = 0;
+    for (int h = 0; h < 2; ++h) {
+        const int i = lane + 64 * h;
+        if (i + 1 < n) {
+            const double gp = up[i + 1] - up[i];
+            if (gp <= gap_limit) {
+                double sn, cn;
+                sincos(uph[i + 1] - uph[i] - TWO_PI_D * fc * gp / fs, &sn, &cn);
+                zr += cn; zi += sn; gs += gp; ++na;
+            }
+        }
+    }
+    zr = wave_sum(zr); zi = wave_sum(zi); gs = wave_sum(gs);
+    s.nadj = (int)wave_sum_u32((unsigned)na);
+    const double rel = s.nadj > 0 ? fc + atan2(zi, zr) * fs / (TWO_PI_D * (gs / (double)s.nadj)) : fc;
+    s.rel = rel;
+    // ---- the phase at the first used burst ----
+    const double w0 = u0.phase - TWO_PI_D * rel * t0 / fs, w1 = u1.phase - TWO_PI_D * rel * t1 / fs;
+    double s0 = 0.0, c0 = 0.0, s1 = 0.0, c1 = 0.0;
+    if (u0.used) sincos(w0, &s0, &c0);
+    if (u1.used) sincos(w1, &s1, &c1);
+    const double phase0 = atan2(wave_sum(s0 + s1), wave_sum(c0 + c1));
+    s.phase0 = phase0;
+    double d0 = 0.0, d1 = 0.0;
+    if (u0.used) { double sn, cn; sincos(w0 - phase0, &sn, &cn); d0 = atan2(sn, cn); }
+    if (u1.used) { double sn, cn; sincos(w1 - phase0, &sn, &cn); d1 = atan2(sn, cn); }
+    s.prms = sqrt(wave_sum(d0 * d0 + d1 * d1) / dn);
+    s.cmean = wave_sum((u0.used ? u0.coh : 0.0) + (u1.used ? u1.coh : 0.0)) / dn;
+    s.cmin = px_wave_min(fmin(u0.used ? u0.coh : 2.0, u1.used ? u1.coh : 2.0));
+    return s;
+}
+
 __global__ void __launch_bounds__(64) k_pair_finish(const long* __restrict__ r_len, long stride, const double* __restrict__ pos_info,
                                                     int ov, int M, double min_coh, const int* __restrict__ pairs,
                                                     const double* __restrict__ part, double* __restrict__ out) {
@@ -259,76 +326,24 @@ __global__ void __launch_bounds__(64) k_pair_finish(const long* __restrict__ r_l
         o[GSMCAL_P_EDGE + j1] = u1.ev ? (u1.edge ? 1.0 : 0.0) : NAN_D;
     }
     if (run && n < 2) status = GSMCAL_S_PAIR_FEW;
-    const bool fit = status == 0;                                  // (uniform)
-    double delay0 = NAN_D, ppm = NAN_D, drms = NAN_D, rel = NAN_D, fc = NAN_D, phase0 = NAN_D, prms = NAN_D, cmean = NAN_D, cmin = NAN_D;
-    int nadj = 0;
-    if (fit) {
-        const double dn = (double)n;
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const int r0 = __popcll(k0 & below), r1 = __popcll(k0) + __popcll(k1 & below);      // ranks among the used bursts
-        if (u0.used) { up[r0] = u0.p; uph[r0] = u0.phase; }
-        if (u1.used) { up[r1] = u1.p; uph[r1] = u1.phase; }
-        __syncthreads();
-        const double p_first = up[0];
-        const double t0 = u0.p - p_first, t1 = u1.p - p_first;
-        // ---- the line of delay on t, two passes ----
-        const double tbar = wave_sum((u0.used ? t0 : 0.0) + (u1.used ? t1 : 0.0)) / dn;
-        const double dbar = wave_sum((u0.used ? u0.delay : 0.0) + (u1.used ? u1.delay : 0.0)) / dn;
-        const double a0 = t0 - tbar, a1 = t1 - tbar;
-        const double sxx = wave_sum((u0.used ? a0 * a0 : 0.0) + (u1.used ? a1 * a1 : 0.0));
-        const double sxy = wave_sum((u0.used ? a0 * (u0.delay - dbar) : 0.0) + (u1.used ? a1 * (u1.delay - dbar) : 0.0));
-        const double slope = sxy / sxx;
-        delay0 = dbar - slope * tbar;
-        ppm = 1e6 * slope;
-        const double q0 = u0.delay - (delay0 + slope * t0), q1 = u1.delay - (delay0 + slope * t1);
-        drms = sqrt(wave_sum((u0.used ? q0 * q0 : 0.0) + (u1.used ? q1 * q1 : 0.0)) / dn);
-        fc = wave_sum((u0.used ? u0.freq : 0.0) + (u1.used ? u1.freq : 0.0)) / dn;
-        // ---- the phase steps between adjacent used bursts: lane l takes the steps l -> l + 1 and l + 64 -> l + 65 ----
-        double zr = 0.0, zi = 0.0, gs = 0.0;
-        int na = 0;
-        for (int h = 0; h < 2; ++h) {
-            const int i = lane + 64 * h;
-            if (i + 1 < n) {
-                const double gp = up[i + 1] - up[i];
-                if (gp <= 1875.0 * (double)ov) {
-                    double sn, cn;
-                    sincos(uph[i + 1] - uph[i] - TWO_PI_D * fc * gp / fs, &sn, &cn);
-                    zr += cn; zi += sn; gs += gp; ++na;
-                }
-            }
-        }
-        zr = wave_sum(zr); zi = wave_sum(zi); gs = wave_sum(gs);
-        nadj = (int)wave_sum_u32((unsigned)na);
-        rel = nadj > 0 ? fc + atan2(zi, zr) * fs / (TWO_PI_D * (gs / (double)nadj)) : fc;
-        // ---- the phase at the first used burst ----
-        const double w0 = u0.phase - TWO_PI_D * rel * t0 / fs, w1 = u1.phase - TWO_PI_D * rel * t1 / fs;
-        double s0 = 0.0, c0 = 0.0, s1 = 0.0, c1 = 0.0;
-        if (u0.used) sincos(w0, &s0, &c0);
-        if (u1.used) sincos(w1, &s1, &c1);
-        phase0 = atan2(wave_sum(s0 + s1), wave_sum(c0 + c1));
-        double d0 = 0.0, d1 = 0.0;
-        if (u0.used) { double sn, cn; sincos(w0 - phase0, &sn, &cn); d0 = atan2(sn, cn); }
-        if (u1.used) { double sn, cn; sincos(w1 - phase0, &sn, &cn); d1 = atan2(sn, cn); }
-        prms = sqrt(wave_sum(d0 * d0 + d1 * d1) / dn);
-        cmean = wave_sum((u0.used ? u0.coh : 0.0) + (u1.used ? u1.coh : 0.0)) / dn;
-        cmin = px_wave_min(fmin(u0.used ? u0.coh : 2.0, u1.used ? u1.coh : 2.0));
-    }
+    PxSummary s;
+    if (status == 0) s = px_summaries(u0, u1, k0, k1, 1875.0 * (double)ov, fs, lane, up, uph);    // (uniform)
     if (lane == 0) {
         o[GSMCAL_P_STATUS] = (double)status;
         o[GSMCAL_P_NUM_BURSTS] = (double)nb;
         o[GSMCAL_P_NUM_EVAL] = (double)num_eval;
         o[GSMCAL_P_NUM_USED] = (double)n;
-        o[GSMCAL_P_NUM_ADJACENT] = (double)nadj;
+        o[GSMCAL_P_NUM_ADJACENT] = (double)s.nadj;
         o[GSMCAL_P_LAG0] = (double)lag0;
-        o[GSMCAL_P_DELAY0] = delay0;
-        o[GSMCAL_P_REL_SAMPLING_PPM] = ppm;
-        o[GSMCAL_P_DELAY_RMS] = drms;
-        o[GSMCAL_P_REL_CARRIER_HZ] = rel;
-        o[GSMCAL_P_BURST_CARRIER_HZ] = fc;
-        o[GSMCAL_P_PHASE0] = phase0;
-        o[GSMCAL_P_PHASE_RMS] = prms;
-        o[GSMCAL_P_MEAN_COHERENCE] = cmean;
-        o[GSMCAL_P_MIN_COHERENCE_SEEN] = cmin;
+        o[GSMCAL_P_DELAY0] = s.delay0;
+        o[GSMCAL_P_REL_SAMPLING_PPM] = s.ppm;
+        o[GSMCAL_P_DELAY_RMS] = s.drms;
+        o[GSMCAL_P_REL_CARRIER_HZ] = s.rel;
+        o[GSMCAL_P_BURST_CARRIER_HZ] = s.fc;
+        o[GSMCAL_P_PHASE0] = s.phase0;
+        o[GSMCAL_P_PHASE_RMS] = s.prms;
+        o[GSMCAL_P_MEAN_COHERENCE] = s.cmean;
+        o[GSMCAL_P_MIN_COHERENCE_SEEN] = s.cmin;
         o[GSMCAL_P_MAX_LAG] = (double)M;
     }
 }

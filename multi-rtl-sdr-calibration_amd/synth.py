@@ -531,6 +531,40 @@ def make_cw(n, step=0.7, amp=100.0, dc=(127.4, 127.6), noise=0.5, drops=(), seed
     return np.clip(np.floor(raw + 0.5), 0, 255).astype(np.uint8)
 
 
+def make_wideband(dongle=0, n=100000, sample_rate=2.048e6, tuned_freq=433.92e6, e_ppm=0.0, c_ppm=0.0, start=0.0, phase=0.0, tx_key=0,
+                  tones=96, band=0.3, amp=30.0, dc=(127.4, 127.6), noise=0.5, iq_gain=None, iq_phase_deg=None, seed=DEFAULT_SEED):
+    """One capture of a wide-band transmission at any centre frequency and sample rate, as a retuned dongle records it: returns (raw
+    uint8 interleaved I,Q of length 2n, truth dict).  The transmission of (seed, tx_key) is a sum of `tones` unit tones over sqrt(tones)
+    (unit power), their frequencies uniform in +-band/2 cycles per nominal sample, their phases uniform: s(t) = sum_i exp(j (2 pi nu_i t
+    + theta_i)) / sqrt(tones), t in nominal sample periods.  It is evaluated EXACTLY at the dongle's sample times -- there is no
+    interpolator in the generator, so what a resampler leaves is the resampler's.  make_stream's convention: dongle sample k is taken
+    at nominal time (start + k) / (1 + e), e = 1e-6 e_ppm, and turned by 2 pi f_off k / sample_rate + phase, f_off = 1e-6 c_ppm
+    tuned_freq.  Then amp, white Gaussian noise (standard deviation `noise` per component, from the generator of (seed, dongle)), the
+    I/Q imbalance (_iq_impair; both None: none), DC, rounding and clipping to bytes as in make_cw."""
+    txr = np.random.Generator(np.random.Philox(key=[int(seed) ^ 0x57494445, int(tx_key)]))
+    nu = txr.uniform(-0.5 * band, 0.5 * band, int(tones))
+    theta = txr.uniform(0.0, 2.0 * math.pi, int(tones))
+    rng = np.random.Generator(np.random.Philox(key=[int(seed), 0x5742 ^ (int(dongle) << 20)]))
+    e = 1e-6 * float(e_ppm)
+    f_off = 1e-6 * float(c_ppm) * float(tuned_freq)
+    y = np.empty(n, dtype=np.complex128)
+    for lo in range(0, n, 1 << 16):                                   # (the (chunk, tones) phase matrix stays small)
+        k = np.arange(lo, min(lo + (1 << 16), n), dtype=np.float64)
+        t = (float(start) + k) / (1.0 + e)
+        s_t = np.exp(1j * (2.0 * math.pi * np.outer(t, nu) + theta)).sum(axis=1) / math.sqrt(int(tones))
+        y[lo: lo + len(k)] = s_t * np.exp(1j * (2.0 * math.pi * f_off / float(sample_rate) * k + float(phase)))
+    y = float(amp) * y + float(noise) * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    if iq_gain is not None or iq_phase_deg is not None:
+        y = _iq_impair(y, iq_gain, iq_phase_deg)
+    raw = np.empty(2 * n, dtype=np.float64)
+    raw[0::2] = y.real + dc[0]
+    raw[1::2] = y.imag + dc[1]
+    raw = np.clip(np.floor(raw + 0.5), 0, 255).astype(np.uint8)
+    truth = {"e_ppm": float(e_ppm), "c_ppm": float(c_ppm), "f_off": f_off, "start": float(start), "phase": float(phase),
+             "sample_rate": float(sample_rate), "tuned_freq": float(tuned_freq), "tx_key": int(tx_key), "nu": nu, "theta": theta}
+    return raw, truth
+
+
 # ------------------------------------------------------------------------------------------------
 # Host twin of the device-side capture expansion (csrc/kernels_frontend.h: k_synth_expand).
 # ------------------------------------------------------------------------------------------------
